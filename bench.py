@@ -8,16 +8,21 @@ bz3_hip_decode_blocks_device (the inverse chain incl. the CRC check), i.e. the r
 bz3_encode_blocks / bz3_decode_blocks (src/libbz3.c:845-870) with device pointers.  value =
 input bytes of all ranks / 2^20 / (t_encode + t_decode).
 
-Wall budget.  One step over a GPU-filling batch of 256 MiB blocks takes minutes (the CM coder is a serial
-recurrence per block), so the requested --steps / --warmup are CLAMPED to what fits the wall budget
-(--budget-s, default 1500 s of the driver's 1800 s): at least one timed step always runs; a warmup step is
-only spent when a second step still fits.  The JSON line carries the steps / warmup actually run and the
-requested ones.  A watchdog thread prints the line with whatever has been measured so far if the hard
-deadline (--deadline-s) is reached while an optional extra leg is still running.
+Default batch: 768 blocks of 8 MiB per GPU (three per CU, the CM routing of the full-size batch), about 10 s per step,
+so that --steps can be honoured as given.  `--block-mib 256` is BASELINE.json's block size: a step of 768 x 256 MiB
+takes about 4.5 minutes (a 256 MiB block's CM coding is a serial recurrence of minutes whatever the batch).
 
-Two timed steps when the budget allows (both reported, with their spread; the first includes the first-call effects:
-workspace allocation).  NOTHING else runs on the host or the GPU during the timed steps (round 3 ran the CPU baseline as
-threads of this process during the second step, which slowed that step's front end 2.6x: profiles/r04_host_contention.json).
+Steps.  --warmup untimed steps run first, then exactly --steps timed steps (each reported in step_s, their mean as
+ms_per_step; without a warmup the first timed step includes the first-call effects: workspace allocation).  One step over
+a GPU-filling batch of 256 MiB blocks takes minutes (the CM coder is a serial recurrence per block): choose --steps by
+ms_per_step.  The wall budget (--budget-s) only decides which extra legs still run after the steps.  A watchdog thread
+prints the line with whatever has been measured so far if the hard deadline (--deadline-s) is reached while an optional
+extra leg is still running; it never cuts the warmup or timed steps short.  NOTHING else runs on the host or the GPU
+during the timed steps (round 3 ran the CPU baseline as threads of this process during the second step, which slowed
+that step's front end 2.6x: profiles/r04_host_contention.json).
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed, as .npy files (a fixed, seeded sample of
+a few blocks; see dump_outputs), so that two builds can be compared output for output on identical inputs.
 
 "cpu_baseline": the REAL reference (oracle/_ref) through its own bz3_encode_blocks / bz3_decode_blocks on min(cores, 64)
 host threads x 256 MiB blocks -- the same blocks the GPU coded, and the reference's coded bytes are compared with the GPU's
@@ -28,10 +33,10 @@ reference's own CLI caps -j at 64 (src/main.c:213) and its batch API is document
 
 Workload: "enwik-style" text = the word-bigram Markov chain over shakespeare.txt tokens of SURVEY.md 8d with 3.5 % of its
 tokens replaced by random [a-z0-9] strings (tests/datagen.py ENWIK_NOISE: the fraction at which 100,000,000 B compress to
-enwik8's 4.41 : 1 at the reference's default -b 16, etc/BENCHMARKS.md:45-47).  Eight independent 256 MiB texts are
+enwik8's 4.41 : 1 at the reference's default -b 16, etc/BENCHMARKS.md:45-47).  Eight independent block-sized texts are
 generated; block k is text k mod 8 with its 64 KiB pieces in a block-specific order.
 
-Extra legs after the timed region (rank 0, N=1 only, each only while the budget lasts), all in "configs":
+Extra legs after the timed region, only with --extras (rank 0, N=1 only, each only while the budget lasts), all in "configs":
   random      768 incompressible blocks (LZP and RLE decline, the coder emits ~1.004 bytes per byte), reference beside it;
   mixed       text, binary and incompressible blocks in ONE batch (the single CM launch lasts as long as its slowest
               block, and blocks the row-cache kernels give up are coded again: cm_blocks_given_up is reported);
@@ -72,15 +77,16 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 PMC_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")  # written from a rocprofv3 --pmc pass (tools/rocpd_summary.py --pmc)
-HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+HBM_PEAK_GBPS = 8000.0  # MI355X: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
 ALG_BYTES_ROUND_TRIP = 32.4  # 17.2 B/B encode + 15.2 B/B decode
 ALG_BYTES_BWT = 11.0
 CFG3_BYTES = 1_000_000_000  # BASELINE.json configs[2]: "enwik9 (1 GB), -b 256, single MI355X"
 CM_MODES = {"auto": -1, "full": 0, "rows": 1, "rows3": 2}
-
-# More hardware queues than the HIP runtime's default 4: the codec's rings use the group's stream + four side streams (api.hip device_count()
-# explains; it sets the same default when it initialises the runtime itself -- here torch does, so it has to be in the environment before that).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# --dump-outputs: a fixed, seeded sample of the last timed step's output (16 MiB of .npy at most, whatever the batch)
+DUMP_SEED = 20251015
+DUMP_BLOCKS = 8  # blocks sampled
+DUMP_HEAD = 4096  # leading bytes of each sampled block (the coded block's header and first symbols) ...
+DUMP_BYTES = 1 << 18  # ... and seeded positions after them, DUMP_BYTES per block in all
 
 # runs of their own whose last record rides along under config.recorded (never under config.legs)
 RECORDED_RUNS = {"cfg5_256x511MiB_round_trip": "r06_bench_cfg5_256x511MiB.json", "random_256x256MiB_round_trip": "r06_bench_random_256x256MiB.json"}
@@ -89,8 +95,9 @@ PHASE = {"name": "start-up", "fatal": True}  # where an exception would come fro
 T_START = time.perf_counter()
 RANK = int(os.environ.get("RANK", "0"))
 WORLD = int(os.environ.get("WORLD_SIZE", "1"))
-RESULT = {"line": None, "printed": False}  # the JSON line as far as it has been measured (rank 0)
+RESULT = {"line": None, "printed": False, "metric": None}  # the JSON line as far as it has been measured (rank 0)
 _PRINT_LOCK = threading.Lock()
+STEPS_DONE = threading.Event()  # the warmup and timed steps are over (the hard deadline waits for it)
 
 
 def parse():
@@ -98,9 +105,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=0)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, a fixed seeded sample of the blocks)")
     ap.add_argument("--blocks", type=int, default=int(os.environ.get("BZ3_BENCH_BLOCKS", "0")),
                     help="blocks per GPU (0 = default for the CM mode: one block per CU, three with the row-cache kernels + lean states)")
-    ap.add_argument("--block-mib", type=float, default=float(os.environ.get("BZ3_BENCH_BLOCK_MIB", "256")))
+    ap.add_argument("--block-mib", type=float, default=float(os.environ.get("BZ3_BENCH_BLOCK_MIB", "8")),
+                    help="block size of the timed batch in MiB (256 = BASELINE.json's metric: minutes per step)")
     ap.add_argument("--kind", default="text", choices=["text", "random"])
     ap.add_argument("--cm-mode", default=os.environ.get("BZ3_BENCH_CM_MODE", "auto"), choices=sorted(CM_MODES),
                     help="CM kernel variant (bz3_hip_set_cm_mode): auto = the library's policy; full = whole model in LDS, one block per CU; "
@@ -108,12 +118,14 @@ def parse():
     ap.add_argument("--lean", type=int, default=int(os.environ.get("BZ3_BENCH_LEAN", "-1")),
                     help="lean states (bz3_hip_set_lean_states): 1 = no per-state swap buffer, in-place CM encode (room for 3x256 blocks of 256 MiB); -1 = by block count")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("BZ3_BENCH_BUDGET_S", "1500")),
-                    help="wall budget from process start: steps/warmup are clamped and the extra legs skipped so that the run ends before it")
+                    help="wall budget from process start: the extra legs after the steps are skipped so that the run ends before it")
     ap.add_argument("--deadline-s", type=float, default=float(os.environ.get("BZ3_BENCH_DEADLINE_S", "1690")),
-                    help="hard deadline: the watchdog prints the JSON line as measured so far and exits")
+                    help="hard deadline: the watchdog prints the JSON line as measured so far and exits (not before the warmup and timed steps are done)")
     ap.add_argument("--lib", default=None, help="another build of libbzip3.so (same-box A/B of two code states; never used by the driver)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg3 / random legs")
+    ap.add_argument("--extras", action="store_true",
+                    help="after the timed steps, the extra legs, while --budget-s lasts (minutes more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no cpu_baseline (the reference on the host + byte parity of the first blocks)")
+    ap.add_argument("--no-extras", action="store_true", help="no extra legs even with --extras")
     ap.add_argument("--cpu-threads", type=int, default=64)
     ap.add_argument("--cpu-block-mib", type=float, default=0.0, help="CPU baseline block size (0 = the bench's block size)")
     ap.add_argument("--cfg3-bytes", type=int, default=CFG3_BYTES, help="size of the cfg3 leg (only BASELINE's 1,000,000,000 B at 256 MiB blocks is reported as cfg3)")
@@ -174,6 +186,16 @@ def progress(msg):
         print(f"[bench {elapsed():8.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+def fail_line(msg):
+    """Print the line with `msg` as its error (rank 0); nothing timed yet: a line that says so."""
+    if RESULT["line"] is None:
+        RESULT["line"] = {"metric": RESULT["metric"], "value": None, "unit": "MiB/s", "n_gpus": WORLD, "steps": 0, "warmup": 0,
+                          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "config": {"workload": "failed before the first timed step completed"}}
+    RESULT["line"]["error"] = msg
+    RESULT["line"]["failed_phase"] = PHASE["name"]
+    emit_line(final=False)
+
+
 def emit_line(final):
     """Print the JSON line once (rank 0)."""
     with _PRINT_LOCK:
@@ -189,11 +211,13 @@ def emit_line(final):
 
 def start_watchdog(deadline_s):
     """The C calls of a step cannot be interrupted from Python (signal handlers only run between bytecodes), but ctypes
-    releases the GIL, so a thread can: at the hard deadline it prints what has been measured and ends the process."""
+    releases the GIL, so a thread can: at the hard deadline (or when the steps end after it) it prints what has been
+    measured and ends the process."""
 
     def run():
         while elapsed() < deadline_s:
             time.sleep(min(5.0, max(0.1, deadline_s - elapsed())))
+        STEPS_DONE.wait()  # the requested steps always run in full: the deadline only cuts the extra legs
         if RANK == 0:
             if emit_line(final=False):
                 progress("hard deadline: JSON line printed with the legs measured so far")
@@ -205,11 +229,23 @@ def start_watchdog(deadline_s):
     t.start()
 
     def on_term(signum, frame):
-        if RANK == 0:
-            emit_line(final=False)
-        os._exit(0 if RESULT["printed"] or RANK != 0 else 3)
+        if RANK == 0 and not emit_line(final=False):
+            fail_line(f"terminated by signal {signum}")
+        os._exit(0 if RANK != 0 or RESULT["line"].get("value") is not None else 3)
 
     signal.signal(signal.SIGTERM, on_term)
+    # on_term runs only once the main thread is back in Python, and a step can sit in one ctypes call for minutes (a `timeout -k` would
+    # SIGKILL it first): the C-level handler also writes the signal number to this pipe at once, and a thread of its own acts on it
+    rfd, wfd = os.pipe()
+    os.set_blocking(wfd, False)
+    signal.set_wakeup_fd(wfd, warn_on_full_buffer=False)
+
+    def on_wakeup():
+        while True:
+            if int(signal.SIGTERM) in os.read(rfd, 64):
+                on_term(int(signal.SIGTERM), None)
+
+    threading.Thread(target=on_wakeup, daemon=True).start()
 
 
 # ---- synthetic data ------------------------------------------------------------------------------------------------
@@ -581,6 +617,7 @@ def cpu_worker(job_file):
 
 def main():
     a = parse()
+    RESULT["metric"] = f"MiB/s encode+decode round-trip, {a.block_mib:g} MiB blocks"
     if a.cpu_worker:
         return cpu_worker(a.cpu_worker)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -597,12 +634,7 @@ def main():
         sys.stderr.flush()
         msg = f"{type(e).__name__}: {str(e)[:400]}"
         if RANK == 0:
-            if RESULT["line"] is None:  # nothing timed yet: a line that says so
-                RESULT["line"] = {"metric": "MiB/s encode+decode round-trip, 256 MiB blocks", "value": None, "unit": "MiB/s", "n_gpus": WORLD, "steps": 0, "warmup": 0,
-                                  "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic", "config": {"workload": "failed before the first timed step completed"}}
-            RESULT["line"]["error"] = msg
-            RESULT["line"]["failed_phase"] = PHASE["name"]
-            emit_line(final=False)
+            fail_line(msg)
         # a failure in or before the timed steps or their verification invalidates the headline: non-zero exit, with the line printed
         # (an AssertionError is a correctness check that did not hold -- a block that failed to code, a round trip that changed the data: always fatal; anything
         # else after the first step has been timed AND verified leaves a valid headline: exit 0 with the error in the line)
@@ -620,6 +652,7 @@ def run(a):
 
     world, rank = WORLD, RANK
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    assert a.steps >= 1 and a.warmup >= 0, "--steps must be at least 1, --warmup at least 0"
     assert world == a.gpus, f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}, or without it (bench.py starts the ranks itself)"
     cuda = not a.emu
     if cuda:
@@ -658,6 +691,7 @@ def run(a):
     block_size = int(a.block_mib * (1 << 20))
     if a.leg == "cfg5":
         block_size = int(a.leg_block_mib * (1 << 20))
+        RESULT["metric"] = f"MiB/s encode+decode round-trip, {a.leg_block_mib:g} MiB blocks (leg {a.leg})"
         if a.blocks <= 0:
             nblk = cus  # 256 x 511 MiB + workspace is what fits beside the swap-buffer pool
     lean = a.lean == 1 or (a.lean < 0 and (nblk > cus or a.leg == "cfg5"))  # (cfg5: 256 x 511 MiB blocks with a swap buffer each would not fit)
@@ -738,14 +772,6 @@ def run(a):
             dist.barrier()
         dev_sync()
 
-    def agree(x):
-        """Rank 0's value of a number, on every rank (all ranks must take the same budget decisions)."""
-        if world == 1:
-            return x
-        t = torch.tensor([float(x)], dtype=torch.float64, device=device)
-        dist.broadcast(t, src=0)
-        return float(t.item())
-
     def max_over_ranks(x):
         if world == 1:
             return x
@@ -793,7 +819,9 @@ def run(a):
             parity_sample["how"] = f"skipped: {type(e).__name__}: {str(e)[:120]}"
             progress("parity sample " + parity_sample["how"])
 
-    def one_step(record=False):
+    def one_step(record=False, capture=False):
+        """One encode + decode of the whole batch.  capture: --dump-outputs' copy of the coded bytes between the two calls (the in-place
+        decode destroys them); returns the seconds it took, which the caller leaves out of the step's time."""
         sizes = (C.c_int32 * nblk)(*[block_size] * nblk)
         t0 = time.perf_counter()
         lib.bz3_hip_encode_blocks_device(states, ptrs, sizes, nblk)
@@ -813,6 +841,13 @@ def run(a):
             stage["front_end_ring"] = {"slots": (ring >> 16) & 0xFF, "window": ring & 0xFFFF, "workspace_handed_back": bool((ring >> 30) & 1), "two_threads": bool((ring >> 29) & 1)}
             if cpu_block == block_size and not coded_kept and not step_s and want_cpu and "coded" not in parity_sample:
                 keep_coded_sample(sizes)  # a few ms of device-to-device copies inside the timed region, first step only (the in-place decode destroys the coded bytes)
+        aside = 0.0
+        if capture:  # (every rank: rank 0 captures, the others wait for it at the barrier, all leave the interval out)
+            t_ = time.perf_counter()
+            if dump:
+                capture_coded(sizes)
+            barrier()
+            aside = time.perf_counter() - t_
         t2 = time.perf_counter()
         lib.bz3_hip_decode_blocks_device(states, ptrs, bsz, sizes, orig, nblk)
         t3 = time.perf_counter()
@@ -825,12 +860,51 @@ def run(a):
             stage["dec"] = {bzip3_amd.T_NAMES[j]: round(tm[j], 3) for j in range(6)}
             stage["t_enc_s"] = round(t1 - t0, 3)
             stage["t_dec_s"] = round(t3 - t2, 3)
+        return aside
 
-    # ---- steps under the wall budget: nothing else runs on the host or the GPU meanwhile ---------------------------------
-    extras_wanted = rank == 0 and world == 1 and not a.no_extras and not a.emu and not a.leg
+    # ---- --dump-outputs: a fixed, seeded sample of what the last timed step computed (rank 0's blocks) -----------------------
+    dump = {}
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+
+        rng_ = np.random.Generator(np.random.PCG64(DUMP_SEED))
+        dump["blocks"] = np.sort(rng_.choice(nblk, size=min(DUMP_BLOCKS, nblk), replace=False))
+        dump["u"] = np.sort(rng_.random(DUMP_BYTES - DUMP_HEAD))  # positions as fractions of a block's length: one sample for any length
+
+        def sample_positions(n):
+            return np.concatenate([np.minimum(np.arange(DUMP_HEAD), n - 1), (dump["u"] * n).astype(np.int64)])
+
+        def capture_coded(sizes):
+            dump["coded_sizes"] = np.array(list(sizes), dtype=np.float64)
+            dump["coded_sample"] = torch.stack([bufs[k][torch.as_tensor(sample_positions(sizes[k]), device=device)] for k in dump["blocks"]])
+
+    def dump_outputs(fingerprints):
+        """DIR/<name>.npy, float32 / float64 (exact: bytes and sizes below 2^24, fingerprints as two 32-bit halves):
+          coded_sizes           every block's coded length (what bz3_hip_encode_blocks_device returned)
+          sample_blocks         the DUMP_BLOCKS blocks sampled (a fixed, seeded choice)
+          coded_sample          their coded bytes: the first DUMP_HEAD, then DUMP_BYTES - DUMP_HEAD at fixed, seeded fractions of the length
+          decoded_sample        their decoded bytes (what bz3_hip_decode_blocks_device left in place), the same way over the block size
+          decoded_fingerprint   every decoded block's 64-bit fingerprint (the round-trip check's), high and low 32 bits"""
+        import numpy as np
+
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        pos = torch.as_tensor(sample_positions(block_size), device=device)
+        out = {
+            "coded_sizes": dump["coded_sizes"],
+            "sample_blocks": dump["blocks"].astype(np.float64),
+            "coded_sample": dump["coded_sample"].to(torch.float32).cpu().numpy(),
+            "decoded_sample": torch.stack([bufs[k][:block_size][pos] for k in dump["blocks"]]).to(torch.float32).cpu().numpy(),
+            "decoded_fingerprint": np.array([[f >> 32, f & 0xFFFFFFFF] for f in fingerprints], dtype=np.float64),
+        }
+        for name, arr in out.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
+        progress(f"outputs of the last timed step: {', '.join(out)} in {a.dump_outputs} ({sum(v.nbytes for v in out.values()) / 2 ** 20:.1f} MiB)")
+
+    # ---- the warmup and timed steps: nothing else runs on the host or the GPU meanwhile -----------------------------------
+    extras_wanted = rank == 0 and world == 1 and a.extras and not a.no_extras and not a.emu and not a.leg
     cpu_need = 2.6 * cpu_block / (4.5 * (1 << 20)) if want_cpu else 0.0  # ~4.5 MiB/s per thread and direction at 256 MiB blocks (BASELINE.md), with margin
-    reserve = (cpu_need + 40.0 if want_cpu else 0.0) + (330.0 if extras_wanted else 0.0) + 30.0  # reference process, legs that follow it, verification
     step_s = []
+    warmup_run = []
     # the workspace survives between the calls of the timed steps (a caller that runs GPU-filling lean batches back to back would ask for the same:
     # include/bz3_hip.h); it is handed back before the extra legs
     keep_ws = not a.emu and os.environ.get("BZ3_BENCH_KEEP_WS", "1") != "0"
@@ -843,7 +917,7 @@ def run(a):
 
     def build_line():
         """The JSON line from what has been timed so far (rank 0 keeps it in RESULT; every exit path prints it)."""
-        steps_run, timed, warmup_run = len(step_s), sum(step_s), 0
+        steps_run, timed = len(step_s), sum(step_s)
         total_bytes = world * nblk * block_size
         value = total_bytes * steps_run / 2 ** 20 / timed
         if rank == 0:
@@ -876,12 +950,12 @@ def run(a):
             if a.emu:
                 what = "16-symbol order-1 Markov (--emu: CPU emulation of the kernels, control-flow test only)"
             out = {
-                "metric": "MiB/s encode+decode round-trip, 256 MiB blocks" if not a.leg else f"MiB/s encode+decode round-trip, {block_size >> 20} MiB blocks (leg {a.leg})",
+                "metric": RESULT["metric"],
                 "value": round(value, 3),
                 "unit": "MiB/s",
                 "n_gpus": world,
                 "steps": steps_run,
-                "warmup": warmup_run,
+                "warmup": len(warmup_run),
                 "ms_per_step": round(timed / steps_run * 1e3, 1),
                 "step_s": [round(x, 2) for x in step_s],
                 "step_spread": round((max(step_s) - min(step_s)) / (timed / steps_run), 4),
@@ -891,8 +965,9 @@ def run(a):
                 "dtype": "u8",
                 "data": "synthetic",
                 "requested": {"steps": a.steps, "warmup": a.warmup, "budget_s": a.budget_s,
-                              "note": "steps/warmup clamped to the wall budget: one step codes and decodes a GPU-filling batch of 256 MiB blocks; both steps are timed, "
-                                      "the first one includes the first-call effects (workspace allocation); nothing else runs on the host or the GPU during the timed steps"},
+                              "note": f"the warmup steps, then the timed steps, as requested: one step codes and decodes a GPU-filling batch of {block_size / 2 ** 20:g} MiB blocks; without a warmup "
+                                      "the first timed step includes the first-call effects (workspace allocation); nothing else runs on the host or the GPU during the timed steps; "
+                                      "the budget only bounds the extra legs"},
                 "config": {
                     "workload": f"{nblk} x {block_size / 2 ** 20:g} MiB {what} blocks per GPU"
                                 + (f" (word-bigram Markov over shakespeare.txt tokens, {noise * 100:g} % noise tokens = enwik8's 4.41 : 1 at -b 16; {nbase} independent texts, "
@@ -940,7 +1015,7 @@ def run(a):
                 "stages": json.loads(json.dumps(stage)),
                 "gen_s": round(t_gen, 1),
                 "configs": {},
-                "cpu_baseline": {"value": None, "unit": "MiB/s", "cores": 0, "kind": "reference", "sample": "not run (budget, --no-cpu-baseline, --leg or N > 1)"},
+                "cpu_baseline": {"value": None, "unit": "MiB/s", "cores": 0, "kind": "reference", "sample": "not run (budget, --no-cpu-baseline or N > 1)"},
             }
             prev = RESULT["line"]
             if prev is not None:  # a line built after an earlier step: what has been measured beside the steps since then stays
@@ -973,59 +1048,67 @@ def run(a):
     front_duo = os.environ.get("BZ3_BENCH_FRONT_DUO", "")  # (experiments: "1" / "0" force the encoder's two-thread front end on / off; unset = the library's default)
     if front_duo in ("0", "1") and hasattr(lib, "bz3_hip_set_front_end_duo"):
         lib.bz3_hip_set_front_end_duo(int(front_duo))
-    PHASE["name"] = "first timed step"
-    inject("step1")
-    barrier()
-    t0 = time.perf_counter()
-    one_step(record=True)
-    barrier()
-    step_s.append(max_over_ranks(time.perf_counter() - t0))
 
     def verify_round_trip():
-        # the round trip must be the identity (decode is in place: the buffers hold the plaintext again)
+        """The round trip must be the identity (decode is in place: the buffers hold the plaintext again); returns the blocks' fingerprints."""
+        got = []
         for k in range(nblk):
-            assert fingerprint(torch, bufs[k][:block_size]) == prints[k], f"block {k}: round trip changed the data"
+            got.append(fingerprint(torch, bufs[k][:block_size]))
+            assert got[k] == prints[k], f"block {k}: round trip changed the data"
         for k in range(n_keep):
             assert torch.equal(bufs[k][:block_size], kept[k]), f"block {k}: round trip changed the data"
+        return got
 
-    build_line()  # from here on every exit path prints a line (the watchdog, SIGTERM, an exception)
-    PHASE["name"] = "verification of the first step's round trip"
-    inject("verify1")
-    verify_round_trip()
-    # the GPU's coded bytes of the parity sample go to shared memory NOW (outside the timed steps): 64 x ~50 MB of HBM that the second
-    # step's ring of LZP contexts can use
+    for w in range(a.warmup):
+        PHASE["name"] = f"warmup step {w + 1}"
+        barrier()
+        one_step()
+        barrier()
+        verify_round_trip()
+        warmup_run.append(w)
     shared_coded = parity_sample.get("coded")
-    if want_cpu and coded_kept:
-        try:
-            shared_coded = SharedBlocks("bz3_bench_coded", [int(c.numel()) for c in coded_kept])
-            for i, c in enumerate(coded_kept):
-                shared_coded.put_tensor(torch, i, c)
-        except Exception as e:
-            shared_coded = None
-            parity_sample["how"] = f"skipped: {type(e).__name__}: {str(e)[:120]}"
-        coded_kept.clear()
-        if cuda:
-            torch.cuda.empty_cache()
-    PHASE["fatal"] = False  # one step timed and verified: the headline stands whatever happens next (but see main(): assertions stay fatal)
-    left = agree(a.budget_s - elapsed()) - reserve
-    second = (a.steps >= 2 or a.warmup > 0) and left > step_s[0] * 1.03
-    if second:
-        PHASE["name"] = "second timed step"
-        inject("step2")
+    for i in range(a.steps):
+        last = i == a.steps - 1
+        nth = {0: "first", 1: "second"}.get(i, f"#{i + 1}")
+        PHASE["name"] = f"{nth} timed step"
+        inject(f"step{i + 1}")
         barrier()
         t0 = time.perf_counter()
-        one_step(record=True)
+        aside = one_step(record=True, capture=bool(a.dump_outputs) and last)
         barrier()
-        step_s.append(max_over_ranks(time.perf_counter() - t0))
-        build_line()
-        PHASE["name"] = "verification of the second step's round trip"
-        verify_round_trip()
+        step_s.append(max_over_ranks(time.perf_counter() - t0 - aside))
+        build_line()  # from here on every exit path prints a line (the watchdog, SIGTERM, an exception)
+        PHASE["name"] = f"verification of the {nth} timed step's round trip"
+        if i == 0:
+            inject("verify1")
+        fingerprints = verify_round_trip()
+        if i > 0:
+            continue
+        # the GPU's coded bytes of the parity sample go to shared memory NOW (outside the timed steps): 64 x ~50 MB of HBM that the next
+        # step's ring of LZP contexts can use
+        if want_cpu and coded_kept:
+            try:
+                shared_coded = SharedBlocks("bz3_bench_coded", [int(c.numel()) for c in coded_kept])
+                for j, c in enumerate(coded_kept):
+                    shared_coded.put_tensor(torch, j, c)
+            except Exception as e:
+                shared_coded = None
+                parity_sample["how"] = f"skipped: {type(e).__name__}: {str(e)[:120]}"
+            coded_kept.clear()
+            if cuda:
+                torch.cuda.empty_cache()
+        PHASE["fatal"] = False  # one step timed and verified: the headline stands whatever happens next (but see main(): assertions stay fatal)
+    if dump:
+        PHASE.update(name="--dump-outputs", fatal=True)  # outputs that were asked for and not written: the run failed
+        dump_outputs(fingerprints)
+        PHASE["fatal"] = False
+    STEPS_DONE.set()
     if keep_ws:
         lib.bz3_hip_set_keep_workspace(-1)
         lib.bz3_hip_release_cached_memory()
     build_line()
     steps_run = len(step_s)
-    progress(f"timed {steps_run} step(s): {[round(x, 1) for x in step_s]} s (requested {a.steps} / {a.warmup}; budget {a.budget_s:.0f}s)")
+    progress(f"timed {steps_run} step(s) after {len(warmup_run)} warmup step(s): {[round(x, 1) for x in step_s]} s")
     PHASE["name"] = "extra legs"
     inject("legs")
     if rank == 0 and not a.emu:

@@ -25,11 +25,14 @@ def shakespeare():
     if "txt" in _cache:
         return _cache["txt"]
     cache_file = "/tmp/bz3_shakespeare_%s.txt" % SHAKESPEARE_MD5[:8]
-    if os.path.exists(cache_file):
-        data = open(cache_file, "rb").read()
+    try:  # (a cache another user left in /tmp may not be readable: then the fixture is decoded again)
+        with open(cache_file, "rb") as fh:
+            data = fh.read()
         if hashlib.md5(data).hexdigest() == SHAKESPEARE_MD5:
             _cache["txt"] = data
             return data
+    except OSError:
+        pass
     from oracle_lib import Oracle
 
     o = Oracle()

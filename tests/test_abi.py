@@ -63,18 +63,31 @@ def test_block_size_validation_needs_no_device(lib):
 
 
 def test_fails_loudly_without_gpu(lib):
-    import torch
+    """In a process that sees no GPU (HIP_VISIBLE_DEVICES=-1, so the test runs on the GPU machine as well) the library counts no device
+    and refuses to work: no state, an exception from the wrapper, BZ3_ERR_INIT from the one-shot API."""
+    import subprocess
+    import sys
 
-    if torch.cuda.is_available():
-        pytest.skip("a GPU is present")
-    assert lib.bz3_hip_device_count() == 0
-    assert not lib.bz3_new(1 << 20)  # NULL, never a CPU fallback
-    with pytest.raises(RuntimeError):
-        bzip3_amd.State(1 << 20)
-    out = (C.c_size_t)(100)
-    src = (C.c_uint8 * 100)()
-    dst = (C.c_uint8 * 1000)()
-    assert lib.bz3_compress(1 << 20, src, dst, 100, C.byref(out)) == bzip3_amd.BZ3_ERR_INIT
+    child = """
+import ctypes as C
+import bzip3_amd
+lib = bzip3_amd.load()
+assert lib.bz3_hip_device_count() == 0
+assert not lib.bz3_new(1 << 20)  # NULL, never a CPU fallback
+try:
+    bzip3_amd.State(1 << 20)
+    raise AssertionError("bzip3_amd.State without a device did not raise")
+except RuntimeError:
+    pass
+out = C.c_size_t(100)
+src = (C.c_uint8 * 100)()
+dst = (C.c_uint8 * 1000)()
+assert lib.bz3_compress(1 << 20, src, dst, 100, C.byref(out)) == bzip3_amd.BZ3_ERR_INIT
+print("refused without a GPU")
+"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", child], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "refused without a GPU" in r.stdout, r.stderr[-2000:]
 
 
 def test_missing_extension_raises(tmp_path):
@@ -93,12 +106,15 @@ def test_product_never_touches_the_oracle():
 
 def test_prototypes_equal_the_reference_header_when_it_is_here():
     """include/libbz3.h is written for this implementation (reference sources stay out of the repository), so its 14 prototypes are
-    compared with the reference's own header token for token wherever the reference tree exists (the build container; not the GPU box)."""
+    compared token for token with the reference's own header, kept as data in tests/golden/libbz3_h_prototypes.json: the sha256 of each
+    prototype after the normalisation below, and the values of the error codes."""
+    import hashlib
+    import json
     import re
 
-    ref_path = "/root/reference/include/libbz3.h"
-    if not os.path.exists(ref_path):
-        pytest.skip("the reference tree is not on this machine")
+    with open(os.path.join(ROOT, "tests", "golden", "libbz3_h_prototypes.json")) as fh:
+        golden = json.load(fh)
+    header = os.path.join(ROOT, "include", "libbz3.h")
 
     def protos(path):
         text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
@@ -111,16 +127,14 @@ def test_prototypes_equal_the_reference_header_when_it_is_here():
             out[name] = decl
         return out
 
-    ours, theirs = protos(os.path.join(ROOT, "include", "libbz3.h")), protos(ref_path)
+    ours, theirs = protos(header), golden["prototype_sha256"]
     assert sorted(ours) == sorted(theirs) and len(theirs) == 14
     for name in theirs:
-        a = re.sub(r"\b\w+(?=[,)])", "", ours[name])    # parameter names may differ, types and order may not
-        b = re.sub(r"\b\w+(?=[,)])", "", theirs[name])
-        assert a == b, (name, ours[name], theirs[name])
-    for macro in ("BZ3_OK", "BZ3_ERR_OUT_OF_BOUNDS", "BZ3_ERR_BWT", "BZ3_ERR_CRC", "BZ3_ERR_MALFORMED_HEADER", "BZ3_ERR_TRUNCATED_DATA", "BZ3_ERR_DATA_TOO_BIG",
-                  "BZ3_ERR_INIT", "BZ3_ERR_DATA_SIZE_TOO_SMALL"):
-        val = lambda p: re.search(r"#define\s+%s\s+(-?\d+)" % macro, open(p).read()).group(1)
-        assert val(os.path.join(ROOT, "include", "libbz3.h")) == val(ref_path), macro
+        a = re.sub(r"\b\w+(?=[,)])", "", ours[name])  # parameter names may differ, types and order may not
+        assert hashlib.sha256(a.encode()).hexdigest() == theirs[name], (name, ours[name])
+    assert len(golden["error_codes"]) == 9
+    for macro, want in golden["error_codes"].items():
+        assert int(re.search(r"#define\s+%s\s+(-?\d+)" % macro, open(header).read()).group(1)) == want, macro
 
 
 def test_cu_partition_masks_are_disjoint_and_balanced(lib):

@@ -69,6 +69,37 @@ def test_bench_single_rank_on_the_emulator():
     _check(d, 1)
 
 
+def test_bench_runs_the_requested_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """`--steps K --warmup W` runs W untimed steps and then exactly K timed ones (ms_per_step: their mean); `--dump-outputs DIR` writes
+    what the last timed step computed as .npy files (float32 / float64, 64 MB at most), identical from run to run with the same arguments."""
+    import numpy as np
+
+    args = ["--emu", "--blocks", "3", "--block-mib", "0.003", "--text-bases", "2", "--steps", "3", "--warmup", "1"]
+    names = ["coded_sample.npy", "coded_sizes.npy", "decoded_fingerprint.npy", "decoded_sample.npy", "sample_blocks.npy"]
+    runs = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        d, err = _run([sys.executable, "bench.py", "--gpus", "1"] + args + ["--dump-outputs", str(out)])
+        assert d["steps"] == 3 and d["warmup"] == 1 and len(d["step_s"]) == 3 and d["complete"] is True
+        assert err.count("encode_blocks done") == 4  # one warmup step + three timed steps
+        assert abs(d["ms_per_step"] - sum(d["step_s"]) / 3 * 1e3) <= 10.0  # (step_s is rounded to 10 ms)
+        assert sorted(os.listdir(out)) == names
+        arrays = {n: np.load(out / n) for n in names}
+        assert all(x.dtype in (np.float32, np.float64) for x in arrays.values())
+        assert sum(x.nbytes for x in arrays.values()) <= 64 << 20
+        sizes, sample = arrays["coded_sizes.npy"], arrays["coded_sample.npy"]
+        assert sizes.shape == (3,) and (sizes > 0).all()
+        assert abs(3 * d["config"]["block_bytes"] / sizes.sum() - d["config"]["compressed_ratio"]) <= 1e-3  # the sizes the step's line counted
+        assert sample.shape[0] == arrays["sample_blocks.npy"].shape[0] == arrays["decoded_sample.npy"].shape[0] == 3
+        assert ((sample >= 0) & (sample <= 255) & (sample == np.round(sample))).all()
+        dec = arrays["decoded_sample.npy"]
+        assert ((dec >= 97) & (dec <= 112)).all()  # --emu's input: 16 symbols from 'a'
+        assert arrays["decoded_fingerprint.npy"].shape == (3, 2)
+        runs.append(arrays)
+    for n in names:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
+
+
 def test_bench_cfg5_leg_control_flow_on_the_emulator():
     """`bench.py --leg cfg5` (a batch of maximum-size blocks of the 16-symbol source; run on its own, not by the driver) at a test size."""
     env = dict(os.environ)
