@@ -71,6 +71,10 @@ def _declare(L, strict=True):
         "bz3_hip_decode_block_device": (i32, [vp, vp, sz, i32, i32]),
         "bz3_hip_encode_blocks_device": (None, [vp, vp, vp, i32]),
         "bz3_hip_decode_blocks_device": (None, [vp, vp, vp, vp, vp, i32]),
+        "bz3_hip_compress_device": (C.c_int, [u32, vp, vp, sz, C.POINTER(sz)]),
+        "bz3_hip_decompress_device": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
+        "bz3_hip_frame_decoded_size_device": (C.c_int, [vp, sz, C.POINTER(sz)]),
+        "bz3_hip_debug_copy_segments": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -273,6 +277,70 @@ def encode_block(data, block_size, lib=None):
 def decode_block(data, orig_size, block_size, lib=None, **kw):
     with State(block_size, lib) as st:
         return st.decode_block(data, orig_size, **kw)
+
+
+class Bz3Error(RuntimeError):
+    """A libbz3 call returned an error code: `.code` is the BZ3_ERR_* value; `.out` (decompress_tensor only) the bytes the call
+    committed before the error, as a view of the output tensor."""
+
+    def __init__(self, code, what, out=None):
+        super().__init__(f"{what} failed with {code} ({_ERR_NAMES.get(code, 'unknown error')})")
+        self.code = code
+        self.out = out
+
+
+_ERR_NAMES = {v: k for k, v in globals().items() if k.startswith("BZ3_ERR_")}
+
+
+def _device_u8(x, what):
+    import torch
+
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or x.dtype != torch.uint8 or not x.is_contiguous():
+        raise TypeError(f"{what} must be a contiguous torch.uint8 tensor on a GPU")
+    return x
+
+
+def compress_tensor(x, block_size=16 << 20, lib=None):
+    """The .bz3 frame of the bytes of `x` (a contiguous torch.uint8 GPU tensor; view a tensor of another dtype with
+    .view(torch.uint8).flatten()), computed on x's GPU: a uint8 tensor on the same device holding exactly the frame bytes of
+    bz3_compress.  The result is a view of a bz3_bound(x.numel())-byte allocation (.clone() it to drop the slack).  Synchronises
+    x's device first; raises Bz3Error with the return code on failure."""
+    import torch
+
+    x = _device_u8(x, "x")
+    L = lib or load()
+    n = x.numel()
+    out = torch.empty(L.bz3_bound(n), dtype=torch.uint8, device=x.device)
+    size = C.c_size_t(out.numel())
+    torch.cuda.synchronize(x.device)
+    rc = L.bz3_hip_compress_device(block_size, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, C.byref(size))
+    if rc != BZ3_OK:
+        raise Bz3Error(rc, "bz3_hip_compress_device")
+    return out[: size.value]
+
+
+def decompress_tensor(frame, out=None, lib=None):
+    """The bytes of a .bz3 frame held in a contiguous torch.uint8 GPU tensor, decoded on its GPU.  `out`: a contiguous uint8 tensor
+    on the same device to decode into (its size is the capacity); by default one of the frame's decoded size
+    (bz3_hip_frame_decoded_size_device).  Returns the view of `out` holding the decoded bytes; raises Bz3Error with the return code
+    of bz3_hip_decompress_device, whose `.out` holds the bytes of the chunks decoded before the error."""
+    import torch
+
+    frame = _device_u8(frame, "frame")
+    L = lib or load()
+    torch.cuda.synchronize(frame.device)
+    if out is None:
+        need = C.c_size_t(0)
+        # a frame with a bad header still decodes (and fails) like bz3_decompress: size `out` for the well-formed chunks before it
+        L.bz3_hip_frame_decoded_size_device(C.c_void_p(frame.data_ptr()), frame.numel(), C.byref(need))
+        out = torch.empty(need.value, dtype=torch.uint8, device=frame.device)
+    else:
+        out = _device_u8(out, "out")
+    size = C.c_size_t(out.numel())
+    rc = L.bz3_hip_decompress_device(C.c_void_p(frame.data_ptr()), C.c_void_p(out.data_ptr()), frame.numel(), C.byref(size))
+    if rc != BZ3_OK:
+        raise Bz3Error(rc, "bz3_hip_decompress_device", out[: size.value])
+    return out[: size.value]
 
 
 def shard_blocks(n_blocks, world_size, rank):

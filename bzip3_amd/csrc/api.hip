@@ -19,11 +19,13 @@
 #include <exception>
 #include <mutex>
 #include <new>
+#include <stdexcept>
 #include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/bz3_hip.h"
+#include "frame.hpp"
 #include "prims.hpp"
 #include "sort.hpp"
 #include "stages.hpp"
@@ -1773,6 +1775,38 @@ void fetch_headers(bz3_state ** states, void ** buffers, const size_t * buffer_s
     }
 }
 
+// A new state on device `dev` (bz3_new: the device pick_device chose; the device frame API: the device that owns the caller's buffers).
+bz3_state * new_state_on(int32_t block_size, int dev) {
+    if (block_size < KiB65 || block_size > MiB511) return nullptr;
+    bz3_state * st = nullptr;
+    try {
+        DeviceCtx * ctx = get_ctx(dev);
+        if (!ctx) return nullptr;
+        st = new bz3_state;
+        st->block_size = block_size;
+        st->device = dev;
+        st->ctx = ctx;
+        HIP_CHECK(hipSetDevice(dev));
+        HIP_CHECK(hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
+        st->xs = st->stream;
+        HIP_CHECK(hipEventCreate(&st->ev0));
+        HIP_CHECK(hipEventCreate(&st->ev1));
+        st->cap = (bz3_bound((size_t)block_size) + 4096 + 255) & ~(size_t)255;
+        st->lean = lean_states();
+        if (!st->lean) HIP_CHECK(hipMalloc((void **)&st->d_swap, st->cap));
+        HIP_CHECK(hipMalloc((void **)&st->d_words, 64 * sizeof(u32)));
+        st->last_error = BZ3_OK;
+        return st;
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: bz3_new failed: %s (%s:%d)\n", e.what, e.file, e.line);
+        state_release(st);
+        return nullptr;
+    } catch (const std::bad_alloc &) {
+        state_release(st);
+        return nullptr;
+    }
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1803,38 +1837,12 @@ BZIP3_API const char * bz3_strerror(struct bz3_state * state) {  // messages: sr
 
 BZIP3_API struct bz3_state * bz3_new(int32_t block_size) {
     if (block_size < KiB65 || block_size > MiB511) return nullptr;  // :536
-    bz3_state * st = nullptr;
-    try {
-        const int dev = pick_device();
-        if (dev < 0) {
-            fprintf(stderr, "bzip3_amd: no HIP device available -- this library has no CPU code path\n");
-            return nullptr;
-        }
-        DeviceCtx * ctx = get_ctx(dev);
-        if (!ctx) return nullptr;
-        st = new bz3_state;
-        st->block_size = block_size;
-        st->device = dev;
-        st->ctx = ctx;
-        HIP_CHECK(hipSetDevice(dev));
-        HIP_CHECK(hipStreamCreateWithFlags(&st->stream, hipStreamNonBlocking));
-        st->xs = st->stream;
-        HIP_CHECK(hipEventCreate(&st->ev0));
-        HIP_CHECK(hipEventCreate(&st->ev1));
-        st->cap = (bz3_bound((size_t)block_size) + 4096 + 255) & ~(size_t)255;
-        st->lean = lean_states();
-        if (!st->lean) HIP_CHECK(hipMalloc((void **)&st->d_swap, st->cap));
-        HIP_CHECK(hipMalloc((void **)&st->d_words, 64 * sizeof(u32)));
-        st->last_error = BZ3_OK;
-        return st;
-    } catch (const HipError & e) {
-        fprintf(stderr, "bzip3_amd: bz3_new failed: %s (%s:%d)\n", e.what, e.file, e.line);
-        state_release(st);
-        return nullptr;
-    } catch (const std::bad_alloc &) {
-        state_release(st);
+    const int dev = pick_device();
+    if (dev < 0) {
+        fprintf(stderr, "bzip3_amd: no HIP device available -- this library has no CPU code path\n");
         return nullptr;
     }
+    return new_state_on(block_size, dev);
 }
 
 BZIP3_API void bz3_free(struct bz3_state * state) { state_release(state); }
@@ -2159,13 +2167,9 @@ BZIP3_API int bz3_decompress(const uint8_t * in, uint8_t * out, size_t in_size, 
         int header_error = BZ3_OK;
         size_t planned = *out_size;
         while (cnt < W && i + cnt < n_blocks) {
-            if (in_size < 8) { header_error = BZ3_ERR_MALFORMED_HEADER; break; }                 // :963
-            const s32 size = (s32)rd_le32(in);
-            if (size < 0 || (u32)size > block_size) { header_error = BZ3_ERR_MALFORMED_HEADER; break; }  // :969
-            if (in_size < (size_t)size + 8) { header_error = BZ3_ERR_TRUNCATED_DATA; break; }    // :974
-            const s32 orig_size = (s32)rd_le32(in + 4);
-            if (orig_size < 0) { header_error = BZ3_ERR_MALFORMED_HEADER; break; }               // :980
-            if (buf_max < planned + (size_t)orig_size) { header_error = BZ3_ERR_DATA_TOO_BIG; break; }  // :985
+            s32 size = 0, orig_size = 0;
+            header_error = frame_chunk_check(in, in_size, block_size, buf_max, planned, &size, &orig_size);  // :963-985
+            if (header_error != BZ3_OK) break;
             memcpy(w.bufs[cnt], in + 8, (size_t)size);
             sizes[cnt] = size;
             orig[cnt] = orig_size;
@@ -2198,6 +2202,377 @@ BZIP3_API int bz3_orig_size_sufficient_for_decode(const uint8_t * block, size_t 
     if (model & 2) { lzp_size = (s32)rd_le32(block + off); off += 4; }
     if (model & 4) rle_size = (s32)rd_le32(block + off);
     return sizes_fit((size_t)orig_size, lzp_size, rle_size, orig_size) ? 1 : 0;
+}
+
+// ---- device-resident frames (bz3_hip.h: bz3_hip_compress_device / bz3_hip_decompress_device) ------------------------------
+// The frame API above with `in` and `out` in HBM of one GPU.  A window of up to 256 blocks at a time: one state per block on
+// the buffers' device and one slab of slots; every move between the caller's buffers and the slots is ONE launch of
+// k_copy_segments (frame.hpp), chunk headers travel as extra segments from a small staged buffer, and on decode the chunk
+// headers are walked on the device (k_frame_walk) and read back once per window.
+namespace {
+
+// The device that owns `p` if it is device memory, else -1.  (The emulator's device memory is host memory, on device 0.)
+int device_of(const void * p) {
+    if (!p) return -1;
+#ifdef BZ3_EMU
+    return 0;
+#else
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return a.type == hipMemoryTypeDevice ? a.device : -1;
+#endif
+}
+
+// Device tables of one k_copy_segments launch: the segments, then the nseg + 1 tile starts.
+constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg) + 15) & ~(size_t)15) + (nseg + 1) * sizeof(u32); }
+
+// Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
+// The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
+void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
+    const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
+    staging.assign(copy_table_bytes(n), 0);
+    memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
+    u32 * starts = (u32 *)(staging.data() + seg_bytes);
+    u64 tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        starts[i] = (u32)tiles;
+        tiles += copy_tiles(segs[i].dst, segs[i].len);
+    }
+    if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
+    starts[n] = (u32)tiles;
+    if (!tiles) return;
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
+    launch(k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+}
+
+constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
+// Layout of a window's small device buffer: staged chunk headers, the copy tables, the walk's records and its tail.
+constexpr size_t META_HDR = 0;
+constexpr size_t META_TAB = 4096;
+constexpr size_t META_REC = META_TAB + ((copy_table_bytes(2 * FRAME_WINDOW_MAX + 1) + 4095) & ~(size_t)4095);
+constexpr size_t META_TAIL = META_REC + FRAME_WINDOW_MAX * sizeof(WalkChunk);
+constexpr size_t META_BYTES = META_TAIL + sizeof(WalkTail);
+static_assert(13 + 8 * FRAME_WINDOW_MAX <= META_TAB, "staged headers overlap the copy tables");
+
+struct DeviceFrame {
+    int device = -1;
+    hipStream_t s = nullptr;  // the lead state's stream (its own for the walk before the states exist)
+    bool own_stream = false;
+    u8 * meta = nullptr;
+    u8 * slab = nullptr;
+    size_t stride = 0;
+    std::vector<bz3_state *> states;
+    std::vector<CopySeg> segs;
+    std::vector<u8> staging;
+    ~DeviceFrame() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (s) (void)hipStreamSynchronize(s);
+        for (bz3_state * st : states) state_release(st);
+        if (slab) (void)hipFree(slab);
+        if (meta) (void)hipFree(meta);
+        if (own_stream && s) (void)hipStreamDestroy(s);
+    }
+    bool open(int dev) {  // the device, a stream and the small buffer
+        if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
+        device = dev;
+        HIP_CHECK(hipSetDevice(dev));
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        own_stream = true;
+        HIP_CHECK(hipMalloc((void **)&meta, META_BYTES));
+        return true;
+    }
+    // Up to `want` states of block_size on the device and a slab of as many slots, within the memory the headroom rule leaves; at least one or false.
+    bool init(u32 block_size, size_t want) {
+        size_t limit = FRAME_WINDOW_MAX;
+        if (const char * e = getenv("BZ3_HIP_FRAME_WINDOW"))  // tests: windows smaller than the frame
+            if (atoi(e) > 0 && (size_t)atoi(e) < limit) limit = (size_t)atoi(e);
+        const size_t cap = (bz3_bound(block_size) + 4096 + 255) & ~(size_t)255;  // a state's cap (new_state_on)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // per block: a slot and a swap buffer (owned or borrowed); beside them the headroom, the stages' workspace and two LZP contexts
+            const size_t fixed = ws_headroom() + workspace_bytes_for((u64)block_size + 64) + 2 * lzp_encode_ctx_bytes((u64)block_size + 128) + ((size_t)64 << 20);
+            const size_t by_mem = free_b > fixed ? (free_b - fixed) / (2 * cap) : 0;
+            if (by_mem < limit) limit = by_mem;
+        }
+        if (want > limit) want = limit;
+        if (want < 1) want = 1;
+        for (size_t i = 0; i < want; i++) {
+            bz3_state * st = new_state_on((int32_t)block_size, device);
+            if (!st) break;
+            states.push_back(st);
+        }
+        while (!states.empty()) {
+            if (hipMalloc((void **)&slab, states.size() * cap) == hipSuccess) break;
+            (void)hipGetLastError();
+            slab = nullptr;
+            const size_t keep = states.size() / 2;
+            while (states.size() > keep) {
+                state_release(states.back());
+                states.pop_back();
+            }
+        }
+        if (states.empty()) return false;
+        stride = cap;
+        HIP_CHECK(hipSetDevice(device));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipStreamDestroy(s));
+        own_stream = false;
+        s = states[0]->stream;
+        return true;
+    }
+    u8 * slot(size_t k) const { return slab + k * stride; }
+    void copy() {  // the segments collected in `segs`, one launch, complete on return
+        copy_segments(segs, staging, meta + META_TAB, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        segs.clear();
+    }
+    void stage_headers(const std::vector<u8> & h) {
+        if (!h.empty()) HIP_CHECK(hipMemcpyAsync(meta + META_HDR, h.data(), h.size(), hipMemcpyHostToDevice, s));
+    }
+    // Up to `limit` chunk headers from (off, done, planned); the records land in rec, the resume state and the first header error in tail.
+    void walk(const u8 * in, size_t in_size, u32 block_size, u32 n_blocks, size_t buf_max, u64 off, u32 done, u64 planned, u32 limit,
+              std::vector<WalkChunk> & rec, WalkTail & tail) {
+        launch(k_frame_walk, dim3(1), dim3(64), 0, s, in, (u64)in_size, block_size, n_blocks, (u64)buf_max, off, done, planned, limit,
+               (WalkChunk *)(meta + META_REC), (WalkTail *)(meta + META_TAIL));
+        staging.resize(META_BYTES - META_REC);
+        HIP_CHECK(hipMemcpyAsync(staging.data(), meta + META_REC, staging.size(), hipMemcpyDeviceToHost, s));  // records and tail: one read-back
+        HIP_CHECK(hipStreamSynchronize(s));
+        memcpy(&tail, staging.data() + (META_TAIL - META_REC), sizeof tail);
+        rec.resize(tail.count);
+        memcpy(rec.data(), staging.data(), tail.count * sizeof(WalkChunk));
+    }
+};
+
+// The frame header of a frame in device memory: BZ3_OK and its two fields, or MALFORMED_HEADER (:930-936).
+int read_frame_header(DeviceFrame & f, const u8 * in, size_t in_size, u32 & block_size, u32 & n_blocks) {
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    u8 h[13];
+    HIP_CHECK(hipMemcpyAsync(h, in, 13, hipMemcpyDeviceToHost, f.s));
+    HIP_CHECK(hipStreamSynchronize(f.s));
+    if (memcmp(h, "BZ3v1", 5) != 0) return BZ3_ERR_MALFORMED_HEADER;
+    block_size = rd_le32(h + 5);
+    n_blocks = rd_le32(h + 9);
+    return BZ3_OK;
+}
+
+int compress_device(u32 block_size, const u8 * in, u8 * out, size_t in_size, size_t * out_size) {
+    if (block_size > in_size) block_size = (u32)bz3_bound(in_size);  // :877
+    block_size = block_size <= (u32)KiB65 ? (u32)KiB65 : block_size;
+    u32 n_blocks = (u32)(in_size / block_size);
+    if (in_size % block_size) n_blocks++;
+    const int dev = device_of(out);
+    if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
+    DeviceFrame f;
+    try {
+        if (block_size > (u32)MiB511 || !f.open(dev) || !f.init(block_size, n_blocks)) return BZ3_ERR_INIT;  // :879-886
+    } catch (...) {
+        return BZ3_ERR_INIT;
+    }
+    const size_t buf_max = *out_size;
+    *out_size = 0;
+    if (buf_max < 13 || buf_max < bz3_bound(in_size)) return BZ3_ERR_DATA_TOO_BIG;
+    try {
+        DeviceGuard g(dev);
+        const u32 W = (u32)f.states.size();
+        std::vector<s32> sizes(W);
+        std::vector<void *> slots(W);
+        std::vector<u8> hdr;
+        size_t pos = 0;
+        for (u32 i0 = 0; i0 == 0 || i0 < n_blocks; i0 += W) {
+            const u32 cnt = i0 < n_blocks ? (n_blocks - i0 < W ? n_blocks - i0 : W) : 0;
+            for (u32 k = 0; k < cnt; k++) {  // scatter: block i0 + k to slot k
+                s32 size = (s32)block_size;
+                if (i0 + k == n_blocks - 1) size = (s32)(in_size % block_size);  // (sic) :914 -- 0 when in_size is a multiple
+                sizes[k] = size;
+                slots[k] = f.slot(k);
+                f.segs.push_back({(u64)(in + (size_t)(i0 + k) * block_size), (u64)f.slot(k), (u64)size});
+            }
+            std::vector<s32> orig(sizes.begin(), sizes.begin() + cnt);
+            if (cnt) {
+                f.copy();
+                run_encode(f.states.data(), slots.data(), sizes.data(), (s32)cnt, false);
+            }
+            // pack: the chunk headers (and the frame header with the first window) from the staged buffer, the coded slots behind them
+            hdr.clear();
+            if (i0 == 0) {
+                hdr.insert(hdr.end(), {'B', 'Z', '3', 'v', '1'});
+                hdr.resize(13);
+                wr_le32(hdr.data() + 5, block_size);
+                wr_le32(hdr.data() + 9, n_blocks);
+                f.segs.push_back({(u64)(f.meta + META_HDR), (u64)out, 13});
+                pos = 13;
+            }
+            int err = BZ3_OK;
+            for (u32 k = 0; k < cnt; k++) {
+                if (bz3_last_error(f.states[k]) != BZ3_OK) {  // :917-922
+                    err = f.states[k]->last_error;
+                    break;
+                }
+                const s32 osz = sizes[k];
+                if (osz < 0 || pos + 8 + (size_t)osz > buf_max) {  // (bz3_bound(in_size) covers the frame: never taken)
+                    err = BZ3_ERR_DATA_TOO_BIG;
+                    break;
+                }
+                const size_t h = hdr.size();
+                hdr.resize(h + 8);
+                wr_le32(hdr.data() + h, (u32)osz);
+                wr_le32(hdr.data() + h + 4, (u32)orig[k]);
+                f.segs.push_back({(u64)(f.meta + META_HDR + h), (u64)(out + pos), 8});
+                f.segs.push_back({(u64)f.slot(k), (u64)(out + pos + 8), (u64)osz});
+                pos += (size_t)osz + 8;
+            }
+            f.stage_headers(hdr);
+            f.copy();
+            *out_size = pos;
+            if (err != BZ3_OK) return err;
+        }
+        return BZ3_OK;
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        return BZ3_ERR_BWT;
+    } catch (...) {
+        return BZ3_ERR_BWT;
+    }
+}
+
+int decompress_device(const u8 * in, u8 * out, size_t in_size, size_t * out_size) {
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
+    DeviceFrame f;
+    const size_t buf_max = *out_size;
+    std::vector<WalkChunk> rec;
+    WalkTail tail{};
+    u32 block_size = 0, n_blocks = 0;
+    try {
+        if (!f.open(dev)) return BZ3_ERR_INIT;
+        DeviceGuard g(dev);
+        const int herr = read_frame_header(f, in, in_size, block_size, n_blocks);
+        if (herr != BZ3_OK) return herr;
+        if (block_size < (u32)KiB65 || block_size > (u32)MiB511) return BZ3_ERR_INIT;  // bz3_new, :953-960
+        // n_blocks is untrusted: the window is sized from the chunks the first walk finds present, never from n_blocks
+        f.walk(in, in_size, block_size, n_blocks, buf_max, 13, 0, 0, (u32)(n_blocks < FRAME_WINDOW_MAX ? n_blocks : FRAME_WINDOW_MAX), rec, tail);
+        if (!f.init(block_size, tail.count ? tail.count : 1)) return BZ3_ERR_INIT;
+    } catch (...) {
+        return BZ3_ERR_INIT;
+    }
+    *out_size = 0;
+    try {
+        DeviceGuard g(dev);
+        const u32 W = (u32)f.states.size();
+        std::vector<s32> sizes(W), orig(W);
+        std::vector<size_t> caps(W, bz3_bound(block_size));
+        std::vector<void *> slots(W);
+        std::vector<u8> hdrs(17 * (size_t)W);
+        u64 off = 13, planned = 0;
+        u32 done = 0;
+        for (bool first = true; done < n_blocks; first = false) {
+            if (!first) f.walk(in, in_size, block_size, n_blocks, buf_max, off, done, planned, n_blocks - done < W ? n_blocks - done : W, rec, tail);
+            const u32 t = tail.count < W ? tail.count : W;
+            const int header_error = t == tail.count ? tail.err : BZ3_OK;  // (a header error beyond this window is found again by the next walk)
+            for (u32 k = 0; k < t; k++) {  // unpack: chunk k to slot k
+                sizes[k] = rec[k].size;
+                orig[k] = rec[k].orig;
+                slots[k] = f.slot(k);
+                memcpy(hdrs.data() + 17 * (size_t)k, rec[k].hdr, 17);
+                f.segs.push_back({(u64)(in + rec[k].in_off + 8), (u64)f.slot(k), (u64)rec[k].size});
+            }
+            u32 ok = 0;
+            if (t) {
+                f.copy();
+                run_decode(f.states.data(), slots.data(), caps.data(), sizes.data(), orig.data(), hdrs.data(), (s32)t, false);
+                while (ok < t && bz3_last_error(f.states[ok]) == BZ3_OK) ok++;
+                for (u32 k = 0; k < ok; k++) f.segs.push_back({(u64)f.slot(k), (u64)(out + rec[k].out_off), (u64)rec[k].orig});  // gather
+                f.copy();
+                if (ok) *out_size = rec[ok - 1].out_off + (size_t)rec[ok - 1].orig;
+                if (ok < t) return f.states[ok]->last_error;  // :989-993
+            }
+            if (header_error != BZ3_OK) return header_error;
+            done += t;
+            if (t < tail.count) {
+                off = rec[t].in_off;
+                planned = rec[t].out_off;
+            } else {
+                off = tail.off;
+                planned = tail.planned;
+            }
+        }
+        return BZ3_OK;
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        return BZ3_ERR_BWT;
+    } catch (...) {
+        return BZ3_ERR_BWT;
+    }
+}
+
+int frame_decoded_size_device(const u8 * in, size_t in_size, size_t * decoded_size) {
+    *decoded_size = 0;
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0) return BZ3_ERR_INIT;
+    try {
+        DeviceFrame f;
+        if (!f.open(dev)) return BZ3_ERR_INIT;
+        DeviceGuard g(dev);
+        u32 block_size = 0, n_blocks = 0;
+        const int herr = read_frame_header(f, in, in_size, block_size, n_blocks);
+        if (herr != BZ3_OK) return herr;
+        if (block_size < (u32)KiB65 || block_size > (u32)MiB511) return BZ3_ERR_INIT;  // what bz3_decompress reports for it
+        std::vector<WalkChunk> rec;
+        WalkTail tail{13, 0, 0, 0, BZ3_OK, 0};
+        while (tail.done < n_blocks && tail.err == BZ3_OK) {
+            const u32 left = n_blocks - tail.done;
+            f.walk(in, in_size, block_size, n_blocks, SIZE_MAX, tail.off, tail.done, tail.planned, left < FRAME_WINDOW_MAX ? left : (u32)FRAME_WINDOW_MAX, rec, tail);
+            *decoded_size = tail.planned;
+        }
+        return tail.err;
+    } catch (...) {
+        return BZ3_ERR_INIT;
+    }
+}
+
+}  // namespace
+
+BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return compress_device(block_size, (const u8 *)in, (u8 *)out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
+    return decompress_device((const u8 *)in, (u8 *)out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size) {
+    return frame_decoded_size_device((const u8 *)in, in_size, decoded_size);
+}
+
+BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev) return BZ3_ERR_INIT;
+    u8 * d_tab = nullptr;
+    hipStream_t s = nullptr;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        std::vector<CopySeg> v((size_t)n);
+        for (s32 i = 0; i < n; i++) v[(size_t)i] = {(u64)src + segs[3 * i], (u64)dst + segs[3 * i + 1], segs[3 * i + 2]};
+        std::vector<u8> staging;
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_CHECK(hipMalloc((void **)&d_tab, copy_table_bytes((size_t)n)));
+        copy_segments(v, staging, d_tab, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    if (s) (void)hipStreamSynchronize(s);
+    if (d_tab) (void)hipFree(d_tab);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
 }
 
 // ---- bz3_hip.h: device control, timings ----------------------------------------------------------------

@@ -1,0 +1,173 @@
+// frame.hpp -- kernels of the device-resident frame API (bz3_hip_compress_device / bz3_hip_decompress_device, api.hip).
+//
+// A frame (src/libbz3.c:876-997) is a 13-byte header, then per block an 8-byte chunk header (coded size, original size)
+// and the coded bytes.  Moving a window of blocks between the caller's buffers and the states' slots is a list of
+// byte segments at arbitrary alignments on both sides: k_copy_segments moves them all in one launch.  Decoding
+// needs the chunk headers, which form a chain (each one's offset depends on the sizes before it): k_frame_walk
+// follows that chain on one lane and hands the host every chunk's offsets and first 17 bytes in one read-back.
+#pragma once
+#include "../../include/libbz3.h"
+#include "hipx.hpp"
+
+namespace bz3 {
+
+// The four checks of one chunk header in bz3_decompress (src/libbz3.c:963-985), in the reference's order.  `p` points at
+// the chunk header, `in_left` bytes of the frame remain from there, `planned` bytes of output precede the chunk.
+// Shared by the host loop (bz3_decompress) and the device walk (k_frame_walk), so the rules exist once.
+__host__ __device__ inline int frame_chunk_check(const u8 * p, size_t in_left, u32 block_size, size_t buf_max, size_t planned,
+                                                 s32 * size, s32 * orig_size) {
+    if (in_left < 8) return BZ3_ERR_MALFORMED_HEADER;  // :963
+    const s32 sz = (s32)((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24));
+    if (sz < 0 || (u32)sz > block_size) return BZ3_ERR_MALFORMED_HEADER;  // :969
+    if (in_left < (size_t)sz + 8) return BZ3_ERR_TRUNCATED_DATA;         // :974
+    const s32 orig = (s32)((u32)p[4] | ((u32)p[5] << 8) | ((u32)p[6] << 16) | ((u32)p[7] << 24));
+    if (orig < 0) return BZ3_ERR_MALFORMED_HEADER;                        // :980
+    if (buf_max < planned + (size_t)orig) return BZ3_ERR_DATA_TOO_BIG;   // :985
+    *size = sz;
+    *orig_size = orig;
+    return BZ3_OK;
+}
+
+// ---- k_copy_segments -------------------------------------------------------------------------------------------------
+// One segment: `len` bytes from absolute device address `src` to `dst`.  Segments of one launch do not overlap on the
+// destination side (they may share a 16-byte granule: the bytes of a shared granule are written with byte stores).
+struct CopySeg {
+    u64 src, dst, len;
+};
+constexpr u32 COPY_THREADS = 256;
+constexpr u32 COPY_GRANULES_PER_LANE = 4;
+constexpr u32 COPY_TILE_GRANULES = COPY_THREADS * COPY_GRANULES_PER_LANE;  // 16 KiB of destination per workgroup
+
+// Destination granules (16-byte aligned) a segment touches, and the workgroups (tiles) it takes.
+__host__ __device__ inline u64 copy_granules(u64 dst, u64 len) { return len ? ((dst + len + 15) >> 4) - (dst >> 4) : 0; }
+__host__ __device__ inline u64 copy_tiles(u64 dst, u64 len) { return (copy_granules(dst, len) + COPY_TILE_GRANULES - 1) / COPY_TILE_GRANULES; }
+
+__device__ __forceinline__ u32 align_byte(u32 hi, u32 lo, u32 r) {  // ((hi:lo) >> 8 r)[31:0], v_alignbyte_b32
+#ifdef BZ3_EMU
+    return (u32)((((u64)hi << 32) | lo) >> (8 * (r & 3)));
+#else
+    return __builtin_amdgcn_alignbyte(hi, lo, r);
+#endif
+}
+
+// One tile of one segment.  Q = (src - dst) / 4 mod 4: which word of the lower aligned source granule holds the first source
+// byte of every destination granule (uniform over a segment, hence a template parameter: the word selection is static).
+// A full destination granule whose source bytes straddle two aligned source granules is built from both of them with
+// v_alignbyte_b32 and written with one 16-byte store; both granules hold bytes of the segment.  The partial head and tail
+// granules are copied byte by byte.  No granule is ever loaded that holds no byte of the segment.
+template <int Q>
+__device__ __forceinline__ uint4 shift_granules(uint4 lo, uint4 hi, u32 r) {  // bytes [4 Q + r, 4 Q + r + 16) of lo:hi
+    const u32 w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint4 o;
+    o.x = align_byte(w[Q + 1], w[Q + 0], r);
+    o.y = align_byte(w[Q + 2], w[Q + 1], r);
+    o.z = align_byte(w[Q + 3], w[Q + 2], r);
+    o.w = align_byte(w[Q + 4], w[Q + 3], r);
+    return o;
+}
+
+template <int Q>
+__device__ __forceinline__ void copy_tile(const u8 * src, u8 * dst, u64 len, u64 g_first, u64 g_end) {
+    const u64 d0 = (u64)dst, d1 = d0 + len;
+    const u64 delta = (u64)src - d0;  // source address = destination address + delta (mod 2^64)
+    const u32 r = (u32)(delta & 3);
+    const bool aligned = (delta & 15) == 0;
+    if (g_end - g_first == COPY_TILE_GRANULES && (g_first << 4) >= d0 && (g_end << 4) <= d1) {  // every granule of the tile is full: loads first, then stores
+        uint4 lo[COPY_GRANULES_PER_LANE], hi[COPY_GRANULES_PER_LANE];
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+            const uint4 * sp = (const uint4 *)((((g_first + k * COPY_THREADS + threadIdx.x) << 4) + delta) & ~(u64)15);
+            lo[k] = sp[0];
+            if (!aligned) hi[k] = sp[1];
+        }
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++)
+            *(uint4 *)((g_first + k * COPY_THREADS + threadIdx.x) << 4) = aligned ? lo[k] : shift_granules<Q>(lo[k], hi[k], r);
+        return;
+    }
+    for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+        const u64 g = g_first + k * COPY_THREADS + threadIdx.x;
+        if (g >= g_end) break;
+        const u64 a = g << 4;  // destination granule [a, a + 16)
+        if (a >= d0 && a + 16 <= d1) {
+            const uint4 * sp = (const uint4 *)((a + delta) & ~(u64)15);
+            *(uint4 *)a = aligned ? sp[0] : shift_granules<Q>(sp[0], sp[1], r);
+        } else {
+            const u64 b0 = a > d0 ? a : d0, b1 = a + 16 < d1 ? a + 16 : d1;
+            for (u64 b = b0; b < b1; b++) *(u8 *)b = *(const u8 *)(b + delta);
+        }
+    }
+}
+
+// Workgroup b copies tile b - tile_start[i] of segment i, where tile_start[i] <= b < tile_start[i + 1] (binary search over the
+// nseg + 1 prefix sums the host computed).
+__global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    const u64 g0 = sg.dst >> 4, g_end = (sg.dst + sg.len + 15) >> 4;
+    const u64 g_first = g0 + (u64)(b - tile_start[lo]) * COPY_TILE_GRANULES;
+    const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+    const u8 * src = (const u8 *)sg.src;
+    u8 * dst = (u8 *)sg.dst;
+    switch ((u32)(((sg.src - sg.dst) >> 2) & 3)) {
+        case 0: copy_tile<0>(src, dst, sg.len, g_first, g_last); break;
+        case 1: copy_tile<1>(src, dst, sg.len, g_first, g_last); break;
+        case 2: copy_tile<2>(src, dst, sg.len, g_first, g_last); break;
+        default: copy_tile<3>(src, dst, sg.len, g_first, g_last); break;
+    }
+}
+
+// ---- k_frame_walk ----------------------------------------------------------------------------------------------------
+// Up to `limit` chunk headers of a frame (`frame`, `in_size` bytes including the 13-byte header), from the state
+// (off = offset of the next chunk header, done = chunks behind, planned = output bytes before it).  One lane: every
+// header's offset depends on the one before it.
+struct WalkChunk {
+    u64 in_off;   // offset of the chunk header in the frame
+    u64 out_off;  // output bytes of the chunks before it (planned)
+    s32 size, orig;
+    u8 hdr[17];   // the first 17 bytes of the chunk's coded bytes (zeros beyond the end of the frame)
+    u8 pad[7];
+};
+struct WalkTail {
+    u64 off, planned;  // resume state after the last well-formed chunk read
+    u32 done;
+    u32 count;  // chunks written to the records
+    s32 err;    // BZ3_OK, or the first header error (the walk stopped at it)
+    u32 pad;
+};
+
+__global__ void __launch_bounds__(64) k_frame_walk(const u8 * __restrict__ frame, u64 in_size, u32 block_size, u32 n_blocks, u64 buf_max,
+                                                   u64 off, u32 done, u64 planned, u32 limit, WalkChunk * __restrict__ rec, WalkTail * __restrict__ tail) {
+    if (threadIdx.x != 0) return;
+    u32 c = 0;
+    int err = BZ3_OK;
+    while (c < limit && done < n_blocks) {
+        s32 size = 0, orig = 0;
+        err = frame_chunk_check(frame + off, in_size - off, block_size, (size_t)buf_max, (size_t)planned, &size, &orig);
+        if (err != BZ3_OK) break;
+        WalkChunk & w = rec[c];
+        w.in_off = off;
+        w.out_off = planned;
+        w.size = size;
+        w.orig = orig;
+        const u64 data = off + 8;
+        for (u32 i = 0; i < 17; i++) w.hdr[i] = data + i < in_size ? frame[data + i] : (u8)0;
+        off = data + (u64)size;
+        planned += (u64)orig;
+        done++;
+        c++;
+    }
+    tail->off = off;
+    tail->planned = planned;
+    tail->done = done;
+    tail->count = c;
+    tail->err = err;
+}
+
+}  // namespace bz3

@@ -10,7 +10,8 @@
  *  - per-stage entry points on host buffers, used by the parity tests to diff each HIP stage
  *    against its reference stage (crc32sum, mrlec, mrled, lzp_compress, lzp_decompress,
  *    libsais_bwt, libsais_unbwt, encode_bytes, decode_bytes);
- *  - per-stage timings of the last block a state processed.
+ *  - per-stage timings of the last block a state processed;
+ *  - the frame API (bz3_compress / bz3_decompress) on device memory.
  */
 #ifndef BZ3_HIP_H
 #define BZ3_HIP_H
@@ -108,6 +109,24 @@ BZIP3_API int32_t bz3_hip_decode_block_device(struct bz3_state * state, void * b
 BZIP3_API void bz3_hip_encode_blocks_device(struct bz3_state * states[], void * buffers[], int32_t sizes[], int32_t n);
 BZIP3_API void bz3_hip_decode_blocks_device(struct bz3_state * states[], void * buffers[], size_t buffer_sizes[], int32_t sizes[],
                                             int32_t orig_sizes[], int32_t n);
+
+/* Frames in device memory: bz3_compress / bz3_decompress (src/libbz3.c:876-997) with `in` and `out` in device memory of ONE GPU.
+ * Same frame bytes, same return codes, same *out_size semantics (capacity on entry, bytes written on return; on a decode error: the bytes
+ * of the chunks decoded before it).  Synchronous: the caller's writes to `in` must be complete before the call (synchronise your stream),
+ * `out` is complete when it returns.  `in` is never written.  The GPU is the one that owns `in` (compress: `out`); both buffers must be
+ * device memory of that GPU, else BZ3_ERR_INIT (an empty `in`, or an `out` of capacity 0 on decode, is not looked at).  The states of
+ * the call live on that GPU whatever bz3_hip_bind_device says.  Blocks go through in windows of up to 256 per call (fewer where the
+ * device's free memory beyond the headroom rule does not hold 256 slots and swap buffers); the headroom rule holds when the call returns. */
+BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size);
+/* Walks the chunk headers of a frame in device memory with bz3_decompress's header checks (no decoding): *decoded_size = sum of the
+ * original sizes of the well-formed chunks; returns BZ3_OK when all n_blocks chunks are present and well-formed, else the error
+ * bz3_decompress would report first for the frame's headers (MALFORMED_HEADER / TRUNCATED_DATA; BZ3_ERR_INIT for a block size bz3_new
+ * refuses or a pointer that is not device memory). */
+BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size);
+/* Test hook: one launch of the segment copy kernel (frame.hpp k_copy_segments) on the device that owns `dst`: n (src_off, dst_off, len)
+ * triples (host array of 3 n u64) relative to `src` / `dst`, non-overlapping on the destination side.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n);
 
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
