@@ -74,6 +74,9 @@ def _declare(L, strict=True):
         "bz3_hip_compress_device": (C.c_int, [u32, vp, vp, sz, C.POINTER(sz)]),
         "bz3_hip_decompress_device": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "bz3_hip_frame_decoded_size_device": (C.c_int, [vp, sz, C.POINTER(sz)]),
+        "bz3_hip_compress_device_many": (C.c_int, [u32, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_decompress_device_many": (C.c_int, [i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_frame_decoded_sizes_device": (C.c_int, [i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_copy_segments": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
@@ -281,12 +284,17 @@ def decode_block(data, orig_size, block_size, lib=None, **kw):
 
 class Bz3Error(RuntimeError):
     """A libbz3 call returned an error code: `.code` is the BZ3_ERR_* value; `.out` (decompress_tensor only) the bytes the call
-    committed before the error, as a view of the output tensor."""
+    committed before the error, as a view of the output tensor.  The batched calls (compress_tensors / decompress_tensors) also set
+    `.index` (the lowest failing frame, whose code `.code` is), `.codes` (every frame's code) and `.outs` (per frame, a view of the
+    bytes the call committed for it)."""
 
-    def __init__(self, code, what, out=None):
-        super().__init__(f"{what} failed with {code} ({_ERR_NAMES.get(code, 'unknown error')})")
+    def __init__(self, code, what, out=None, index=None, codes=None, outs=None):
+        super().__init__(f"{what} failed with {code} ({_ERR_NAMES.get(code, 'unknown error')})" + ("" if index is None else f" at frame {index}"))
         self.code = code
         self.out = out
+        self.index = index
+        self.codes = codes
+        self.outs = outs
 
 
 _ERR_NAMES = {v: k for k, v in globals().items() if k.startswith("BZ3_ERR_")}
@@ -341,6 +349,97 @@ def decompress_tensor(frame, out=None, lib=None):
     if rc != BZ3_OK:
         raise Bz3Error(rc, "bz3_hip_decompress_device", out[: size.value])
     return out[: size.value]
+
+
+def _same_device(ts, what):
+    dev = ts[0].device
+    for t in ts:
+        if t.device != dev:
+            raise ValueError(f"{what}: all tensors must be on one GPU ({dev} and {t.device})")
+    return dev
+
+
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _carve(total, sizes, device):
+    """Views of one uint8 allocation on `device`, of the given sizes, each starting at a multiple of 16 bytes."""
+    import torch
+
+    offs, o = [], 0
+    for n in sizes:
+        offs.append(o)
+        o += (n + 15) & ~15
+    buf = torch.empty(max(o, 1), dtype=torch.uint8, device=device)
+    return [buf[a : a + n] for a, n in zip(offs, sizes)]
+
+
+def compress_tensors(xs, block_size=16 << 20, lib=None):
+    """compress_tensor for many tensors in ONE call (bz3_hip_compress_device_many): frame i is exactly compress_tensor(xs[i],
+    block_size).  Blocks of all tensors share windows of up to 256 blocks, so many small tensors (a state_dict) code in a few CM
+    launches instead of one per tensor.  All tensors must be contiguous torch.uint8 tensors on one GPU; one device synchronisation
+    per call.  The frames are views of one allocation of bz3_bound bytes per tensor (.clone() one to drop the rest).  Raises
+    Bz3Error (with .index / .codes / .outs) if any frame fails.  [] returns []."""
+    import torch
+
+    xs = [_device_u8(x, f"xs[{i}]") for i, x in enumerate(xs)]
+    if not xs:
+        return []
+    dev = _same_device(xs, "compress_tensors")
+    L = lib or load()
+    n = len(xs)
+    caps = [L.bz3_bound(x.numel()) for x in xs]
+    outs = _carve(sum(caps), caps, dev)
+    in_sizes = (C.c_size_t * n)(*[x.numel() for x in xs])
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    torch.cuda.synchronize(dev)
+    rc = L.bz3_hip_compress_device_many(block_size, n, _ptrs(xs), in_sizes, _ptrs(outs), out_sizes, rcs)
+    frames = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, "bz3_hip_compress_device_many", index=idx, codes=codes, outs=frames)
+    return frames
+
+
+def decompress_tensors(frames, outs=None, lib=None):
+    """decompress_tensor for many frames in ONE call (bz3_hip_decompress_device_many): result i is exactly
+    decompress_tensor(frames[i], outs[i]).  `outs`: contiguous uint8 tensors on the frames' GPU, one per frame (their sizes are the
+    capacities); by default views of one allocation sized with bz3_hip_frame_decoded_sizes_device.  One device synchronisation per
+    call.  Raises Bz3Error (with .index / .codes / .outs, the bytes committed per frame) if any frame fails.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    if not frames:
+        return []
+    dev = _same_device(frames, "decompress_tensors")
+    L = lib or load()
+    n = len(frames)
+    in_ptrs = _ptrs(frames)
+    in_sizes = (C.c_size_t * n)(*[f.numel() for f in frames])
+    torch.cuda.synchronize(dev)
+    if outs is None:
+        need = (C.c_size_t * n)()
+        rcs = (C.c_int * n)()
+        # a frame with a bad header still decodes (and fails) like bz3_decompress: size its output for the well-formed chunks before it
+        L.bz3_hip_frame_decoded_sizes_device(n, in_ptrs, in_sizes, need, rcs)
+        outs = _carve(sum(need), list(need), dev)
+    else:
+        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
+        if len(outs) != n:
+            raise ValueError(f"decompress_tensors: {n} frames and {len(outs)} outputs")
+        _same_device(frames + outs, "decompress_tensors")
+    out_sizes = (C.c_size_t * n)(*[o.numel() for o in outs])
+    rcs = (C.c_int * n)()
+    rc = L.bz3_hip_decompress_device_many(n, in_ptrs, in_sizes, _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, "bz3_hip_decompress_device_many", index=idx, codes=codes, outs=res)
+    return res
 
 
 def shard_blocks(n_blocks, world_size, rank):

@@ -2204,11 +2204,13 @@ BZIP3_API int bz3_orig_size_sufficient_for_decode(const uint8_t * block, size_t 
     return sizes_fit((size_t)orig_size, lzp_size, rle_size, orig_size) ? 1 : 0;
 }
 
-// ---- device-resident frames (bz3_hip.h: bz3_hip_compress_device / bz3_hip_decompress_device) ------------------------------
-// The frame API above with `in` and `out` in HBM of one GPU.  A window of up to 256 blocks at a time: one state per block on
-// the buffers' device and one slab of slots; every move between the caller's buffers and the slots is ONE launch of
-// k_copy_segments (frame.hpp), chunk headers travel as extra segments from a small staged buffer, and on decode the chunk
-// headers are walked on the device (k_frame_walk) and read back once per window.
+// ---- device-resident frames (bz3_hip.h: bz3_hip_compress_device[_many] / bz3_hip_decompress_device[_many]) -------------------
+// The frame API above with `in` and `out` in HBM of one GPU, for one frame or many in one call (the single-frame entry
+// points are the n = 1 case).  A window of up to 256 blocks at a time, taken in frame order across frame boundaries: one
+// state per block on the buffers' device and one slab of slots; every move between the caller's buffers and the slots is
+// ONE launch of k_copy_segments (frame.hpp), frame and chunk headers travel as extra segments from a small staged buffer,
+// and on decode the chunk headers of all frames are walked on the device (k_frame_walk_many, one lane per frame) and read
+// back once per window.
 namespace {
 
 // The device that owns `p` if it is device memory, else -1.  (The emulator's device memory is host memory, on device 0.)
@@ -2249,25 +2251,47 @@ void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging,
 }
 
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
-// Layout of a window's small device buffer: staged chunk headers, the copy tables, the walk's records and its tail.
-constexpr size_t META_HDR = 0;
-constexpr size_t META_TAB = 4096;
-constexpr size_t META_REC = META_TAB + ((copy_table_bytes(2 * FRAME_WINDOW_MAX + 1) + 4095) & ~(size_t)4095);
-constexpr size_t META_TAIL = META_REC + FRAME_WINDOW_MAX * sizeof(WalkChunk);
-constexpr size_t META_BYTES = META_TAIL + sizeof(WalkTail);
-static_assert(13 + 8 * FRAME_WINDOW_MAX <= META_TAB, "staged headers overlap the copy tables");
+constexpr size_t WALK_RECORDS = 4096;     // chunk records of one walk (bz3_hip_frame_decoded_sizes_device; a window's walk takes at most FRAME_WINDOW_MAX)
+static_assert(WALK_RECORDS >= FRAME_WINDOW_MAX, "a window's walk must fit the records");
 
-struct DeviceFrame {
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Layout of a call's small device buffer, sized for its n frames: staged headers (one 13-byte frame header per frame and one
+// 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
+// header), the walk's arguments, records and tails.
+struct MetaLayout {
+    size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, bytes = 0;
+    MetaLayout() = default;
+    explicit MetaLayout(size_t frames) : n(frames) {
+        tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
+        args = tab + align256(copy_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        rec = args + align256(n * sizeof(WalkArg));
+        tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
+        bytes = tails + align256(n * sizeof(WalkTail));
+    }
+};
+
+// Blocks per window: FRAME_WINDOW_MAX, or fewer under BZ3_HIP_FRAME_WINDOW (tests: windows that cut through frames).
+size_t frame_window_limit() {
+    size_t limit = FRAME_WINDOW_MAX;
+    if (const char * e = getenv("BZ3_HIP_FRAME_WINDOW"))
+        if (atoi(e) > 0 && (size_t)atoi(e) < limit) limit = (size_t)atoi(e);
+    return limit;
+}
+
+// The device, stream, states, slab and small buffer of one call over n frames.
+struct DeviceFrames {
     int device = -1;
-    hipStream_t s = nullptr;  // the lead state's stream (its own for the walk before the states exist)
+    hipStream_t s = nullptr;  // the lead state's stream (its own for the walks before the states exist)
     bool own_stream = false;
     u8 * meta = nullptr;
+    MetaLayout lay;
     u8 * slab = nullptr;
     size_t stride = 0;
     std::vector<bz3_state *> states;
     std::vector<CopySeg> segs;
     std::vector<u8> staging;
-    ~DeviceFrame() {
+    ~DeviceFrames() {
         if (device < 0) return;
         (void)hipSetDevice(device);
         if (s) (void)hipStreamSynchronize(s);
@@ -2276,20 +2300,20 @@ struct DeviceFrame {
         if (meta) (void)hipFree(meta);
         if (own_stream && s) (void)hipStreamDestroy(s);
     }
-    bool open(int dev) {  // the device, a stream and the small buffer
+    bool open(int dev, size_t n) {  // the device, a stream and the small buffer
         if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
         device = dev;
+        lay = MetaLayout(n);
         HIP_CHECK(hipSetDevice(dev));
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         own_stream = true;
-        HIP_CHECK(hipMalloc((void **)&meta, META_BYTES));
+        HIP_CHECK(hipMalloc((void **)&meta, lay.bytes));
         return true;
     }
-    // Up to `want` states of block_size on the device and a slab of as many slots, within the memory the headroom rule leaves; at least one or false.
+    // Up to `want` states of block_size (the call's largest) on the device and a slab of as many slots, within the memory the
+    // headroom rule leaves; at least one or false.
     bool init(u32 block_size, size_t want) {
-        size_t limit = FRAME_WINDOW_MAX;
-        if (const char * e = getenv("BZ3_HIP_FRAME_WINDOW"))  // tests: windows smaller than the frame
-            if (atoi(e) > 0 && (size_t)atoi(e) < limit) limit = (size_t)atoi(e);
+        size_t limit = frame_window_limit();
         const size_t cap = (bz3_bound(block_size) + 4096 + 255) & ~(size_t)255;  // a state's cap (new_state_on)
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -2326,228 +2350,528 @@ struct DeviceFrame {
     }
     u8 * slot(size_t k) const { return slab + k * stride; }
     void copy() {  // the segments collected in `segs`, one launch, complete on return
-        copy_segments(segs, staging, meta + META_TAB, s);
+        if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
+        copy_segments(segs, staging, meta + lay.tab, s);
         HIP_CHECK(hipStreamSynchronize(s));
         segs.clear();
     }
     void stage_headers(const std::vector<u8> & h) {
-        if (!h.empty()) HIP_CHECK(hipMemcpyAsync(meta + META_HDR, h.data(), h.size(), hipMemcpyHostToDevice, s));
+        if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
+        if (!h.empty()) HIP_CHECK(hipMemcpyAsync(meta + lay.hdr, h.data(), h.size(), hipMemcpyHostToDevice, s));
     }
-    // Up to `limit` chunk headers from (off, done, planned); the records land in rec, the resume state and the first header error in tail.
-    void walk(const u8 * in, size_t in_size, u32 block_size, u32 n_blocks, size_t buf_max, u64 off, u32 done, u64 planned, u32 limit,
-              std::vector<WalkChunk> & rec, WalkTail & tail) {
-        launch(k_frame_walk, dim3(1), dim3(64), 0, s, in, (u64)in_size, block_size, n_blocks, (u64)buf_max, off, done, planned, limit,
-               (WalkChunk *)(meta + META_REC), (WalkTail *)(meta + META_TAIL));
-        staging.resize(META_BYTES - META_REC);
-        HIP_CHECK(hipMemcpyAsync(staging.data(), meta + META_REC, staging.size(), hipMemcpyDeviceToHost, s));  // records and tail: one read-back
+    // One launch of k_frame_walk_many over args.size() frames and one read-back: tails[q] is frame q's resume state, its
+    // records are rec[args[q].rec_base ..].
+    void walk(const std::vector<WalkArg> & args, std::vector<WalkChunk> & rec, std::vector<WalkTail> & tails) {
+        const size_t n = args.size();
+        size_t nrec = 0;
+        for (const WalkArg & a : args) nrec = std::max(nrec, (size_t)a.rec_base + a.limit);
+        if (n > lay.n || nrec > WALK_RECORDS) throw std::length_error("walk larger than its buffer");
+        tails.resize(n);
+        rec.resize(nrec);
+        if (!n) return;
+        HIP_CHECK(hipMemcpyAsync(meta + lay.args, args.data(), n * sizeof(WalkArg), hipMemcpyHostToDevice, s));
+        launch(k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s, (const WalkArg *)(meta + lay.args), (u32)n,
+               (WalkChunk *)(meta + lay.rec), (WalkTail *)(meta + lay.tails));
+        if (nrec) HIP_CHECK(hipMemcpyAsync(rec.data(), meta + lay.rec, nrec * sizeof(WalkChunk), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(tails.data(), meta + lay.tails, n * sizeof(WalkTail), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        memcpy(&tail, staging.data() + (META_TAIL - META_REC), sizeof tail);
-        rec.resize(tail.count);
-        memcpy(rec.data(), staging.data(), tail.count * sizeof(WalkChunk));
     }
 };
 
-// The frame header of a frame in device memory: BZ3_OK and its two fields, or MALFORMED_HEADER (:930-936).
-int read_frame_header(DeviceFrame & f, const u8 * in, size_t in_size, u32 & block_size, u32 & n_blocks) {
-    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
-    u8 h[13];
-    HIP_CHECK(hipMemcpyAsync(h, in, 13, hipMemcpyDeviceToHost, f.s));
-    HIP_CHECK(hipStreamSynchronize(f.s));
-    if (memcmp(h, "BZ3v1", 5) != 0) return BZ3_ERR_MALFORMED_HEADER;
-    block_size = rd_le32(h + 5);
-    n_blocks = rd_le32(h + 9);
-    return BZ3_OK;
+// Where a frame's walk stands: (off, planned, done) resume it; off == 0 before its header was read.
+struct WalkPos {
+    u64 off = 0, planned = 0;
+    u32 done = 0, block_size = 0, n_blocks = 0;
+    WalkArg arg(const u8 * in, size_t in_size, size_t buf_max, u32 limit, u32 rec_base) const {
+        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0};
+    }
+    void take(const WalkTail & t) {
+        off = t.off;
+        planned = t.planned;
+        done = t.done;
+        block_size = t.block_size;
+        n_blocks = t.n_blocks;
+    }
+};
+
+// The frame headers of the frames with live[i]: one walk with limit 0.  A frame with a bad header gets its code in rcs and
+// leaves `live`.
+void walk_frame_headers(DeviceFrames & f, s32 n, const u8 * const * ins, const size_t * in_sizes, std::vector<WalkPos> & pos, std::vector<char> & live, int * rcs) {
+    std::vector<WalkArg> args;
+    std::vector<s32> who;
+    for (s32 i = 0; i < n; i++)
+        if (live[i]) {
+            args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, 0, 0));
+            who.push_back(i);
+        }
+    std::vector<WalkChunk> rec;
+    std::vector<WalkTail> tails;
+    f.walk(args, rec, tails);
+    for (size_t q = 0; q < who.size(); q++) {
+        const s32 i = who[q];
+        if (tails[q].err != BZ3_OK) {
+            rcs[i] = tails[q].err;
+            live[i] = 0;
+        } else {
+            pos[i].take(tails[q]);
+        }
+    }
 }
 
-int compress_device(u32 block_size, const u8 * in, u8 * out, size_t in_size, size_t * out_size) {
-    if (block_size > in_size) block_size = (u32)bz3_bound(in_size);  // :877
-    block_size = block_size <= (u32)KiB65 ? (u32)KiB65 : block_size;
-    u32 n_blocks = (u32)(in_size / block_size);
-    if (in_size % block_size) n_blocks++;
-    const int dev = device_of(out);
-    if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
-    DeviceFrame f;
-    try {
-        if (block_size > (u32)MiB511 || !f.open(dev) || !f.init(block_size, n_blocks)) return BZ3_ERR_INIT;  // :879-886
-    } catch (...) {
-        return BZ3_ERR_INIT;
+// ---- compress: n frames whose buffers passed the pointer checks, on device dev --------------------------------------------
+// Blocks go through windows in frame order, across frame boundaries: scatter (one copy launch), run_encode (one CM launch
+// for the window's blocks of all frames), pack (the frame headers of the frames that start in the window, the chunk headers
+// and the coded slots: one copy launch).  Every frame keeps its own output position and error.
+void compress_frames(int dev, u32 block_size_arg, s32 n, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
+    struct Frame {
+        u32 bs = 0, nb = 0, next = 0;  // effective block size, blocks, next block to scatter
+        size_t pos = 0, buf_max = 0;   // bytes written, capacity
+        bool live = false, started = false, fin = false;
+    };
+    std::vector<Frame> fr((size_t)n);
+    u32 bs_max = 0;
+    u64 total = 0;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        Frame & x = fr[i];
+        const size_t in_size = in_sizes[i];
+        u32 bs = block_size_arg;
+        if (bs > in_size) bs = (u32)bz3_bound(in_size);  // :877
+        x.bs = bs <= (u32)KiB65 ? (u32)KiB65 : bs;
+        x.nb = (u32)(in_size / x.bs);
+        if (in_size % x.bs) x.nb++;
+        if (x.bs > (u32)MiB511) {  // :879-886 (bz3_new)
+            rcs[i] = BZ3_ERR_INIT;
+            continue;
+        }
+        x.live = true;
+        bs_max = std::max(bs_max, x.bs);
+        total += x.nb;
     }
-    const size_t buf_max = *out_size;
-    *out_size = 0;
-    if (buf_max < 13 || buf_max < bz3_bound(in_size)) return BZ3_ERR_DATA_TOO_BIG;
+    if (!bs_max) return;
+    DeviceFrames f;
+    bool ok = false;
+    try {
+        ok = f.open(dev, (size_t)n) && f.init(bs_max, (size_t)std::min<u64>(total, FRAME_WINDOW_MAX));
+    } catch (...) {
+        ok = false;
+    }
+    for (s32 i = 0; i < n; i++) {
+        Frame & x = fr[i];
+        if (!x.live) continue;
+        if (!ok) {
+            rcs[i] = BZ3_ERR_INIT;
+            x.live = false;
+            continue;
+        }
+        x.buf_max = out_sizes[i];
+        out_sizes[i] = 0;
+        if (x.buf_max < 13 || x.buf_max < bz3_bound(in_sizes[i])) {  // (bz3_bound(in_size) covers the frame, so no chunk overflows it later)
+            rcs[i] = BZ3_ERR_DATA_TOO_BIG;
+            x.live = false;
+        }
+    }
+    if (!ok) return;
     try {
         DeviceGuard g(dev);
         const u32 W = (u32)f.states.size();
-        std::vector<s32> sizes(W);
+        std::vector<s32> sizes(W), orig(W), owner(W);
         std::vector<void *> slots(W);
+        std::vector<s32> heads, touched;
         std::vector<u8> hdr;
-        size_t pos = 0;
-        for (u32 i0 = 0; i0 == 0 || i0 < n_blocks; i0 += W) {
-            const u32 cnt = i0 < n_blocks ? (n_blocks - i0 < W ? n_blocks - i0 : W) : 0;
-            for (u32 k = 0; k < cnt; k++) {  // scatter: block i0 + k to slot k
-                s32 size = (s32)block_size;
-                if (i0 + k == n_blocks - 1) size = (s32)(in_size % block_size);  // (sic) :914 -- 0 when in_size is a multiple
-                sizes[k] = size;
-                slots[k] = f.slot(k);
-                f.segs.push_back({(u64)(in + (size_t)(i0 + k) * block_size), (u64)f.slot(k), (u64)size});
+        s32 cur = 0;  // frames before it are finished
+        for (;;) {
+            while (cur < n && (!fr[cur].live || fr[cur].fin)) cur++;
+            if (cur == n) break;
+            // scatter: the next W blocks in frame order, block k to slot k
+            u32 cnt = 0;
+            heads.clear();
+            touched.clear();
+            for (s32 i = cur; i < n && cnt < W; i++) {
+                Frame & x = fr[i];
+                if (!x.live || x.fin) continue;
+                if (!x.started) heads.push_back(i);
+                touched.push_back(i);
+                for (; x.next < x.nb && cnt < W; x.next++, cnt++) {
+                    s32 size = (s32)x.bs;
+                    if (x.next == x.nb - 1) size = (s32)(in_sizes[i] % x.bs);  // (sic) :914 -- 0 when in_size is a multiple
+                    sizes[cnt] = orig[cnt] = size;
+                    owner[cnt] = i;
+                    slots[cnt] = f.slot(cnt);
+                    f.states[cnt]->block_size = (s32)x.bs;  // every check of the block is made against its own frame's block size
+                    f.states[cnt]->last_error = BZ3_OK;
+                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size});
+                }
             }
-            std::vector<s32> orig(sizes.begin(), sizes.begin() + cnt);
             if (cnt) {
                 f.copy();
                 run_encode(f.states.data(), slots.data(), sizes.data(), (s32)cnt, false);
             }
-            // pack: the chunk headers (and the frame header with the first window) from the staged buffer, the coded slots behind them
+            // pack: frame headers, chunk headers from the staged buffer, the coded slots behind them
             hdr.clear();
-            if (i0 == 0) {
+            for (s32 i : heads) {
+                Frame & x = fr[i];
+                const size_t h = hdr.size();
                 hdr.insert(hdr.end(), {'B', 'Z', '3', 'v', '1'});
-                hdr.resize(13);
-                wr_le32(hdr.data() + 5, block_size);
-                wr_le32(hdr.data() + 9, n_blocks);
-                f.segs.push_back({(u64)(f.meta + META_HDR), (u64)out, 13});
-                pos = 13;
+                hdr.resize(h + 13);
+                wr_le32(hdr.data() + h + 5, x.bs);
+                wr_le32(hdr.data() + h + 9, x.nb);
+                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)outs[i], 13});
+                x.pos = 13;
+                x.started = true;
             }
-            int err = BZ3_OK;
             for (u32 k = 0; k < cnt; k++) {
+                const s32 i = owner[k];
+                Frame & x = fr[i];
+                if (!x.live) continue;  // an earlier block of its frame failed in this window
                 if (bz3_last_error(f.states[k]) != BZ3_OK) {  // :917-922
-                    err = f.states[k]->last_error;
-                    break;
+                    rcs[i] = f.states[k]->last_error;
+                    x.live = false;
+                    continue;
                 }
                 const s32 osz = sizes[k];
-                if (osz < 0 || pos + 8 + (size_t)osz > buf_max) {  // (bz3_bound(in_size) covers the frame: never taken)
-                    err = BZ3_ERR_DATA_TOO_BIG;
-                    break;
+                if (osz < 0 || x.pos + 8 + (size_t)osz > x.buf_max) {  // (never taken: bz3_bound(in_size) covers the frame)
+                    rcs[i] = BZ3_ERR_DATA_TOO_BIG;
+                    x.live = false;
+                    continue;
                 }
                 const size_t h = hdr.size();
                 hdr.resize(h + 8);
                 wr_le32(hdr.data() + h, (u32)osz);
                 wr_le32(hdr.data() + h + 4, (u32)orig[k]);
-                f.segs.push_back({(u64)(f.meta + META_HDR + h), (u64)(out + pos), 8});
-                f.segs.push_back({(u64)f.slot(k), (u64)(out + pos + 8), (u64)osz});
-                pos += (size_t)osz + 8;
+                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
+                f.segs.push_back({(u64)f.slot(k), (u64)(outs[i] + x.pos + 8), (u64)osz});
+                x.pos += (size_t)osz + 8;
             }
             f.stage_headers(hdr);
             f.copy();
-            *out_size = pos;
-            if (err != BZ3_OK) return err;
+            for (s32 i : touched) {
+                out_sizes[i] = fr[i].pos;
+                fr[i].fin = fr[i].live && fr[i].next == fr[i].nb;
+            }
         }
-        return BZ3_OK;
     } catch (const HipError & e) {
         fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
-        return BZ3_ERR_BWT;
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].live && !fr[i].fin) rcs[i] = BZ3_ERR_BWT;
     } catch (...) {
-        return BZ3_ERR_BWT;
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].live && !fr[i].fin) rcs[i] = BZ3_ERR_BWT;
     }
 }
 
-int decompress_device(const u8 * in, u8 * out, size_t in_size, size_t * out_size) {
-    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
-    const int dev = device_of(in);
-    if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
-    DeviceFrame f;
-    const size_t buf_max = *out_size;
-    std::vector<WalkChunk> rec;
-    WalkTail tail{};
-    u32 block_size = 0, n_blocks = 0;
-    try {
-        if (!f.open(dev)) return BZ3_ERR_INIT;
-        DeviceGuard g(dev);
-        const int herr = read_frame_header(f, in, in_size, block_size, n_blocks);
-        if (herr != BZ3_OK) return herr;
-        if (block_size < (u32)KiB65 || block_size > (u32)MiB511) return BZ3_ERR_INIT;  // bz3_new, :953-960
-        // n_blocks is untrusted: the window is sized from the chunks the first walk finds present, never from n_blocks
-        f.walk(in, in_size, block_size, n_blocks, buf_max, 13, 0, 0, (u32)(n_blocks < FRAME_WINDOW_MAX ? n_blocks : FRAME_WINDOW_MAX), rec, tail);
-        if (!f.init(block_size, tail.count ? tail.count : 1)) return BZ3_ERR_INIT;
-    } catch (...) {
-        return BZ3_ERR_INIT;
+// ---- decompress: n frames whose buffers passed the pointer checks, on device dev ------------------------------------------
+// One walk reads every frame header.  Then per window: the walk of the next chunks of the frames in order, up to the
+// window's size in all (one launch, one read-back), scatter, run_decode (one CM launch), gather.  Every frame keeps its
+// own resume point, committed size and error: a chunk that fails ends its frame alone, the chunks of the frame before it
+// are committed; a header error found by the walk ends the frame once the chunks before it are committed.
+void decompress_frames(int dev, s32 n, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
+    struct Frame {
+        size_t buf_max = 0, committed = 0;
+        u32 decoded = 0;        // chunks decoded and committed (pos.done: chunks walked)
+        int pending = BZ3_OK;   // the header error the walk stopped at
+        bool failed = false;    // a chunk of the current window failed
+    };
+    struct Chunk {
+        s32 frame;
+        WalkChunk rec;
+    };
+    std::vector<Frame> fr((size_t)n);
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
+        else live[i] = any = 1;
+        fr[i].buf_max = out_sizes[i];
     }
-    *out_size = 0;
+    if (!any) return;
+    DeviceFrames f;
+    std::vector<Chunk> win;
+    std::vector<WalkArg> args;
+    std::vector<s32> who;
+    std::vector<WalkChunk> rec;
+    std::vector<WalkTail> tails;
+    s32 cur = 0;  // frames before it are finished
+    // The next chunks of the live frames from `cur` on, W at most in all, into `win` (frame order).  A frame's limit is what
+    // is left of it or of the window; only a frame that stops at a header error walks fewer, and then the frames behind
+    // it are walked again with what is left of the window.
+    auto collect = [&](size_t W) {
+        win.clear();
+        while (win.size() < W) {
+            args.clear();
+            who.clear();
+            u32 budget = (u32)(W - win.size()), base = 0;
+            for (s32 i = cur; i < n && budget; i++) {
+                if (!live[i] || fr[i].pending != BZ3_OK || pos[i].done == pos[i].n_blocks) continue;
+                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+                args.push_back(pos[i].arg(ins[i], in_sizes[i], fr[i].buf_max, lim, base));
+                who.push_back(i);
+                base += lim;
+                budget -= lim;
+            }
+            if (args.empty()) return;
+            f.walk(args, rec, tails);
+            bool stopped = false;
+            for (size_t q = 0; q < who.size(); q++) {
+                const s32 i = who[q];
+                for (u32 r = 0; r < tails[q].count; r++) win.push_back({i, rec[args[q].rec_base + r]});
+                pos[i].take(tails[q]);
+                if (tails[q].err != BZ3_OK) {
+                    fr[i].pending = tails[q].err;
+                    stopped = true;
+                }
+            }
+            if (!stopped) return;  // every frame walked its limit: the window is full or no chunk is left
+        }
+    };
+    // Chunks of `win` beyond the first W go back to their frames (the first window is walked before the states exist).
+    auto give_back = [&](size_t W) {
+        while (win.size() > W) {
+            const Chunk & c = win.back();
+            WalkPos & p = pos[c.frame];
+            p.off = c.rec.in_off;
+            p.planned = c.rec.out_off;
+            p.done--;
+            fr[c.frame].pending = BZ3_OK;  // found again by a later walk
+            win.pop_back();
+        }
+    };
+    u32 bs_max = 0;
+    try {
+        if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) bs_max = std::max(bs_max, pos[i].block_size);
+        if (!bs_max) return;
+        // n_blocks is untrusted: the states are sized from the chunks the first walk finds present, never from n_blocks
+        collect(frame_window_limit());
+        if (!f.init(bs_max, win.empty() ? 1 : win.size())) throw std::runtime_error("no states");
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_INIT;
+        return;
+    }
+    for (s32 i = 0; i < n; i++)
+        if (live[i]) out_sizes[i] = 0;
     try {
         DeviceGuard g(dev);
         const u32 W = (u32)f.states.size();
         std::vector<s32> sizes(W), orig(W);
-        std::vector<size_t> caps(W, bz3_bound(block_size));
+        std::vector<size_t> caps(W);
         std::vector<void *> slots(W);
         std::vector<u8> hdrs(17 * (size_t)W);
-        u64 off = 13, planned = 0;
-        u32 done = 0;
-        for (bool first = true; done < n_blocks; first = false) {
-            if (!first) f.walk(in, in_size, block_size, n_blocks, buf_max, off, done, planned, n_blocks - done < W ? n_blocks - done : W, rec, tail);
-            const u32 t = tail.count < W ? tail.count : W;
-            const int header_error = t == tail.count ? tail.err : BZ3_OK;  // (a header error beyond this window is found again by the next walk)
-            for (u32 k = 0; k < t; k++) {  // unpack: chunk k to slot k
-                sizes[k] = rec[k].size;
-                orig[k] = rec[k].orig;
+        give_back(W);
+        for (bool first = true;; first = false) {
+            if (!first) collect(W);
+            const u32 t = (u32)win.size();
+            for (u32 k = 0; k < t; k++) {  // scatter: chunk k to slot k
+                const Chunk & c = win[k];
+                sizes[k] = c.rec.size;
+                orig[k] = c.rec.orig;
                 slots[k] = f.slot(k);
-                memcpy(hdrs.data() + 17 * (size_t)k, rec[k].hdr, 17);
-                f.segs.push_back({(u64)(in + rec[k].in_off + 8), (u64)f.slot(k), (u64)rec[k].size});
+                caps[k] = bz3_bound(pos[c.frame].block_size);
+                f.states[k]->block_size = (s32)pos[c.frame].block_size;  // every check of the block is made against its own frame's block size
+                f.states[k]->last_error = BZ3_OK;
+                memcpy(hdrs.data() + 17 * (size_t)k, c.rec.hdr, 17);
+                f.segs.push_back({(u64)(ins[c.frame] + c.rec.in_off + 8), (u64)f.slot(k), (u64)c.rec.size});
             }
-            u32 ok = 0;
             if (t) {
                 f.copy();
                 run_decode(f.states.data(), slots.data(), caps.data(), sizes.data(), orig.data(), hdrs.data(), (s32)t, false);
-                while (ok < t && bz3_last_error(f.states[ok]) == BZ3_OK) ok++;
-                for (u32 k = 0; k < ok; k++) f.segs.push_back({(u64)f.slot(k), (u64)(out + rec[k].out_off), (u64)rec[k].orig});  // gather
+                for (u32 k = 0; k < t; k++) {  // gather: per frame, the chunks before its first failure
+                    const Chunk & c = win[k];
+                    Frame & x = fr[c.frame];
+                    if (x.failed) continue;
+                    if (bz3_last_error(f.states[k]) != BZ3_OK) {  // :989-993
+                        rcs[c.frame] = f.states[k]->last_error;
+                        x.failed = true;
+                        continue;
+                    }
+                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig});
+                    x.committed = c.rec.out_off + (size_t)c.rec.orig;
+                    x.decoded++;
+                }
                 f.copy();
-                if (ok) *out_size = rec[ok - 1].out_off + (size_t)rec[ok - 1].orig;
-                if (ok < t) return f.states[ok]->last_error;  // :989-993
             }
-            if (header_error != BZ3_OK) return header_error;
-            done += t;
-            if (t < tail.count) {
-                off = rec[t].in_off;
-                planned = rec[t].out_off;
-            } else {
-                off = tail.off;
-                planned = tail.planned;
+            // a frame ends at a failed chunk, or once every chunk it walked is committed and the walk is over (all chunks, or a header error)
+            bool left = false;
+            for (s32 i = cur; i < n; i++) {
+                if (!live[i]) continue;
+                Frame & x = fr[i];
+                out_sizes[i] = x.committed;
+                if (x.failed) live[i] = 0;
+                else if (x.decoded == pos[i].done && (x.pending != BZ3_OK || pos[i].done == pos[i].n_blocks)) {
+                    rcs[i] = x.pending;
+                    live[i] = 0;
+                } else {
+                    left = true;
+                }
             }
+            while (cur < n && !live[cur]) cur++;
+            if (!left) break;
         }
-        return BZ3_OK;
     } catch (const HipError & e) {
         fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
-        return BZ3_ERR_BWT;
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_BWT;
     } catch (...) {
-        return BZ3_ERR_BWT;
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_BWT;
     }
 }
 
-int frame_decoded_size_device(const u8 * in, size_t in_size, size_t * decoded_size) {
-    *decoded_size = 0;
-    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
-    const int dev = device_of(in);
-    if (dev < 0) return BZ3_ERR_INIT;
-    try {
-        DeviceFrame f;
-        if (!f.open(dev)) return BZ3_ERR_INIT;
-        DeviceGuard g(dev);
-        u32 block_size = 0, n_blocks = 0;
-        const int herr = read_frame_header(f, in, in_size, block_size, n_blocks);
-        if (herr != BZ3_OK) return herr;
-        if (block_size < (u32)KiB65 || block_size > (u32)MiB511) return BZ3_ERR_INIT;  // what bz3_decompress reports for it
-        std::vector<WalkChunk> rec;
-        WalkTail tail{13, 0, 0, 0, BZ3_OK, 0};
-        while (tail.done < n_blocks && tail.err == BZ3_OK) {
-            const u32 left = n_blocks - tail.done;
-            f.walk(in, in_size, block_size, n_blocks, SIZE_MAX, tail.off, tail.done, tail.planned, left < FRAME_WINDOW_MAX ? left : (u32)FRAME_WINDOW_MAX, rec, tail);
-            *decoded_size = tail.planned;
-        }
-        return tail.err;
-    } catch (...) {
-        return BZ3_ERR_INIT;
+// ---- decoded sizes: n frames' chunk headers, walked in rounds of up to WALK_RECORDS chunks over all frames -------------------
+void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t * in_sizes, size_t * decoded, int * rcs) {
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        decoded[i] = 0;
+        rcs[i] = BZ3_OK;
+        if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;
+        else live[i] = any = 1;
     }
+    if (!any) return;
+    try {
+        DeviceFrames f;
+        if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // a block size bz3_new refuses: BZ3_ERR_INIT, what bz3_decompress reports for it
+        std::vector<WalkArg> args;
+        std::vector<s32> who;
+        std::vector<WalkChunk> rec;
+        std::vector<WalkTail> tails;
+        for (;;) {
+            args.clear();
+            who.clear();
+            u32 budget = (u32)WALK_RECORDS, base = 0;
+            for (s32 i = 0; i < n && budget; i++) {
+                if (!live[i]) continue;
+                if (pos[i].done == pos[i].n_blocks) {
+                    live[i] = 0;
+                    continue;
+                }
+                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+                args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, lim, base));
+                who.push_back(i);
+                base += lim;
+                budget -= lim;
+            }
+            if (args.empty()) break;
+            f.walk(args, rec, tails);
+            for (size_t q = 0; q < who.size(); q++) {
+                const s32 i = who[q];
+                pos[i].take(tails[q]);
+                decoded[i] = pos[i].planned;
+                if (tails[q].err != BZ3_OK) {
+                    rcs[i] = tails[q].err;
+                    live[i] = 0;
+                }
+            }
+        }
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_INIT;
+    }
+}
+
+// ---- the entry points' argument checks ------------------------------------------------------------------------------------
+// The GPU of a call: every non-empty buffer (a[i] with a_sizes[i] > 0, likewise b) must be device memory of the GPU the first
+// one lives on.  -1: no buffer is non-empty; -2: one is not.
+int frames_device(s32 n, const void * const * a, const size_t * a_sizes, const void * const * b, const size_t * b_sizes) {
+    int dev = -1;
+    auto check = [&](const void * p) {
+        const int d = device_of(p);
+        if (d < 0 || (dev >= 0 && d != dev)) return false;
+        dev = d;
+        return true;
+    };
+    for (s32 i = 0; i < n; i++) {
+        if (a_sizes[i] && !check(a[i])) return -2;
+        if (b && b_sizes[i] && !check(b[i])) return -2;
+    }
+    return dev;
+}
+
+// Whole-call failure: every frame gets `rc` and size 0.
+int fail_frames(s32 n, int * rcs, size_t * sizes, int rc) {
+    for (s32 i = 0; i < n; i++) {
+        if (rcs) rcs[i] = rc;
+        if (sizes) sizes[i] = 0;
+    }
+    return rc;
+}
+
+int first_error(s32 n, const int * rcs) {
+    for (s32 i = 0; i < n; i++)
+        if (rcs[i] != BZ3_OK) return rcs[i];
+    return BZ3_OK;
 }
 
 }  // namespace
 
 BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
-    return compress_device(block_size, (const u8 *)in, (u8 *)out, in_size, out_size);
+    const int dev = device_of(out);
+    if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    u8 * outs[1] = {(u8 *)out};
+    int rc = BZ3_OK;
+    compress_frames(dev, block_size, 1, ins, &in_size, outs, out_size, &rc);
+    return rc;
 }
 
 BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
-    return decompress_device((const u8 *)in, (u8 *)out, in_size, out_size);
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    u8 * outs[1] = {(u8 *)out};
+    int rc = BZ3_OK;
+    decompress_frames(dev, 1, ins, &in_size, outs, out_size, &rc);
+    return rc;
 }
 
 BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size) {
-    return frame_decoded_size_device((const u8 *)in, in_size, decoded_size);
+    *decoded_size = 0;
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    int rc = BZ3_OK;
+    decoded_sizes_frames(dev, 1, ins, &in_size, decoded_size, &rc);
+    return rc;
+}
+
+BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                           size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    compress_frames(dev, block_size, n, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_many(int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[], size_t out_sizes[],
+                                             int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    decompress_frames(dev, n, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const ins[], const size_t in_sizes[], size_t decoded_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !decoded_sizes || !rcs) return fail_frames(n, rcs, decoded_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, nullptr, nullptr);
+    if (dev == -2) return fail_frames(n, rcs, decoded_sizes, BZ3_ERR_INIT);
+    decoded_sizes_frames(dev, n, (const u8 * const *)ins, in_sizes, decoded_sizes, rcs);
+    return first_error(n, rcs);
 }
 
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) {

@@ -3,8 +3,9 @@
 // A frame (src/libbz3.c:876-997) is a 13-byte header, then per block an 8-byte chunk header (coded size, original size)
 // and the coded bytes.  Moving a window of blocks between the caller's buffers and the states' slots is a list of
 // byte segments at arbitrary alignments on both sides: k_copy_segments moves them all in one launch.  Decoding
-// needs the chunk headers, which form a chain (each one's offset depends on the sizes before it): k_frame_walk
-// follows that chain on one lane and hands the host every chunk's offsets and first 17 bytes in one read-back.
+// needs the chunk headers, which form a chain (each one's offset depends on the sizes before it): k_frame_walk_many
+// follows the chains of many frames, one lane per frame, and hands the host every chunk's offsets and first 17 bytes
+// in one read-back.
 #pragma once
 #include "../../include/libbz3.h"
 #include "hipx.hpp"
@@ -13,7 +14,7 @@ namespace bz3 {
 
 // The four checks of one chunk header in bz3_decompress (src/libbz3.c:963-985), in the reference's order.  `p` points at
 // the chunk header, `in_left` bytes of the frame remain from there, `planned` bytes of output precede the chunk.
-// Shared by the host loop (bz3_decompress) and the device walk (k_frame_walk), so the rules exist once.
+// Shared by the host loop (bz3_decompress) and the device walk (k_frame_walk_many), so the rules exist once.
 __host__ __device__ inline int frame_chunk_check(const u8 * p, size_t in_left, u32 block_size, size_t buf_max, size_t planned,
                                                  s32 * size, s32 * orig_size) {
     if (in_left < 8) return BZ3_ERR_MALFORMED_HEADER;  // :963
@@ -123,10 +124,12 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
     }
 }
 
-// ---- k_frame_walk ----------------------------------------------------------------------------------------------------
-// Up to `limit` chunk headers of a frame (`frame`, `in_size` bytes including the 13-byte header), from the state
-// (off = offset of the next chunk header, done = chunks behind, planned = output bytes before it).  One lane: every
-// header's offset depends on the one before it.
+// ---- k_frame_walk_many -----------------------------------------------------------------------------------------------
+// The chunk headers of n frames, one lane per frame (the headers of one frame form a chain: every header's offset depends
+// on the one before it).  Lane i resumes frame i from its state (off = offset of the next chunk header, done = chunks
+// behind, planned = output bytes before it); off == 0 is the first visit, which reads and checks the 13-byte frame header
+// first (src/libbz3.c:930-960) and then walks from offset 13.  It walks up to `limit` chunks, writes their records from
+// rec[rec_base] on and its resume state to tails[i].
 struct WalkChunk {
     u64 in_off;   // offset of the chunk header in the frame
     u64 out_off;  // output bytes of the chunks before it (planned)
@@ -134,40 +137,67 @@ struct WalkChunk {
     u8 hdr[17];   // the first 17 bytes of the chunk's coded bytes (zeros beyond the end of the frame)
     u8 pad[7];
 };
+struct WalkArg {
+    u64 in, in_size, buf_max;  // the frame (device address, bytes), the output capacity
+    u64 off, planned;          // resume state (off == 0: first visit)
+    u32 done, limit, rec_base;
+    u32 block_size, n_blocks;  // from the frame header (ignored on a first visit)
+    u32 pad;
+};
 struct WalkTail {
     u64 off, planned;  // resume state after the last well-formed chunk read
     u32 done;
     u32 count;  // chunks written to the records
     s32 err;    // BZ3_OK, or the first header error (the walk stopped at it)
+    u32 block_size, n_blocks;  // the frame header's fields
     u32 pad;
 };
+static_assert(sizeof(WalkChunk) % 16 == 0 && sizeof(WalkArg) % 8 == 0 && sizeof(WalkTail) % 8 == 0, "walk records are packed arrays");
+constexpr u32 WALK_THREADS = 64;
 
-__global__ void __launch_bounds__(64) k_frame_walk(const u8 * __restrict__ frame, u64 in_size, u32 block_size, u32 n_blocks, u64 buf_max,
-                                                   u64 off, u32 done, u64 planned, u32 limit, WalkChunk * __restrict__ rec, WalkTail * __restrict__ tail) {
-    if (threadIdx.x != 0) return;
-    u32 c = 0;
+__global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
+                                                                  WalkTail * __restrict__ tails) {
+    const u32 i = blockIdx.x * WALK_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const WalkArg a = args[i];
+    const u8 * frame = (const u8 *)a.in;
+    u64 off = a.off, planned = a.planned;
+    u32 done = a.done, block_size = a.block_size, n_blocks = a.n_blocks, c = 0;
     int err = BZ3_OK;
-    while (c < limit && done < n_blocks) {
+    if (off == 0) {  // the frame header, in the order of decompress: size and magic (:930-936), then what bz3_new accepts (:953-960)
+        if (a.in_size < 13 || frame[0] != 'B' || frame[1] != 'Z' || frame[2] != '3' || frame[3] != 'v' || frame[4] != '1') {
+            err = BZ3_ERR_MALFORMED_HEADER;
+        } else {
+            block_size = (u32)frame[5] | ((u32)frame[6] << 8) | ((u32)frame[7] << 16) | ((u32)frame[8] << 24);
+            n_blocks = (u32)frame[9] | ((u32)frame[10] << 8) | ((u32)frame[11] << 16) | ((u32)frame[12] << 24);
+            if (block_size < 65u * 1024 || block_size > 511u * 1024 * 1024) err = BZ3_ERR_INIT;
+            off = 13;
+        }
+    }
+    while (err == BZ3_OK && c < a.limit && done < n_blocks) {
         s32 size = 0, orig = 0;
-        err = frame_chunk_check(frame + off, in_size - off, block_size, (size_t)buf_max, (size_t)planned, &size, &orig);
+        err = frame_chunk_check(frame + off, a.in_size - off, block_size, (size_t)a.buf_max, (size_t)planned, &size, &orig);
         if (err != BZ3_OK) break;
-        WalkChunk & w = rec[c];
+        WalkChunk & w = rec[a.rec_base + c];
         w.in_off = off;
         w.out_off = planned;
         w.size = size;
         w.orig = orig;
         const u64 data = off + 8;
-        for (u32 i = 0; i < 17; i++) w.hdr[i] = data + i < in_size ? frame[data + i] : (u8)0;
+        for (u32 k = 0; k < 17; k++) w.hdr[k] = data + k < a.in_size ? frame[data + k] : (u8)0;
         off = data + (u64)size;
         planned += (u64)orig;
         done++;
         c++;
     }
-    tail->off = off;
-    tail->planned = planned;
-    tail->done = done;
-    tail->count = c;
-    tail->err = err;
+    WalkTail & t = tails[i];
+    t.off = off;
+    t.planned = planned;
+    t.done = done;
+    t.count = c;
+    t.err = err;
+    t.block_size = block_size;
+    t.n_blocks = n_blocks;
 }
 
 }  // namespace bz3

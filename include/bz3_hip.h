@@ -124,6 +124,25 @@ BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_s
  * bz3_decompress would report first for the frame's headers (MALFORMED_HEADER / TRUNCATED_DATA; BZ3_ERR_INIT for a block size bz3_new
  * refuses or a pointer that is not device memory). */
 BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size);
+/* n independent frames on ONE GPU in one call: frame i gets exactly the bytes, return code and out_sizes[i] that
+ * bz3_hip_compress_device(block_size, ins[i], outs[i], in_sizes[i], &out_sizes[i]) (bz3_hip_decompress_device(ins[i], outs[i],
+ * in_sizes[i], &out_sizes[i])) would give it alone (out_sizes[i]: capacity on entry, bytes written on return; errors included: a short
+ * output, a corrupt chunk after committed ones, header errors in the reference's order).  One frame's failure never changes another
+ * frame's result, and a failing frame's later blocks go into no later window.  Blocks of all frames go through windows of up to 256
+ * blocks in frame order, across frame boundaries, so one window's CM launch codes blocks of many frames; every block is checked
+ * against its own frame's block size (compress: the :877 rule per frame; decode: each frame's header).  rcs[i] receives frame i's code;
+ * returns BZ3_OK if all are BZ3_OK, else the code of the lowest-indexed failing frame.  n == 0 returns BZ3_OK and touches nothing.
+ * Before any write, BZ3_ERR_INIT for the whole call, in every rcs[i] and with every out_sizes[i] = 0: n < 0; a NULL array with n > 0;
+ * a non-empty buffer (ins[i] with in_sizes[i] > 0, outs[i] with out_sizes[i] > 0) that is not device memory of the GPU the first
+ * non-empty buffer lives on (an empty buffer is not looked at).  Synchronous, with the headroom rule, as the single-frame calls. */
+BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[],
+                                           void * const outs[], size_t out_sizes[], int rcs[]);
+BZIP3_API int bz3_hip_decompress_device_many(int32_t n, const void * const ins[], const size_t in_sizes[],
+                                             void * const outs[], size_t out_sizes[], int rcs[]);
+/* bz3_hip_frame_decoded_size_device for n frames, in one walk: decoded_sizes[i] and rcs[i] as the single call gives them; the return
+ * code and the whole-call checks as bz3_hip_decompress_device_many (with no output buffers). */
+BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const ins[], const size_t in_sizes[],
+                                                 size_t decoded_sizes[], int rcs[]);
 /* Test hook: one launch of the segment copy kernel (frame.hpp k_copy_segments) on the device that owns `dst`: n (src_off, dst_off, len)
  * triples (host array of 3 n u64) relative to `src` / `dst`, non-overlapping on the destination side.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n);
