@@ -78,6 +78,11 @@ def _declare(L, strict=True):
         "bz3_hip_decompress_device_many": (C.c_int, [i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_frame_decoded_sizes_device": (C.c_int, [i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_copy_segments": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_compress_device_planes": (C.c_int, [u32, u32, vp, vp, sz, C.POINTER(sz)]),
+        "bz3_hip_decompress_device_planes": (C.c_int, [u32, vp, vp, sz, C.POINTER(sz)]),
+        "bz3_hip_compress_device_planes_many": (C.c_int, [u32, i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_decompress_device_planes_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_planes": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -308,33 +313,50 @@ def _device_u8(x, what):
     return x
 
 
-def compress_tensor(x, block_size=16 << 20, lib=None):
+def _planes_arg(planes, n):
+    """`planes` of the batched calls: an int for every tensor, or one int per tensor."""
+    ks = [int(planes)] * n if isinstance(planes, int) else [int(k) for k in planes]
+    if len(ks) != n:
+        raise ValueError(f"planes: {len(ks)} element sizes for {n} tensors")
+    for k in ks:
+        if k not in (1, 2, 4, 8):
+            raise ValueError(f"planes must be 1, 2, 4 or 8, not {k}")
+    return ks
+
+
+def compress_tensor(x, block_size=16 << 20, lib=None, planes=1):
     """The .bz3 frame of the bytes of `x` (a contiguous torch.uint8 GPU tensor; view a tensor of another dtype with
-    .view(torch.uint8).flatten()), computed on x's GPU: a uint8 tensor on the same device holding exactly the frame bytes of
-    bz3_compress.  The result is a view of a bz3_bound(x.numel())-byte allocation (.clone() it to drop the slack).  Synchronises
-    x's device first; raises Bz3Error with the return code on failure."""
+    .view(torch.uint8).flatten(), or use pack_tensor), computed on x's GPU: a uint8 tensor on the same device holding exactly the
+    frame bytes of bz3_compress.  The result is a view of a bz3_bound(x.numel())-byte allocation (.clone() it to drop the slack).
+    Synchronises x's device first; raises Bz3Error with the return code on failure.  `planes` = 2, 4 or 8: every block is split into
+    the byte planes of its `planes`-byte elements first (bz3_hip_compress_device_planes); pass the same value to decompress_tensor.
+    As bz3_compress does (src/libbz3.c:914), an input whose size is a non-zero multiple of the block size loses its last block without
+    an error: pack_tensor chooses a block size at which nothing is lost."""
     import torch
 
     x = _device_u8(x, "x")
+    (k,) = _planes_arg(planes, 1)
     L = lib or load()
     n = x.numel()
     out = torch.empty(L.bz3_bound(n), dtype=torch.uint8, device=x.device)
     size = C.c_size_t(out.numel())
     torch.cuda.synchronize(x.device)
-    rc = L.bz3_hip_compress_device(block_size, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, C.byref(size))
+    rc = L.bz3_hip_compress_device_planes(block_size, k, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, C.byref(size))
     if rc != BZ3_OK:
-        raise Bz3Error(rc, "bz3_hip_compress_device")
+        raise Bz3Error(rc, "bz3_hip_compress_device_planes")
     return out[: size.value]
 
 
-def decompress_tensor(frame, out=None, lib=None):
+def decompress_tensor(frame, out=None, lib=None, planes=1):
     """The bytes of a .bz3 frame held in a contiguous torch.uint8 GPU tensor, decoded on its GPU.  `out`: a contiguous uint8 tensor
     on the same device to decode into (its size is the capacity); by default one of the frame's decoded size
     (bz3_hip_frame_decoded_size_device).  Returns the view of `out` holding the decoded bytes; raises Bz3Error with the return code
-    of bz3_hip_decompress_device, whose `.out` holds the bytes of the chunks decoded before the error."""
+    of bz3_hip_decompress_device_planes, whose `.out` holds the bytes of the chunks decoded before the error.  `planes`: the value the
+    frame was compressed with (it is not stored in the frame)."""
     import torch
 
     frame = _device_u8(frame, "frame")
+    (k,) = _planes_arg(planes, 1)
     L = lib or load()
     torch.cuda.synchronize(frame.device)
     if out is None:
@@ -345,9 +367,9 @@ def decompress_tensor(frame, out=None, lib=None):
     else:
         out = _device_u8(out, "out")
     size = C.c_size_t(out.numel())
-    rc = L.bz3_hip_decompress_device(C.c_void_p(frame.data_ptr()), C.c_void_p(out.data_ptr()), frame.numel(), C.byref(size))
+    rc = L.bz3_hip_decompress_device_planes(k, C.c_void_p(frame.data_ptr()), C.c_void_p(out.data_ptr()), frame.numel(), C.byref(size))
     if rc != BZ3_OK:
-        raise Bz3Error(rc, "bz3_hip_decompress_device", out[: size.value])
+        raise Bz3Error(rc, "bz3_hip_decompress_device_planes", out[: size.value])
     return out[: size.value]
 
 
@@ -375,45 +397,60 @@ def _carve(total, sizes, device):
     return [buf[a : a + n] for a, n in zip(offs, sizes)]
 
 
-def compress_tensors(xs, block_size=16 << 20, lib=None):
-    """compress_tensor for many tensors in ONE call (bz3_hip_compress_device_many): frame i is exactly compress_tensor(xs[i],
-    block_size).  Blocks of all tensors share windows of up to 256 blocks, so many small tensors (a state_dict) code in a few CM
-    launches instead of one per tensor.  All tensors must be contiguous torch.uint8 tensors on one GPU; one device synchronisation
-    per call.  The frames are views of one allocation of bz3_bound bytes per tensor (.clone() one to drop the rest).  Raises
-    Bz3Error (with .index / .codes / .outs) if any frame fails.  [] returns []."""
+def _compress_many(L, xs, block_sizes, ks, dev, slack=False):
+    """One bz3_hip_compress_device_planes_many call per distinct block size (one, unless pack_state_dict had to move some): frames
+    in the order of xs.  `slack`: room for the frame and chunk headers on top of bz3_bound, which covers the coded blocks alone (a
+    small incompressible tensor's frame is a few bytes longer than bz3_bound of its size)."""
     import torch
 
-    xs = [_device_u8(x, f"xs[{i}]") for i, x in enumerate(xs)]
-    if not xs:
-        return []
-    dev = _same_device(xs, "compress_tensors")
-    L = lib or load()
     n = len(xs)
-    caps = [L.bz3_bound(x.numel()) for x in xs]
+    caps = [L.bz3_bound(x.numel()) + ((13 + 8 * (x.numel() // _KiB65 + 2) + 15) & ~15 if slack else 0) for x in xs]
     outs = _carve(sum(caps), caps, dev)
-    in_sizes = (C.c_size_t * n)(*[x.numel() for x in xs])
-    out_sizes = (C.c_size_t * n)(*caps)
-    rcs = (C.c_int * n)()
+    frames, codes = [None] * n, [BZ3_OK] * n
     torch.cuda.synchronize(dev)
-    rc = L.bz3_hip_compress_device_many(block_size, n, _ptrs(xs), in_sizes, _ptrs(outs), out_sizes, rcs)
-    frames = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
+    for bs in sorted(set(block_sizes)):
+        idx = [i for i in range(n) if block_sizes[i] == bs]
+        g = len(idx)
+        out_sizes = (C.c_size_t * g)(*[caps[i] for i in idx])
+        rcs = (C.c_int * g)()
+        L.bz3_hip_compress_device_planes_many(bs, g, (C.c_uint32 * g)(*[ks[i] for i in idx]), _ptrs([xs[i] for i in idx]),
+                                              (C.c_size_t * g)(*[xs[i].numel() for i in idx]), _ptrs([outs[i] for i in idx]), out_sizes, rcs)
+        for j, i in enumerate(idx):
+            frames[i], codes[i] = outs[i][: out_sizes[j]], rcs[j]
+    if any(c != BZ3_OK for c in codes):
         idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(rc, "bz3_hip_compress_device_many", index=idx, codes=codes, outs=frames)
+        raise Bz3Error(codes[idx], "bz3_hip_compress_device_planes_many", index=idx, codes=codes, outs=frames)
     return frames
 
 
-def decompress_tensors(frames, outs=None, lib=None):
-    """decompress_tensor for many frames in ONE call (bz3_hip_decompress_device_many): result i is exactly
-    decompress_tensor(frames[i], outs[i]).  `outs`: contiguous uint8 tensors on the frames' GPU, one per frame (their sizes are the
-    capacities); by default views of one allocation sized with bz3_hip_frame_decoded_sizes_device.  One device synchronisation per
-    call.  Raises Bz3Error (with .index / .codes / .outs, the bytes committed per frame) if any frame fails.  [] returns []."""
+def compress_tensors(xs, block_size=16 << 20, lib=None, planes=1):
+    """compress_tensor for many tensors in ONE call (bz3_hip_compress_device_planes_many): frame i is exactly compress_tensor(xs[i],
+    block_size, planes=planes[i]).  Blocks of all tensors share windows of up to 256 blocks, so many small tensors (a state_dict) code
+    in a few CM launches instead of one per tensor.  All tensors must be contiguous torch.uint8 tensors on one GPU; one device
+    synchronisation per call.  The frames are views of one allocation of bz3_bound bytes per tensor (.clone() one to drop the rest).
+    `planes`: an int, or one int per tensor.  Raises Bz3Error (with .index / .codes / .outs) if any frame fails.  [] returns [].  As
+    bz3_compress does (src/libbz3.c:914), a tensor whose size is a non-zero multiple of the block size loses its last block without an
+    error: pack_state_dict chooses block sizes at which nothing is lost."""
+    xs = [_device_u8(x, f"xs[{i}]") for i, x in enumerate(xs)]
+    if not xs:
+        return []
+    ks = _planes_arg(planes, len(xs))
+    dev = _same_device(xs, "compress_tensors")
+    return _compress_many(lib or load(), xs, [block_size] * len(xs), ks, dev)
+
+
+def decompress_tensors(frames, outs=None, lib=None, planes=1):
+    """decompress_tensor for many frames in ONE call (bz3_hip_decompress_device_planes_many): result i is exactly
+    decompress_tensor(frames[i], outs[i], planes=planes[i]).  `outs`: contiguous uint8 tensors on the frames' GPU, one per frame (their
+    sizes are the capacities); by default views of one allocation sized with bz3_hip_frame_decoded_sizes_device.  `planes`: an int, or
+    one int per frame.  One device synchronisation per call.  Raises Bz3Error (with .index / .codes / .outs, the bytes committed per
+    frame) if any frame fails.  [] returns []."""
     import torch
 
     frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
     if not frames:
         return []
+    ks = _planes_arg(planes, len(frames))
     dev = _same_device(frames, "decompress_tensors")
     L = lib or load()
     n = len(frames)
@@ -433,13 +470,179 @@ def decompress_tensors(frames, outs=None, lib=None):
         _same_device(frames + outs, "decompress_tensors")
     out_sizes = (C.c_size_t * n)(*[o.numel() for o in outs])
     rcs = (C.c_int * n)()
-    rc = L.bz3_hip_decompress_device_many(n, in_ptrs, in_sizes, _ptrs(outs), out_sizes, rcs)
+    rc = L.bz3_hip_decompress_device_planes_many(n, (C.c_uint32 * n)(*ks), in_ptrs, in_sizes, _ptrs(outs), out_sizes, rcs)
     res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
     if rc != BZ3_OK:
         codes = list(rcs)
         idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(rc, "bz3_hip_decompress_device_many", index=idx, codes=codes, outs=res)
+        raise Bz3Error(rc, "bz3_hip_decompress_device_planes_many", index=idx, codes=codes, outs=res)
     return res
+
+
+# ---- typed tensors ------------------------------------------------------------------------------------------------------------
+# The byte-plane element size pack_tensor uses when `planes` is None, by dtype name: the component size where the measurements of
+# DESIGN.md ("Typed tensors") show the planes frame smaller than the interleaved one, 1 where they show it larger or no different
+# (16-bit floats, int32) and for every dtype nobody measured.
+DEFAULT_PLANES = {
+    "float32": 4,
+    "float64": 8,
+    "int64": 8,
+    "complex64": 4,
+    "complex128": 8,
+    "bfloat16": 1,
+    "float16": 1,
+    "int32": 1,
+    "int16": 1,
+    "int8": 1,
+    "uint8": 1,
+    "bool": 1,
+}
+_KiB65, _MiB511 = 65 * 1024, 511 << 20
+
+
+def default_planes(dtype):
+    """DEFAULT_PLANES[dtype] (1 for a dtype that is not in the table)."""
+    return DEFAULT_PLANES.get(str(dtype).replace("torch.", ""), 1)
+
+
+def _lossless_block_size(nbytes, block_size, planes):
+    """The block size the typed calls hand to the library for a tensor of `nbytes` bytes: the multiple of `planes` closest to
+    `block_size` at which bz3_compress drops nothing.  bz3_compress gives its last block nbytes % bs bytes (src/libbz3.c:914), so a
+    size that is a non-zero multiple of bs loses a block, unless bs > nbytes, where :877 replaces bs by bz3_bound(nbytes) and the
+    input is one block.  The result bs satisfies: bs % planes == 0; 65 KiB <= bs; the block size in effect after :877-878 is at most
+    511 MiB; and nbytes == 0, or bs > nbytes, or nbytes % bs != 0.  It is searched downwards from block_size (clamped to
+    [65 KiB, 511 MiB] and rounded down to a multiple of planes) in steps of planes, and upwards from there once the 65 KiB floor is
+    reached.  Pure arithmetic: no GPU, no library call."""
+    if planes not in (1, 2, 4, 8):
+        raise ValueError(f"planes must be 1, 2, 4 or 8, not {planes}")
+
+    def ok(bs):
+        eff = max(_KiB65, bs if bs <= nbytes else nbytes + nbytes // 50 + 32)  # :877-878 (bz3_bound)
+        return eff <= _MiB511 and (nbytes == 0 or bs > nbytes or nbytes % bs != 0)
+
+    start = min(max(int(block_size), _KiB65), _MiB511)
+    start -= start % planes
+    bs = start
+    if bs > nbytes > 0 and not ok(bs):  # one block of bz3_bound(nbytes) > 511 MiB: no size above nbytes will do either
+        bs = nbytes - nbytes % planes
+    while bs >= _KiB65:
+        if ok(bs):
+            return bs
+        bs -= planes
+    bs = start + planes
+    while not ok(bs):
+        bs += planes
+    return bs
+
+
+class PackedTensor:
+    """A tensor as pack_tensor leaves it: `frame` (a uint8 GPU tensor holding a .bz3 frame of the tensor's bytes, split into byte planes
+    of `planes` bytes per block), and what unpack_tensor needs to restore it: `dtype`, `shape`, `planes`, `block_size` (the one really
+    used, see _lossless_block_size) and `nbytes`."""
+
+    __slots__ = ("frame", "dtype", "shape", "planes", "block_size", "nbytes")
+
+    def __init__(self, frame, dtype, shape, planes, block_size, nbytes):
+        self.frame, self.dtype, self.shape, self.planes, self.block_size, self.nbytes = frame, dtype, shape, planes, block_size, nbytes
+
+    def __repr__(self):
+        return f"PackedTensor({self.dtype}, {tuple(self.shape)}, planes={self.planes}, block_size={self.block_size}, {self.frame.numel()} of {self.nbytes} bytes)"
+
+
+def _as_bytes(x, what):
+    import torch
+
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise TypeError(f"{what} must be a torch tensor on a GPU")
+    x = x.detach().contiguous()
+    if x.is_complex():
+        x = torch.view_as_real(x)
+    return x.reshape(-1).view(torch.uint8)
+
+
+def _from_bytes(raw, dtype, shape):
+    import torch
+
+    if dtype.is_complex:
+        return torch.view_as_complex(raw.view(torch.empty(0, dtype=dtype).real.dtype).reshape(tuple(shape) + (2,)))
+    return raw.view(dtype).reshape(shape)
+
+
+def _pack_many(xs, block_size, planes, lib):
+    raws = [_as_bytes(x, f"tensor {i}") for i, x in enumerate(xs)]
+    ks = [default_planes(x.dtype) for x in xs] if planes is None else _planes_arg(planes, len(xs))
+    bss = [_lossless_block_size(r.numel(), block_size, k) for r, k in zip(raws, ks)]
+    dev = _same_device(raws, "pack")
+    frames = _compress_many(lib or load(), raws, bss, ks, dev, slack=True)
+    return [PackedTensor(f, x.dtype, x.shape, k, bs, r.numel()) for f, x, k, bs, r in zip(frames, xs, ks, bss, raws)]
+
+
+def _unpack_many(ps, outs, lib):
+    import torch
+
+    for p in ps:
+        if not isinstance(p, PackedTensor):
+            raise TypeError("unpack: a PackedTensor is expected")
+    if outs is None:
+        dev = _same_device([p.frame for p in ps], "unpack")
+        # every output at a multiple of 16 bytes, so that any dtype can view it
+        raws = _carve(0, [p.nbytes for p in ps], dev)
+        res = None
+    else:
+        res = outs
+        raws = []
+        for p, o in zip(ps, outs):
+            if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or o.shape != p.shape or not o.is_contiguous():
+                raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and shape")
+            raws.append(_as_bytes(o, "out"))
+    got = decompress_tensors([p.frame for p in ps], raws, lib=lib, planes=[p.planes for p in ps])
+    for p, g in zip(ps, got):
+        if g.numel() != p.nbytes:
+            raise ValueError(f"unpack: the frame decodes to {g.numel()} bytes, the tensor has {p.nbytes}")
+    return res if res is not None else [_from_bytes(r, p.dtype, p.shape) for r, p in zip(raws, ps)]
+
+
+def pack_tensor(x, block_size=16 << 20, planes=None, lib=None):
+    """Losslessly compresses a GPU tensor of any dtype and shape on its GPU: a PackedTensor whose `.frame` is an ordinary .bz3 frame.
+    Non-contiguous input is made contiguous; zero-element and 0-d tensors round-trip; a CPU tensor is a TypeError.  `planes`: the
+    byte-plane element size (1, 2, 4 or 8: bz3_hip_compress_device_planes), by default DEFAULT_PLANES for x's dtype.  The block size
+    handed to the library is _lossless_block_size(nbytes, block_size, planes), never one at which bz3_compress would drop the last
+    block (src/libbz3.c:914); it is recorded in the result.  The frame decodes anywhere: bz3_decompress gives S(x), the tensor's bytes
+    with every chunk split into planes; merge_k per chunk restores them.  Cost of the planes: the split and the merge
+    ride on the launches that move blocks into and out of their slots, so they add no pass.  The low mantissa planes of floats are
+    incompressible and such blocks can take the slower CM route, so time is the user's trade against size; measured on an MI355X on 256
+    fp32 tensors of 16 MiB of N(0, 0.02) (tools/planes_probe.py, profiles/planes_probe.json): pack_state_dict + unpack_state_dict at
+    planes=4 took 16.28 s + 30.75 s for frames of 0.8366 of the input, compress_tensors + decompress_tensors at planes=1 and the same
+    block size 16.48 s + 31.08 s for 0.8610.  The tensors unpack_tensor / unpack_state_dict return are views of one allocation per call."""
+    return _pack_many([x], block_size, None if planes is None else [planes], lib)[0]
+
+
+def unpack_tensor(p, out=None, lib=None):
+    """The tensor a PackedTensor holds, on the frame's GPU, in `out` if given (a contiguous tensor of p.dtype and p.shape).  Raises
+    Bz3Error if the frame does not decode and ValueError if it decodes to another number of bytes than p.nbytes."""
+    return _unpack_many([p], None if out is None else [out], lib)[0]
+
+
+def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None):
+    """pack_tensor for every tensor of a dict, batched: {name: PackedTensor}, each equal to pack_tensor(sd[name], block_size, planes).
+    One bz3_hip_compress_device_planes_many call per distinct lossless block size (the C call takes one block size): the tensors whose
+    size is no multiple of `block_size` share one call and its windows of up to 256 blocks; those whose block size had to move
+    (_lossless_block_size) go in one more call per moved size, typically one or two.  All tensors on one GPU.  `planes`: None
+    (DEFAULT_PLANES per dtype), an int, or {name: int}."""
+    names = list(sd)
+    if isinstance(planes, dict):
+        planes = [planes[k] for k in names]
+    if not names:
+        return {}
+    return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib)))
+
+
+def unpack_state_dict(packed, lib=None):
+    """The tensors of pack_state_dict's result, decoded in ONE batched call (bz3_hip_decompress_device_planes_many)."""
+    names = list(packed)
+    if not names:
+        return {}
+    return dict(zip(names, _unpack_many([packed[k] for k in names], None, lib)))
 
 
 def shard_blocks(n_blocks, world_size, rank):

@@ -26,6 +26,7 @@
 
 #include "../../include/bz3_hip.h"
 #include "frame.hpp"
+#include "planes.hpp"
 #include "prims.hpp"
 #include "sort.hpp"
 #include "stages.hpp"
@@ -2210,7 +2211,8 @@ BZIP3_API int bz3_orig_size_sufficient_for_decode(const uint8_t * block, size_t 
 // state per block on the buffers' device and one slab of slots; every move between the caller's buffers and the slots is
 // ONE launch of k_copy_segments (frame.hpp), frame and chunk headers travel as extra segments from a small staged buffer,
 // and on decode the chunk headers of all frames are walked on the device (k_frame_walk_many, one lane per frame) and read
-// back once per window.
+// back once per window.  The _planes entry points give every frame an element size: its blocks are split into byte planes on
+// the way into their slots and merged on the way out (planes.hpp), in the same launches; elem_sizes == nullptr is 1 everywhere.
 namespace {
 
 // The device that owns `p` if it is device memory, else -1.  (The emulator's device memory is host memory, on device 0.)
@@ -2236,18 +2238,20 @@ constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg)
 void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
     const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
     staging.assign(copy_table_bytes(n), 0);
-    memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
+    if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
     u32 * starts = (u32 *)(staging.data() + seg_bytes);
     u64 tiles = 0;
+    bool planes = false;  // a segment with an element size: k_move_segments (planes.hpp)
     for (size_t i = 0; i < n; i++) {
         starts[i] = (u32)tiles;
-        tiles += copy_tiles(segs[i].dst, segs[i].len);
+        tiles += segment_tiles(segs[i]);
+        planes |= (segs[i].mode & 0xff) > 1;
     }
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
     HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
-    launch(k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+    launch(planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
 }
 
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
@@ -2422,7 +2426,8 @@ void walk_frame_headers(DeviceFrames & f, s32 n, const u8 * const * ins, const s
 // Blocks go through windows in frame order, across frame boundaries: scatter (one copy launch), run_encode (one CM launch
 // for the window's blocks of all frames), pack (the frame headers of the frames that start in the window, the chunk headers
 // and the coded slots: one copy launch).  Every frame keeps its own output position and error.
-void compress_frames(int dev, u32 block_size_arg, s32 n, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
+void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes,
+                     int * rcs) {
     struct Frame {
         u32 bs = 0, nb = 0, next = 0;  // effective block size, blocks, next block to scatter
         size_t pos = 0, buf_max = 0;   // bytes written, capacity
@@ -2500,7 +2505,7 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u8 * const * ins,
                     slots[cnt] = f.slot(cnt);
                     f.states[cnt]->block_size = (s32)x.bs;  // every check of the block is made against its own frame's block size
                     f.states[cnt]->last_error = BZ3_OK;
-                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size});
+                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0});
                 }
             }
             if (cnt) {
@@ -2565,7 +2570,7 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u8 * const * ins,
 // window's size in all (one launch, one read-back), scatter, run_decode (one CM launch), gather.  Every frame keeps its
 // own resume point, committed size and error: a chunk that fails ends its frame alone, the chunks of the frame before it
 // are committed; a header error found by the walk ends the frame once the chunks before it are committed.
-void decompress_frames(int dev, s32 n, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
+void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
     struct Frame {
         size_t buf_max = 0, committed = 0;
         u32 decoded = 0;        // chunks decoded and committed (pos.done: chunks walked)
@@ -2690,7 +2695,7 @@ void decompress_frames(int dev, s32 n, const u8 * const * ins, const size_t * in
                         x.failed = true;
                         continue;
                     }
-                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig});
+                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] | PLANES_INVERSE : 0});
                     x.committed = c.rec.out_off + (size_t)c.rec.orig;
                     x.decoded++;
                 }
@@ -2811,27 +2816,43 @@ int first_error(s32 n, const int * rcs) {
     return BZ3_OK;
 }
 
+bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
+    for (s32 i = 0; i < n; i++)
+        if (!planes_elem_size_ok(elem_sizes[i])) return false;
+    return true;
+}
+
 }  // namespace
 
-BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+BZIP3_API int bz3_hip_compress_device_planes(uint32_t block_size, uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
     const int dev = device_of(out);
     if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
     const u8 * ins[1] = {(const u8 *)in};
     u8 * outs[1] = {(u8 *)out};
     int rc = BZ3_OK;
-    compress_frames(dev, block_size, 1, ins, &in_size, outs, out_size, &rc);
+    compress_frames(dev, block_size, 1, &elem_size, ins, &in_size, outs, out_size, &rc);
     return rc;
 }
 
-BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
+BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_compress_device_planes(block_size, 1, in, out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes(uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
     if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
     const int dev = device_of(in);
     if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
     const u8 * ins[1] = {(const u8 *)in};
     u8 * outs[1] = {(u8 *)out};
     int rc = BZ3_OK;
-    decompress_frames(dev, 1, ins, &in_size, outs, out_size, &rc);
+    decompress_frames(dev, 1, &elem_size, ins, &in_size, outs, out_size, &rc);
     return rc;
+}
+
+BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_decompress_device_planes(1, in, out, in_size, out_size);
 }
 
 BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size) {
@@ -2845,24 +2866,37 @@ BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size,
     return rc;
 }
 
-BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[],
-                                           size_t out_sizes[], int rcs[]) {
+// (elem_sizes == NULL: element size 1 for every frame, as bz3_hip.h says; the calls without _planes pass it.)
+BZIP3_API int bz3_hip_compress_device_planes_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                  void * const outs[], size_t out_sizes[], int rcs[]) {
     if (n == 0) return BZ3_OK;
     if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
     if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    compress_frames(dev, block_size, n, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    compress_frames(dev, block_size, n, elem_sizes, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                           size_t out_sizes[], int rcs[]) {
+    return bz3_hip_compress_device_planes_many(block_size, n, nullptr, ins, in_sizes, outs, out_sizes, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                                    size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
     return first_error(n, rcs);
 }
 
 BZIP3_API int bz3_hip_decompress_device_many(int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[], size_t out_sizes[],
                                              int rcs[]) {
-    if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    decompress_frames(dev, n, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
-    return first_error(n, rcs);
+    return bz3_hip_decompress_device_planes_many(n, nullptr, ins, in_sizes, outs, out_sizes, rcs);
 }
 
 BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const ins[], const size_t in_sizes[], size_t decoded_sizes[], int rcs[]) {
@@ -2874,8 +2908,12 @@ BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const i
     return first_error(n, rcs);
 }
 
-BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) {
+namespace {
+// n segments of `width` u64 each (src_off, dst_off, len[, elem_size | inverse << 8]) relative to src / dst, one launch.
+int32_t debug_move_segments(const void * src, void * dst, const uint64_t * segs, int32_t n, int width) {
     if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    for (s32 i = 0; width == 4 && i < n; i++)
+        if (!planes_elem_size_ok(segs[4 * i + 3] & 0xff) || (segs[4 * i + 3] >> 9)) return BZ3_ERR_INIT;
     const int dev = device_of(dst);
     if (dev < 0 || device_of(src) != dev) return BZ3_ERR_INIT;
     u8 * d_tab = nullptr;
@@ -2884,7 +2922,8 @@ BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, cons
     try {
         DeviceGuard g(dev);
         std::vector<CopySeg> v((size_t)n);
-        for (s32 i = 0; i < n; i++) v[(size_t)i] = {(u64)src + segs[3 * i], (u64)dst + segs[3 * i + 1], segs[3 * i + 2]};
+        for (s32 i = 0; i < n; i++)
+            v[(size_t)i] = {(u64)src + segs[width * i], (u64)dst + segs[width * i + 1], segs[width * i + 2], width == 4 ? segs[4 * i + 3] : 0};
         std::vector<u8> staging;
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         HIP_CHECK(hipMalloc((void **)&d_tab, copy_table_bytes((size_t)n)));
@@ -2898,6 +2937,11 @@ BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, cons
     if (s) (void)hipStreamDestroy(s);
     return rc;
 }
+}  // namespace
+
+BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, dst, segs, n, 3); }
+
+BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, dst, segs, n, 4); }
 
 // ---- bz3_hip.h: device control, timings ----------------------------------------------------------------
 BZIP3_API int bz3_hip_device_count(void) { return device_count(); }

@@ -32,8 +32,10 @@ __host__ __device__ inline int frame_chunk_check(const u8 * p, size_t in_left, u
 // ---- k_copy_segments -------------------------------------------------------------------------------------------------
 // One segment: `len` bytes from absolute device address `src` to `dst`.  Segments of one launch do not overlap on the
 // destination side (they may share a 16-byte granule: the bytes of a shared granule are written with byte stores).
+// `mode`: 0 or 1, a plain copy; an element size of 2, 4 or 8 (| PLANES_INVERSE), a byte-plane split (merge) of the segment
+// (planes.hpp: such a launch goes to k_move_segments).
 struct CopySeg {
-    u64 src, dst, len;
+    u64 src, dst, len, mode;
 };
 constexpr u32 COPY_THREADS = 256;
 constexpr u32 COPY_GRANULES_PER_LANE = 4;
@@ -102,17 +104,9 @@ __device__ __forceinline__ void copy_tile(const u8 * src, u8 * dst, u64 len, u64
 
 // Workgroup b copies tile b - tile_start[i] of segment i, where tile_start[i] <= b < tile_start[i + 1] (binary search over the
 // nseg + 1 prefix sums the host computed).
-__global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
-    const u32 b = blockIdx.x;
-    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const CopySeg sg = segs[lo];
+__device__ __forceinline__ void copy_segment_tile(const CopySeg & sg, u32 tile) {
     const u64 g0 = sg.dst >> 4, g_end = (sg.dst + sg.len + 15) >> 4;
-    const u64 g_first = g0 + (u64)(b - tile_start[lo]) * COPY_TILE_GRANULES;
+    const u64 g_first = g0 + (u64)tile * COPY_TILE_GRANULES;
     const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
     const u8 * src = (const u8 *)sg.src;
     u8 * dst = (u8 *)sg.dst;
@@ -122,6 +116,17 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
         case 2: copy_tile<2>(src, dst, sg.len, g_first, g_last); break;
         default: copy_tile<3>(src, dst, sg.len, g_first, g_last); break;
     }
+}
+
+__global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    copy_segment_tile(segs[lo], b - tile_start[lo]);
 }
 
 // ---- k_frame_walk_many -----------------------------------------------------------------------------------------------

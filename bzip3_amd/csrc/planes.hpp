@@ -1,0 +1,265 @@
+// planes.hpp -- byte-plane split / merge of a frame's blocks (bz3_hip_compress_device_planes / bz3_hip_decompress_device_planes, api.hip).
+//
+// For a block of s bytes of k-byte elements, m = s / k:
+//     split_k(b)[q m + e] = b[e k + q]   (0 <= q < k, 0 <= e < m),     split_k(b)[j] = b[j]   (m k <= j < s: the tail stays in place)
+// merge_k is its inverse.  The frame path copies every block into a slot and back anyway (frame.hpp k_copy_segments); a segment with
+// an element size is split (compress, scatter side) or merged (decompress, gather side) during that copy instead.  Both sides of
+// both directions may sit at any alignment: the interleaved side is the caller's buffer (in + j block_size, out + planned), and
+// plane q starts at slot + q m, which is 16-byte aligned only where m is.
+//
+// One workgroup moves a tile of PLANES_TILE_ELEMS elements in two phases:
+//   1. a lane takes 16 elements into registers with 16-byte loads (k contiguous granules of the interleaved side, or one granule of
+//      each plane; a side that is not 16-byte aligned is built from the aligned granules around it with v_alignbyte_b32, as copy_tile
+//      does), transposes bytes with v_perm_b32 and writes k aligned 16-byte rows to LDS, laid out as the destination wants them;
+//   2. a lane takes destination granules (16-byte aligned in global memory), reads their 16 bytes from LDS at whatever byte offset
+//      that is (five dword reads, v_alignbyte_b32) and writes them with one 16-byte store.
+// 255 of the 256 lanes' elements make a tile: the destination granule that straddles the end of a tile belongs to the tile it
+// starts in, which therefore holds up to 15 elements of the next one (the 256th lane's).  Byte stores are left for the partial
+// granules at the two ends of a plane (split) or of the block (merge) and for the tail.  As in copy_tile, no granule is loaded that
+// holds no byte of the segment, and no byte outside the segment's destination is written.
+#pragma once
+#include "frame.hpp"
+
+namespace bz3 {
+
+constexpr u32 PLANES_TILE_ELEMS = (COPY_THREADS - 1) * 16;  // elements whose destination granules a workgroup owns
+constexpr u32 PLANES_LOAD_ELEMS = COPY_THREADS * 16;        // elements a workgroup loads (the last 16 for the straddling granules)
+constexpr u32 PLANE_STRIDE = PLANES_LOAD_ELEMS + 16;        // LDS bytes per plane (split): phase 2 reads up to 20 bytes from offset < 4080
+constexpr u32 PLANES_LDS_BYTES = 8 * PLANE_STRIDE;          // >= 8 * PLANES_LOAD_ELEMS + 16, the merge layout
+constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = elem_size | PLANES_INVERSE for merge
+
+__host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
+// Workgroups of a split / merge segment: one per PLANES_TILE_ELEMS elements; a block shorter than an element still has its tail.
+__host__ __device__ inline u64 planes_tiles(u64 len, u64 k) {
+    const u64 t = (len / k + PLANES_TILE_ELEMS - 1) / PLANES_TILE_ELEMS;
+    return len ? (t ? t : 1) : 0;
+}
+__host__ __device__ inline u64 segment_tiles(const CopySeg & sg) {
+    return (sg.mode & 0xff) > 1 ? planes_tiles(sg.len, sg.mode & 0xff) : copy_tiles(sg.dst, sg.len);
+}
+
+__device__ __forceinline__ u32 byte_perm(u32 hi, u32 lo, u32 sel) {  // byte i of the result = byte sel[i] (0..7) of hi:lo, v_perm_b32
+#ifdef BZ3_EMU
+    const u64 v = ((u64)hi << 32) | lo;
+    u32 o = 0;
+    for (u32 i = 0; i < 4; i++) o |= (u32)((v >> (8 * ((sel >> (8 * i)) & 7))) & 0xff) << (8 * i);
+    return o;
+#else
+    return __builtin_amdgcn_perm(hi, lo, sel);
+#endif
+}
+
+// Bytes [sh, sh + 16) of lo:hi, 0 <= sh < 16 (sh is uniform over a wave: the word selection is two rounds of conditional moves).
+__device__ __forceinline__ uint4 shift_bytes(uint4 lo, uint4 hi, u32 sh) {
+    u32 w0 = lo.x, w1 = lo.y, w2 = lo.z, w3 = lo.w, w4 = hi.x, w5 = hi.y, w6 = hi.z, w7 = hi.w;
+    if (sh & 4) { w0 = w1; w1 = w2; w2 = w3; w3 = w4; w4 = w5; w5 = w6; w6 = w7; }
+    if (sh & 8) { w0 = w2; w1 = w3; w2 = w4; w3 = w5; w4 = w6; }
+    uint4 o;
+    o.x = align_byte(w1, w0, sh & 3);
+    o.y = align_byte(w2, w1, sh & 3);
+    o.z = align_byte(w3, w2, sh & 3);
+    o.w = align_byte(w4, w3, sh & 3);
+    return o;
+}
+
+// 16 bytes from any address: the one or two aligned granules that hold them.
+__device__ __forceinline__ uint4 load16_any(u64 addr) {
+    const uint4 * g = (const uint4 *)(addr & ~(u64)15);
+    const u32 sh = (u32)(addr & 15);
+    return sh ? shift_bytes(g[0], g[1], sh) : g[0];
+}
+
+// 16 bytes of LDS from any byte offset: five aligned dwords.
+__device__ __forceinline__ uint4 lds16_any(const u8 * lds, u32 x) {
+    const u32 * w = (const u32 *)(lds + (x & ~3u));
+    uint4 o;
+    o.x = align_byte(w[1], w[0], x & 3);
+    o.y = align_byte(w[2], w[1], x & 3);
+    o.z = align_byte(w[3], w[2], x & 3);
+    o.w = align_byte(w[4], w[3], x & 3);
+    return o;
+}
+
+// 4 x 4 byte transpose: byte c of r[j] -> byte j of r[c].  Its own inverse.
+__device__ __forceinline__ void transpose4(u32 & r0, u32 & r1, u32 & r2, u32 & r3) {
+    const u32 a = byte_perm(r1, r0, 0x05010400), b = byte_perm(r1, r0, 0x07030602);  // [r0.0 r1.0 r0.1 r1.1], [r0.2 r1.2 r0.3 r1.3]
+    const u32 c = byte_perm(r3, r2, 0x05010400), d = byte_perm(r3, r2, 0x07030602);
+    r0 = byte_perm(c, a, 0x05040100);
+    r1 = byte_perm(c, a, 0x07060302);
+    r2 = byte_perm(d, b, 0x05040100);
+    r3 = byte_perm(d, b, 0x07060302);
+}
+
+// w: 16 elements of K bytes, interleaved (4 K words); p[q]: byte q of the 16 elements (4 words).
+template <int K>
+__device__ __forceinline__ void deinterleave(const u32 (&w)[4 * K], u32 (&p)[K][4]) {
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        if (K == 2) {
+            p[0][n] = byte_perm(w[2 * n + 1], w[2 * n], 0x06040200);
+            p[1][n] = byte_perm(w[2 * n + 1], w[2 * n], 0x07050301);
+        } else {  // words h, h + K/4, h + 2 K/4, h + 3 K/4 of four consecutive elements hold their bytes 4 h .. 4 h + 3
+#pragma unroll
+            for (int h = 0; h < K / 4; h++) {
+                u32 r0 = w[K * n + h], r1 = w[K * n + K / 4 + h], r2 = w[K * n + 2 * (K / 4) + h], r3 = w[K * n + 3 * (K / 4) + h];
+                transpose4(r0, r1, r2, r3);
+                p[(4 * h + 0) % K][n] = r0;
+                p[(4 * h + 1) % K][n] = r1;
+                p[(4 * h + 2) % K][n] = r2;
+                p[(4 * h + 3) % K][n] = r3;
+            }
+        }
+    }
+}
+
+template <int K>
+__device__ __forceinline__ void interleave(const u32 (&p)[K][4], u32 (&w)[4 * K]) {
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        if (K == 2) {
+            w[2 * n] = byte_perm(p[1][n], p[0][n], 0x05010400);
+            w[2 * n + 1] = byte_perm(p[1][n], p[0][n], 0x07030602);
+        } else {
+#pragma unroll
+            for (int h = 0; h < K / 4; h++) {
+                u32 r0 = p[(4 * h + 0) % K][n], r1 = p[(4 * h + 1) % K][n], r2 = p[(4 * h + 2) % K][n], r3 = p[(4 * h + 3) % K][n];
+                transpose4(r0, r1, r2, r3);
+                w[K * n + h] = r0;
+                w[K * n + K / 4 + h] = r1;
+                w[K * n + 2 * (K / 4) + h] = r2;
+                w[K * n + 3 * (K / 4) + h] = r3;
+            }
+        }
+    }
+}
+
+// Phase 2 of both directions: the bytes [s0, s1) of global memory from LDS, where the byte at address `origin` is lds[0].  Granule
+// i of the lane is (s0 & ~15) + 16 (lane + 256 i); granules inside [s0, s1) get one 16-byte store, the partial ones byte stores.
+template <int ROUNDS>
+__device__ __forceinline__ void store_from_lds(const u8 * lds, u64 origin, u64 s0, u64 s1) {
+#pragma unroll
+    for (int i = 0; i < ROUNDS; i++) {
+        const u64 a = (s0 & ~(u64)15) + 16 * (u64)(threadIdx.x + COPY_THREADS * i);
+        if (a >= s1) break;
+        if (a >= s0 && a + 16 <= s1) {
+            *(uint4 *)a = lds16_any(lds, (u32)(a - origin));
+        } else {
+            const u64 b0 = a > s0 ? a : s0, b1 = a + 16 < s1 ? a + 16 : s1;
+            for (u64 b = b0; b < b1; b++) *(u8 *)b = lds[b - origin];
+        }
+    }
+}
+
+__device__ __forceinline__ u64 align16_up_to(u64 a, u64 end) {
+    a = (a + 15) & ~(u64)15;
+    return a < end ? a : end;
+}
+
+// Tile `tile` of a split: elements [ea, ea + PLANES_TILE_ELEMS) of the block at `src` into the planes at `dst`.
+template <int K>
+__device__ __forceinline__ void split_tile(const u8 * src, u8 * dst, u64 len, u64 tile, u8 * lds) {
+    const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
+    const u64 e = ea + 16 * (u64)threadIdx.x;
+    if (e + 16 <= m) {
+        const u64 addr = (u64)src + e * K;
+        const uint4 * g = (const uint4 *)(addr & ~(u64)15);
+        const u32 sh = (u32)(addr & 15);
+        uint4 v[K + 1];
+#pragma unroll
+        for (int i = 0; i < K; i++) v[i] = g[i];
+        if (sh) {
+            v[K] = g[K];  // holds the lane's last sh bytes
+#pragma unroll
+            for (int i = 0; i < K; i++) v[i] = shift_bytes(v[i], v[i + 1], sh);
+        }
+        u32 w[4 * K], p[K][4];
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            w[4 * i] = v[i].x;
+            w[4 * i + 1] = v[i].y;
+            w[4 * i + 2] = v[i].z;
+            w[4 * i + 3] = v[i].w;
+        }
+        deinterleave<K>(w, p);
+#pragma unroll
+        for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
+    } else {
+        for (u64 i = e; i < m; i++)
+            for (int q = 0; q < K; q++) lds[q * PLANE_STRIDE + (i - ea)] = src[i * K + q];
+    }
+    __syncthreads();
+    const bool last = ea + PLANES_TILE_ELEMS >= m;
+#pragma unroll
+    for (int q = 0; q < K; q++) {
+        const u64 p0 = (u64)dst + q * m, pend = p0 + m;
+        const u64 s0 = tile == 0 ? p0 : align16_up_to(p0 + ea, pend);
+        const u64 s1 = last ? pend : align16_up_to(p0 + ea + PLANES_TILE_ELEMS, pend);
+        store_from_lds<1>(lds + q * PLANE_STRIDE, p0 + ea, s0, s1);
+    }
+    if (tile == 0 && threadIdx.x < len - m * K) dst[m * K + threadIdx.x] = src[m * K + threadIdx.x];
+}
+
+// Tile `tile` of a merge: elements [ea, ea + PLANES_TILE_ELEMS) of the planes at `src` into the block at `dst`.
+template <int K>
+__device__ __forceinline__ void merge_tile(const u8 * src, u8 * dst, u64 len, u64 tile, u8 * lds) {
+    const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
+    const u64 e = ea + 16 * (u64)threadIdx.x;
+    if (e + 16 <= m) {
+        u32 w[4 * K], p[K][4];
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            const uint4 v = load16_any((u64)src + q * m + e);
+            p[q][0] = v.x;
+            p[q][1] = v.y;
+            p[q][2] = v.z;
+            p[q][3] = v.w;
+        }
+        interleave<K>(p, w);
+#pragma unroll
+        for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    } else {
+        for (u64 i = e; i < m; i++)
+            for (int q = 0; q < K; q++) lds[(i - ea) * K + q] = src[q * m + i];
+    }
+    __syncthreads();
+    const bool last = ea + PLANES_TILE_ELEMS >= m;
+    const u64 d0 = (u64)dst, dend = d0 + m * K;
+    const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ea * K, dend);
+    const u64 s1 = last ? dend : align16_up_to(d0 + (ea + PLANES_TILE_ELEMS) * K, dend);
+    store_from_lds<K>(lds, d0 + ea * K, s0, s1);  // at most 255 K + 1 granules
+    if (tile == 0 && threadIdx.x < len - m * K) dst[m * K + threadIdx.x] = src[m * K + threadIdx.x];
+}
+
+// One tile of a segment with an element size (CopySeg::mode).
+__device__ __forceinline__ void planes_tile(const CopySeg & sg, u64 tile, u8 * lds) {
+    const u8 * src = (const u8 *)sg.src;
+    u8 * dst = (u8 *)sg.dst;
+    switch ((u32)sg.mode) {
+        case 2: split_tile<2>(src, dst, sg.len, tile, lds); break;
+        case 4: split_tile<4>(src, dst, sg.len, tile, lds); break;
+        case 8: split_tile<8>(src, dst, sg.len, tile, lds); break;
+        case 2 | PLANES_INVERSE: merge_tile<2>(src, dst, sg.len, tile, lds); break;
+        case 4 | PLANES_INVERSE: merge_tile<4>(src, dst, sg.len, tile, lds); break;
+        case 8 | PLANES_INVERSE: merge_tile<8>(src, dst, sg.len, tile, lds); break;
+        default: break;
+    }
+}
+
+// k_copy_segments for a launch in which some segment has an element size: segments without one take copy_tile as before, the
+// others split_tile / merge_tile.  tile_start counts a segment's workgroups with segment_tiles.  (A kernel of its own so that launches
+// of plain copies keep k_copy_segments, which holds no LDS.)
+__global__ void __launch_bounds__(COPY_THREADS) k_move_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    if ((sg.mode & 0xff) > 1) planes_tile(sg, b - tile_start[lo], (u8 *)lds);
+    else copy_segment_tile(sg, b - tile_start[lo]);
+}
+
+}  // namespace bz3

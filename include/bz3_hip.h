@@ -147,6 +147,29 @@ BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const i
  * triples (host array of 3 n u64) relative to `src` / `dst`, non-overlapping on the destination side.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n);
 
+/* Byte-plane frames: the device frame calls above for typed data.  For a block of s bytes of elem_size-byte elements (k = elem_size,
+ * m = s / k), split_k(b)[q m + e] = b[e k + q] for 0 <= q < k, 0 <= e < m, and split_k(b)[j] = b[j] for m k <= j < s (the tail of
+ * s % k bytes stays in place); merge_k is its inverse, k = 1 the identity.  S(x) applies split_k to every block bz3_compress cuts x
+ * into (src/libbz3.c:877-914: block j is x[j bs, (j + 1) bs), the last one in_size % bs bytes), never across blocks.  The compress
+ * calls write exactly bz3_compress(block_size, S(x)): an ordinary .bz3 frame, which any bzip3 decodes to S(x).  The decompress
+ * calls decode a frame and apply merge_k to every chunk, of the original size its chunk header gives (not the header's block size).
+ * The element size is not stored in the frame: pass the one the frame was made with.  Everything else is the contract of the calls
+ * without _planes, with S(x) in the place of x: return codes, *out_size, the bytes committed before an error (whole merged chunks),
+ * the pointer checks, the independence of the frames of a _many call, windows, the headroom rule.  elem_size must be 1, 2, 4 or 8,
+ * else BZ3_ERR_INIT for the whole call before any write (_many: in every rcs[i], every out_sizes[i] = 0); 1 gives the bytes of the
+ * calls without _planes; a NULL elem_sizes in the _many calls is 1 for every frame.  The split and the merge happen in the launches that move a window's blocks into and out of their slots
+ * (planes.hpp), so no pass over the data and no buffer of the size of the input is added. */
+BZIP3_API int bz3_hip_compress_device_planes(uint32_t block_size, uint32_t elem_size, const void * in, void * out, size_t in_size,
+                                             size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device_planes(uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size);
+BZIP3_API int bz3_hip_compress_device_planes_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[],
+                                                  const size_t in_sizes[], void * const outs[], size_t out_sizes[], int rcs[]);
+BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[],
+                                                    const size_t in_sizes[], void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: bz3_hip_debug_copy_segments with n (src_off, dst_off, len, elem_size | inverse << 8) quadruples (host array of 4 n u64):
+ * a segment is copied (elem_size 1), split (inverse 0) or merged (inverse 1) in one launch.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
