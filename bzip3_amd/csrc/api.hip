@@ -2213,6 +2213,8 @@ BZIP3_API int bz3_orig_size_sufficient_for_decode(const uint8_t * block, size_t 
 // and on decode the chunk headers of all frames are walked on the device (k_frame_walk_many, one lane per frame) and read
 // back once per window.  The _planes entry points give every frame an element size: its blocks are split into byte planes on
 // the way into their slots and merged on the way out (planes.hpp), in the same launches; elem_sizes == nullptr is 1 everywhere.
+// The _delta entry points give a frame a base of the size of its input as well: a block's segment carries the address of the base bytes
+// that pair with it, which the same launch subtracts before the split and adds after the merge; bases == nullptr is no base anywhere.
 namespace {
 
 // The device that owns `p` if it is device memory, else -1.  (The emulator's device memory is host memory, on device 0.)
@@ -2241,17 +2243,18 @@ void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging,
     if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
     u32 * starts = (u32 *)(staging.data() + seg_bytes);
     u64 tiles = 0;
-    bool planes = false;  // a segment with an element size: k_move_segments (planes.hpp)
+    bool planes = false, delta = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
     for (size_t i = 0; i < n; i++) {
         starts[i] = (u32)tiles;
         tiles += segment_tiles(segs[i]);
         planes |= (segs[i].mode & 0xff) > 1;
+        delta |= segs[i].base != 0;
     }
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
     HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
-    launch(planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+    launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
 }
 
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
@@ -2426,8 +2429,9 @@ void walk_frame_headers(DeviceFrames & f, s32 n, const u8 * const * ins, const s
 // Blocks go through windows in frame order, across frame boundaries: scatter (one copy launch), run_encode (one CM launch
 // for the window's blocks of all frames), pack (the frame headers of the frames that start in the window, the chunk headers
 // and the coded slots: one copy launch).  Every frame keeps its own output position and error.
-void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes,
-                     int * rcs) {
+// bases (or nullptr): per frame nullptr, or in_sizes[i] bytes the frame is coded against; block j pairs with base bytes [j bs, j bs + len_j).
+void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes, const u8 * const * ins, const u8 * const * bases, const size_t * in_sizes,
+                     u8 * const * outs, size_t * out_sizes, int * rcs) {
     struct Frame {
         u32 bs = 0, nb = 0, next = 0;  // effective block size, blocks, next block to scatter
         size_t pos = 0, buf_max = 0;   // bytes written, capacity
@@ -2505,7 +2509,8 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
                     slots[cnt] = f.slot(cnt);
                     f.states[cnt]->block_size = (s32)x.bs;  // every check of the block is made against its own frame's block size
                     f.states[cnt]->last_error = BZ3_OK;
-                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0});
+                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0,
+                                      bases && bases[i] ? (u64)(bases[i] + (size_t)x.next * x.bs) : 0});
                 }
             }
             if (cnt) {
@@ -2570,7 +2575,11 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
 // window's size in all (one launch, one read-back), scatter, run_decode (one CM launch), gather.  Every frame keeps its
 // own resume point, committed size and error: a chunk that fails ends its frame alone, the chunks of the frame before it
 // are committed; a header error found by the walk ends the frame once the chunks before it are committed.
-void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, u8 * const * outs, size_t * out_sizes, int * rcs) {
+// bases (or nullptr): per frame nullptr, or base_sizes[i] bytes that are added to the decoded bytes at the same offsets; such a frame's capacity
+// is the smaller of out_sizes[i] and base_sizes[i], so that the walk refuses a chunk that runs past the base as one that runs past `out`.
+// outs[i] may be bases[i] (planes.hpp, "In place").
+void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
+                       u8 * const * outs, size_t * out_sizes, int * rcs) {
     struct Frame {
         size_t buf_max = 0, committed = 0;
         u32 decoded = 0;        // chunks decoded and committed (pos.done: chunks walked)
@@ -2589,7 +2598,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         rcs[i] = BZ3_OK;
         if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
         else live[i] = any = 1;
-        fr[i].buf_max = out_sizes[i];
+        fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
     }
     if (!any) return;
     DeviceFrames f;
@@ -2695,7 +2704,8 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                         x.failed = true;
                         continue;
                     }
-                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] | PLANES_INVERSE : 0});
+                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
+                                      bases && bases[c.frame] ? (u64)(bases[c.frame] + c.rec.out_off) : 0});
                     x.committed = c.rec.out_off + (size_t)c.rec.orig;
                     x.decoded++;
                 }
@@ -2816,6 +2826,12 @@ int first_error(s32 n, const int * rcs) {
     return BZ3_OK;
 }
 
+// Do [a, a + a_size) and [b, b + b_size) share a byte?
+bool ranges_overlap(const void * a, size_t a_size, const void * b, size_t b_size) {
+    const u64 x = (u64)a, y = (u64)b;
+    return a_size && b_size && x < y + b_size && y < x + a_size;
+}
+
 bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
     for (s32 i = 0; i < n; i++)
         if (!planes_elem_size_ok(elem_sizes[i])) return false;
@@ -2824,31 +2840,45 @@ bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
 
 }  // namespace
 
-BZIP3_API int bz3_hip_compress_device_planes(uint32_t block_size, uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+BZIP3_API int bz3_hip_compress_device_delta(uint32_t block_size, uint32_t elem_size, const void * in, const void * base, void * out, size_t in_size,
+                                            size_t * out_size) {
     if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
     const int dev = device_of(out);
     if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
+    if (base && in_size && (device_of(base) != dev || ranges_overlap(out, *out_size, base, in_size) || ranges_overlap(out, *out_size, in, in_size))) return BZ3_ERR_INIT;
     const u8 * ins[1] = {(const u8 *)in};
+    const u8 * bases[1] = {(const u8 *)base};
     u8 * outs[1] = {(u8 *)out};
     int rc = BZ3_OK;
-    compress_frames(dev, block_size, 1, &elem_size, ins, &in_size, outs, out_size, &rc);
+    compress_frames(dev, block_size, 1, &elem_size, ins, bases, &in_size, outs, out_size, &rc);
     return rc;
+}
+
+BZIP3_API int bz3_hip_compress_device_planes(uint32_t block_size, uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_compress_device_delta(block_size, elem_size, in, nullptr, out, in_size, out_size);
 }
 
 BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
     return bz3_hip_compress_device_planes(block_size, 1, in, out, in_size, out_size);
 }
 
-BZIP3_API int bz3_hip_decompress_device_planes(uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+BZIP3_API int bz3_hip_decompress_device_delta(uint32_t elem_size, const void * in, const void * base, size_t base_size, void * out, size_t in_size,
+                                              size_t * out_size) {
     if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
     if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
     const int dev = device_of(in);
     if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
+    if (base && base_size && (device_of(base) != dev || (base != out && ranges_overlap(out, *out_size, base, base_size)))) return BZ3_ERR_INIT;
     const u8 * ins[1] = {(const u8 *)in};
+    const u8 * bases[1] = {(const u8 *)base};
     u8 * outs[1] = {(u8 *)out};
     int rc = BZ3_OK;
-    decompress_frames(dev, 1, &elem_size, ins, &in_size, outs, out_size, &rc);
+    decompress_frames(dev, 1, &elem_size, ins, &in_size, bases, &base_size, outs, out_size, &rc);
     return rc;
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes(uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_decompress_device_delta(elem_size, in, nullptr, 0, out, in_size, out_size);
 }
 
 BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
@@ -2866,16 +2896,26 @@ BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size,
     return rc;
 }
 
-// (elem_sizes == NULL: element size 1 for every frame, as bz3_hip.h says; the calls without _planes pass it.)
-BZIP3_API int bz3_hip_compress_device_planes_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
-                                                  void * const outs[], size_t out_sizes[], int rcs[]) {
+// (elem_sizes == NULL: element size 1 for every frame, as bz3_hip.h says; bases == NULL: no frame has a base.  The calls without _delta pass them.)
+BZIP3_API int bz3_hip_compress_device_delta_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const void * const bases[],
+                                                 const size_t in_sizes[], void * const outs[], size_t out_sizes[], int rcs[]) {
     if (n == 0) return BZ3_OK;
     if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
     if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    compress_frames(dev, block_size, n, elem_sizes, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: in_sizes[i] bytes of the same GPU that the frame's output overlaps neither with it nor with the input
+        if (!bases[i] || !in_sizes[i]) continue;
+        if (device_of(bases[i]) != dev || ranges_overlap(outs[i], out_sizes[i], bases[i], in_sizes[i]) || ranges_overlap(outs[i], out_sizes[i], ins[i], in_sizes[i]))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    compress_frames(dev, block_size, n, elem_sizes, (const u8 * const *)ins, (const u8 * const *)bases, in_sizes, (u8 * const *)outs, out_sizes, rcs);
     return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_compress_device_planes_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                  void * const outs[], size_t out_sizes[], int rcs[]) {
+    return bz3_hip_compress_device_delta_many(block_size, n, elem_sizes, ins, nullptr, in_sizes, outs, out_sizes, rcs);
 }
 
 BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[],
@@ -2883,15 +2923,25 @@ BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const
     return bz3_hip_compress_device_planes_many(block_size, n, nullptr, ins, in_sizes, outs, out_sizes, rcs);
 }
 
-BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
-                                                    size_t out_sizes[], int rcs[]) {
+BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                   const void * const bases[], const size_t base_sizes[], void * const outs[], size_t out_sizes[], int rcs[]) {
     if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
     if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        if (device_of(bases[i]) != dev || (bases[i] != outs[i] && ranges_overlap(outs[i], out_sizes[i], bases[i], base_sizes[i])))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs);
     return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                                    size_t out_sizes[], int rcs[]) {
+    return bz3_hip_decompress_device_delta_many(n, elem_sizes, ins, in_sizes, nullptr, nullptr, outs, out_sizes, rcs);
 }
 
 BZIP3_API int bz3_hip_decompress_device_many(int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[], size_t out_sizes[],
@@ -2909,21 +2959,27 @@ BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const i
 }
 
 namespace {
-// n segments of `width` u64 each (src_off, dst_off, len[, elem_size | inverse << 8]) relative to src / dst, one launch.
-int32_t debug_move_segments(const void * src, void * dst, const uint64_t * segs, int32_t n, int width) {
+// n segments of `width` u64 each relative to src / base / dst, one launch: (src_off, dst_off, len[, elem_size | inverse << 8]), or with
+// width 5 (src_off, base_off, dst_off, len, elem_size | inverse << 8), base_off = UINT64_MAX for a segment without a base.
+int32_t debug_move_segments(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, int width) {
     if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
-    for (s32 i = 0; width == 4 && i < n; i++)
-        if (!planes_elem_size_ok(segs[4 * i + 3] & 0xff) || (segs[4 * i + 3] >> 9)) return BZ3_ERR_INIT;
+    for (s32 i = 0; width >= 4 && i < n; i++) {
+        const u64 mode = segs[width * i + width - 1];
+        if (!planes_elem_size_ok(mode & 0xff) || (mode >> 9)) return BZ3_ERR_INIT;
+    }
     const int dev = device_of(dst);
-    if (dev < 0 || device_of(src) != dev) return BZ3_ERR_INIT;
+    if (dev < 0 || device_of(src) != dev || (width == 5 && device_of(base) != dev)) return BZ3_ERR_INIT;
     u8 * d_tab = nullptr;
     hipStream_t s = nullptr;
     int rc = BZ3_OK;
     try {
         DeviceGuard g(dev);
         std::vector<CopySeg> v((size_t)n);
-        for (s32 i = 0; i < n; i++)
-            v[(size_t)i] = {(u64)src + segs[width * i], (u64)dst + segs[width * i + 1], segs[width * i + 2], width == 4 ? segs[4 * i + 3] : 0};
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)width * i;
+            if (width == 5) v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[2], q[3], q[4], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]};
+            else v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[1], q[2], width == 4 ? q[3] : 0, 0};
+        }
         std::vector<u8> staging;
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         HIP_CHECK(hipMalloc((void **)&d_tab, copy_table_bytes((size_t)n)));
@@ -2939,9 +2995,62 @@ int32_t debug_move_segments(const void * src, void * dst, const uint64_t * segs,
 }
 }  // namespace
 
-BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, dst, segs, n, 3); }
+BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 3); }
 
-BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, dst, segs, n, 4); }
+BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 4); }
+
+BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    return debug_move_segments(src, base, dst, segs, n, 5);
+}
+
+// The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state `init`, no inversion) over n bytes of device memory: crc32c_device on a
+// caller's buffer.  Its kernels read dwords, so the up to three bytes before the first 4-byte boundary are fetched and folded in on the host.
+BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc) {
+    if (!crc) return BZ3_ERR_INIT;
+    if (!n) {
+        *crc = init;
+        return BZ3_OK;
+    }
+    const int dev = device_of(p);
+    DeviceCtx * ctx = nullptr;
+    try {
+        ctx = dev < 0 ? nullptr : get_ctx(dev);
+    } catch (...) {
+        ctx = nullptr;
+    }
+    if (!ctx) return BZ3_ERR_INIT;
+    hipStream_t s = nullptr;
+    u32 * d_words = nullptr;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_CHECK(hipMalloc((void **)&d_words, 64));
+        const u8 * d = (const u8 *)p;
+        const size_t head = std::min(n, (size_t)((0 - (u64)d) & 3));
+        u32 reg = init;
+        if (head) {
+            u8 h[4] = {0};
+            HIP_CHECK(hipMemcpyAsync(h, d, head, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < head; i++) {
+                reg ^= h[i];
+                for (int k = 0; k < 8; k++) reg = (reg >> 1) ^ (0x82F63B78u & (0u - (reg & 1u)));
+            }
+        }
+        if (n > head) {
+            crc32c_device(d + head, (u64)(n - head), reg, ctx->d_crc, d_words, s);
+            reg = read_word(s, d_words + 1);
+        }
+        *crc = reg;
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    if (s) (void)hipStreamSynchronize(s);
+    if (d_words) (void)hipFree(d_words);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
+}
 
 // ---- bz3_hip.h: device control, timings ----------------------------------------------------------------
 BZIP3_API int bz3_hip_device_count(void) { return device_count(); }

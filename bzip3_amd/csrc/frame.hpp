@@ -33,9 +33,11 @@ __host__ __device__ inline int frame_chunk_check(const u8 * p, size_t in_left, u
 // One segment: `len` bytes from absolute device address `src` to `dst`.  Segments of one launch do not overlap on the
 // destination side (they may share a 16-byte granule: the bytes of a shared granule are written with byte stores).
 // `mode`: 0 or 1, a plain copy; an element size of 2, 4 or 8 (| PLANES_INVERSE), a byte-plane split (merge) of the segment
-// (planes.hpp: such a launch goes to k_move_segments).
+// (planes.hpp: such a launch goes to k_move_segments).  `base`: 0, or the address of `len` bytes on the caller's side of the move that
+// are subtracted from the source bytes before a split (mode without PLANES_INVERSE) or added after a merge (with it), byte by byte
+// mod 256 (planes.hpp: a launch with such a segment goes to k_delta_segments).
 struct CopySeg {
-    u64 src, dst, len, mode;
+    u64 src, dst, len, mode, base;
 };
 constexpr u32 COPY_THREADS = 256;
 constexpr u32 COPY_GRANULES_PER_LANE = 4;

@@ -17,6 +17,27 @@
 // starts in, which therefore holds up to 15 elements of the next one (the 256th lane's).  Byte stores are left for the partial
 // granules at the two ends of a plane (split) or of the block (merge) and for the tail.  As in copy_tile, no granule is loaded that
 // holds no byte of the segment, and no byte outside the segment's destination is written.
+//
+// Delta segments (CopySeg::base != 0; bz3_hip_*_device_delta, api.hip).  D(x, b)[i] = (x[i] - b[i]) mod 256 for every byte.  A split
+// segment with a base stores split_k(src - base), a merge segment merge_k(src) + base; the base lies on the interleaved (caller's)
+// side, at the offsets of that side, with an alignment of its own.  The difference is taken in phase 1, on the registers that hold
+// the interleaved bytes (before the transpose of a split, after the one of a merge), four bytes per operation (sub_bytes /
+// add_bytes: gfx950 has no packed byte subtract); the base's granules are loaded as the interleaved side's are.  k = 1 needs no
+// LDS: delta1_tile is copy_tile with a second read stream.
+//
+// In place.  A merge may write its output over the base (dst == base, the decode call's `out == base`) because every base byte a
+// workgroup needs is read by that workgroup before anyone writes it:
+//   * the bytes a tile stores, [s0, s1), are disjoint from every other tile's and every other segment's, so only the tile itself
+//     ever writes them;
+//   * they lie within the 256 lanes' elements [ea, ea + PLANES_LOAD_ELEMS) (s1 <= d0 + (ea + PLANES_TILE_ELEMS) k + 15), so all of
+//     them are read from the base in phase 1, before the tile's barrier, and stored in phase 2, after it;
+//   * what else phase 1 reads of the base -- the rest of the 256th lane's elements, the bytes of the straddling granule below s0,
+//     the neighbours inside an aligned granule -- belongs to other tiles, which may have overwritten it already: those sums land in
+//     LDS outside [s0 - origin, s1 - origin) and phase 2 never reads them;
+//   * a tail byte is read and written by one thread, in that order, and used by no other;
+//   * delta1_tile reads the base at the destination's own granules (dst == base: the same alignment), each by the thread that then
+//     stores it.
+// Any other overlap of base and destination is the caller's error (api.hip refuses it).
 #pragma once
 #include "frame.hpp"
 
@@ -67,6 +88,38 @@ __device__ __forceinline__ uint4 load16_any(u64 addr) {
     const uint4 * g = (const uint4 *)(addr & ~(u64)15);
     const u32 sh = (u32)(addr & 15);
     return sh ? shift_bytes(g[0], g[1], sh) : g[0];
+}
+
+// Byte-wise difference / sum of two dwords.  The low seven bits of every byte are subtracted (added) with the top bits set (cleared)
+// so that no borrow (carry) leaves a byte; the top bit of every byte is x ^ y ^ borrow (carry), an exclusive or.
+__host__ __device__ inline u32 sub_bytes(u32 x, u32 y) { return ((x | 0x80808080u) - (y & 0x7f7f7f7fu)) ^ ((x ^ ~y) & 0x80808080u); }
+__host__ __device__ inline u32 add_bytes(u32 x, u32 y) { return ((x & 0x7f7f7f7fu) + (y & 0x7f7f7f7fu)) ^ ((x ^ y) & 0x80808080u); }
+template <bool INV>
+__device__ __forceinline__ uint4 delta16(uint4 x, uint4 b) {  // x + b (INV) or x - b, 16 bytes
+    return INV ? make_uint4(add_bytes(x.x, b.x), add_bytes(x.y, b.y), add_bytes(x.z, b.z), add_bytes(x.w, b.w))
+               : make_uint4(sub_bytes(x.x, b.x), sub_bytes(x.y, b.y), sub_bytes(x.z, b.z), sub_bytes(x.w, b.w));
+}
+
+// 16 elements of K bytes from any address into 4 K words: the K (aligned) or K + 1 aligned granules that hold them.
+template <int K>
+__device__ __forceinline__ void load_elems16(u64 addr, u32 (&w)[4 * K]) {
+    const uint4 * g = (const uint4 *)(addr & ~(u64)15);
+    const u32 sh = (u32)(addr & 15);
+    uint4 v[K + 1];
+#pragma unroll
+    for (int i = 0; i < K; i++) v[i] = g[i];
+    if (sh) {
+        v[K] = g[K];  // holds the lane's last sh bytes
+#pragma unroll
+        for (int i = 0; i < K; i++) v[i] = shift_bytes(v[i], v[i + 1], sh);
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+        w[4 * i] = v[i].x;
+        w[4 * i + 1] = v[i].y;
+        w[4 * i + 2] = v[i].z;
+        w[4 * i + 3] = v[i].w;
+    }
 }
 
 // 16 bytes of LDS from any byte offset: five aligned dwords.
@@ -155,37 +208,27 @@ __device__ __forceinline__ u64 align16_up_to(u64 a, u64 end) {
     return a < end ? a : end;
 }
 
-// Tile `tile` of a split: elements [ea, ea + PLANES_TILE_ELEMS) of the block at `src` into the planes at `dst`.
-template <int K>
-__device__ __forceinline__ void split_tile(const u8 * src, u8 * dst, u64 len, u64 tile, u8 * lds) {
+// Tile `tile` of a split: elements [ea, ea + PLANES_TILE_ELEMS) of the block at `src` into the planes at `dst`; with D, of the
+// block's byte-wise difference from the bytes at `base`.
+template <int K, bool D>
+__device__ __forceinline__ void split_tile(const u8 * src, const u8 * base, u8 * dst, u64 len, u64 tile, u8 * lds) {
     const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
     const u64 e = ea + 16 * (u64)threadIdx.x;
     if (e + 16 <= m) {
-        const u64 addr = (u64)src + e * K;
-        const uint4 * g = (const uint4 *)(addr & ~(u64)15);
-        const u32 sh = (u32)(addr & 15);
-        uint4 v[K + 1];
-#pragma unroll
-        for (int i = 0; i < K; i++) v[i] = g[i];
-        if (sh) {
-            v[K] = g[K];  // holds the lane's last sh bytes
-#pragma unroll
-            for (int i = 0; i < K; i++) v[i] = shift_bytes(v[i], v[i + 1], sh);
-        }
         u32 w[4 * K], p[K][4];
+        load_elems16<K>((u64)src + e * K, w);
+        if (D) {
+            u32 b[4 * K];
+            load_elems16<K>((u64)base + e * K, b);
 #pragma unroll
-        for (int i = 0; i < K; i++) {
-            w[4 * i] = v[i].x;
-            w[4 * i + 1] = v[i].y;
-            w[4 * i + 2] = v[i].z;
-            w[4 * i + 3] = v[i].w;
+            for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
         }
         deinterleave<K>(w, p);
 #pragma unroll
         for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
     } else {
         for (u64 i = e; i < m; i++)
-            for (int q = 0; q < K; q++) lds[q * PLANE_STRIDE + (i - ea)] = src[i * K + q];
+            for (int q = 0; q < K; q++) lds[q * PLANE_STRIDE + (i - ea)] = D ? (u8)(src[i * K + q] - base[i * K + q]) : src[i * K + q];
     }
     __syncthreads();
     const bool last = ea + PLANES_TILE_ELEMS >= m;
@@ -196,12 +239,16 @@ __device__ __forceinline__ void split_tile(const u8 * src, u8 * dst, u64 len, u6
         const u64 s1 = last ? pend : align16_up_to(p0 + ea + PLANES_TILE_ELEMS, pend);
         store_from_lds<1>(lds + q * PLANE_STRIDE, p0 + ea, s0, s1);
     }
-    if (tile == 0 && threadIdx.x < len - m * K) dst[m * K + threadIdx.x] = src[m * K + threadIdx.x];
+    if (tile == 0 && threadIdx.x < len - m * K) {
+        const u64 t = m * K + threadIdx.x;
+        dst[t] = D ? (u8)(src[t] - base[t]) : src[t];
+    }
 }
 
-// Tile `tile` of a merge: elements [ea, ea + PLANES_TILE_ELEMS) of the planes at `src` into the block at `dst`.
-template <int K>
-__device__ __forceinline__ void merge_tile(const u8 * src, u8 * dst, u64 len, u64 tile, u8 * lds) {
+// Tile `tile` of a merge: elements [ea, ea + PLANES_TILE_ELEMS) of the planes at `src` into the block at `dst`; with D, plus the
+// bytes at `base` (which may be `dst`: every read of the base is phase 1's or the tail thread's own, see the head of this file).
+template <int K, bool D>
+__device__ __forceinline__ void merge_tile(const u8 * src, const u8 * base, u8 * dst, u64 len, u64 tile, u8 * lds) {
     const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
     const u64 e = ea + 16 * (u64)threadIdx.x;
     if (e + 16 <= m) {
@@ -215,11 +262,17 @@ __device__ __forceinline__ void merge_tile(const u8 * src, u8 * dst, u64 len, u6
             p[q][3] = v.w;
         }
         interleave<K>(p, w);
+        if (D) {
+            u32 b[4 * K];
+            load_elems16<K>((u64)base + e * K, b);
+#pragma unroll
+            for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
+        }
 #pragma unroll
         for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
     } else {
         for (u64 i = e; i < m; i++)
-            for (int q = 0; q < K; q++) lds[(i - ea) * K + q] = src[q * m + i];
+            for (int q = 0; q < K; q++) lds[(i - ea) * K + q] = D ? (u8)(src[q * m + i] + base[i * K + q]) : src[q * m + i];
     }
     __syncthreads();
     const bool last = ea + PLANES_TILE_ELEMS >= m;
@@ -227,20 +280,25 @@ __device__ __forceinline__ void merge_tile(const u8 * src, u8 * dst, u64 len, u6
     const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ea * K, dend);
     const u64 s1 = last ? dend : align16_up_to(d0 + (ea + PLANES_TILE_ELEMS) * K, dend);
     store_from_lds<K>(lds, d0 + ea * K, s0, s1);  // at most 255 K + 1 granules
-    if (tile == 0 && threadIdx.x < len - m * K) dst[m * K + threadIdx.x] = src[m * K + threadIdx.x];
+    if (tile == 0 && threadIdx.x < len - m * K) {
+        const u64 t = m * K + threadIdx.x;
+        dst[t] = D ? (u8)(src[t] + base[t]) : src[t];
+    }
 }
 
-// One tile of a segment with an element size (CopySeg::mode).
+// One tile of a segment with an element size (CopySeg::mode); D: and a base.
+template <bool D>
 __device__ __forceinline__ void planes_tile(const CopySeg & sg, u64 tile, u8 * lds) {
     const u8 * src = (const u8 *)sg.src;
+    const u8 * base = (const u8 *)sg.base;
     u8 * dst = (u8 *)sg.dst;
     switch ((u32)sg.mode) {
-        case 2: split_tile<2>(src, dst, sg.len, tile, lds); break;
-        case 4: split_tile<4>(src, dst, sg.len, tile, lds); break;
-        case 8: split_tile<8>(src, dst, sg.len, tile, lds); break;
-        case 2 | PLANES_INVERSE: merge_tile<2>(src, dst, sg.len, tile, lds); break;
-        case 4 | PLANES_INVERSE: merge_tile<4>(src, dst, sg.len, tile, lds); break;
-        case 8 | PLANES_INVERSE: merge_tile<8>(src, dst, sg.len, tile, lds); break;
+        case 2: split_tile<2, D>(src, base, dst, sg.len, tile, lds); break;
+        case 4: split_tile<4, D>(src, base, dst, sg.len, tile, lds); break;
+        case 8: split_tile<8, D>(src, base, dst, sg.len, tile, lds); break;
+        case 2 | PLANES_INVERSE: merge_tile<2, D>(src, base, dst, sg.len, tile, lds); break;
+        case 4 | PLANES_INVERSE: merge_tile<4, D>(src, base, dst, sg.len, tile, lds); break;
+        case 8 | PLANES_INVERSE: merge_tile<8, D>(src, base, dst, sg.len, tile, lds); break;
         default: break;
     }
 }
@@ -258,8 +316,68 @@ __global__ void __launch_bounds__(COPY_THREADS) k_move_segments(const CopySeg * 
         else hi = mid;
     }
     const CopySeg sg = segs[lo];
-    if ((sg.mode & 0xff) > 1) planes_tile(sg, b - tile_start[lo], (u8 *)lds);
+    if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, b - tile_start[lo], (u8 *)lds);
     else copy_segment_tile(sg, b - tile_start[lo]);
+}
+
+// ---- delta segments ---------------------------------------------------------------------------------------------------------------
+// One tile of a segment with a base and no element size: copy_tile's tiling (COPY_TILE_GRANULES destination granules from g_first), a
+// destination granule = the source's 16 bytes minus (INV: plus) the base's, each built from the one or two aligned granules that hold
+// them (both hold bytes of the segment, or of the base range, because the destination granule lies inside the segment), one 16-byte
+// store; byte by byte at the partial granules of the two ends.
+template <bool INV>
+__device__ __forceinline__ void delta1_tile(const u8 * src, const u8 * base, u8 * dst, u64 len, u64 g_first, u64 g_end) {
+    const u64 d0 = (u64)dst, d1 = d0 + len;
+    const u64 ds = (u64)src - d0, db = (u64)base - d0;  // source / base address = destination address + ds / db (mod 2^64)
+    if (g_end - g_first == COPY_TILE_GRANULES && (g_first << 4) >= d0 && (g_end << 4) <= d1) {  // every granule of the tile is full: loads first, then stores
+        uint4 x[COPY_GRANULES_PER_LANE], b[COPY_GRANULES_PER_LANE];
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+            const u64 a = (g_first + k * COPY_THREADS + threadIdx.x) << 4;
+            x[k] = load16_any(a + ds);
+            b[k] = load16_any(a + db);
+        }
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) *(uint4 *)((g_first + k * COPY_THREADS + threadIdx.x) << 4) = delta16<INV>(x[k], b[k]);
+        return;
+    }
+    for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+        const u64 g = g_first + k * COPY_THREADS + threadIdx.x;
+        if (g >= g_end) break;
+        const u64 a = g << 4;  // destination granule [a, a + 16)
+        if (a >= d0 && a + 16 <= d1) {
+            *(uint4 *)a = delta16<INV>(load16_any(a + ds), load16_any(a + db));
+        } else {
+            const u64 b0 = a > d0 ? a : d0, b1 = a + 16 < d1 ? a + 16 : d1;
+            for (u64 b = b0; b < b1; b++) *(u8 *)b = INV ? (u8)(*(const u8 *)(b + ds) + *(const u8 *)(b + db)) : (u8)(*(const u8 *)(b + ds) - *(const u8 *)(b + db));
+        }
+    }
+}
+
+// k_move_segments for a launch in which some segment has a base: those segments take the delta tiles, the others what they take in
+// k_move_segments.  (A kernel of its own, as k_move_segments is: launches without a base keep the code and the registers they had.)
+__global__ void __launch_bounds__(COPY_THREADS) k_delta_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    const u32 tile = b - tile_start[lo];
+    if (!sg.base) {
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
+        else copy_segment_tile(sg, tile);
+    } else if ((sg.mode & 0xff) > 1) {
+        planes_tile<true>(sg, tile, (u8 *)lds);
+    } else {
+        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
+        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+        if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+        else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+    }
 }
 
 }  // namespace bz3

@@ -170,6 +170,46 @@ BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t el
  * a segment is copied (elem_size 1), split (inverse 0) or merged (inverse 1) in one launch.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n);
 
+/* Delta frames: the byte-plane calls above for data of which an earlier version (the base) is in device memory of the same GPU.
+ * D(x, b)[i] = (x[i] - b[i]) mod 256 for every byte i of x, b holding as many bytes as x; its inverse is (d[i] + b[i]) mod 256.  The
+ * compress calls write exactly bz3_compress(block_size, S(D(in, base))), S as defined above for elem_size (1: the identity): an
+ * ordinary .bz3 frame, which stores neither the element size nor anything about the base.  D is position-wise, so block j pairs with
+ * the base bytes [j bs, j bs + len_j); what src/libbz3.c:914 drops stays dropped.  The decompress calls decode a frame, apply merge_k
+ * to every chunk and add the base bytes at the chunk's output offsets.  Everything else is the contract of the _planes calls with
+ * S(D(x, b)) in the place of S(x): return codes, *out_size, whole restored chunks committed before an error and nothing else of `out`
+ * touched, the independence of the frames of a _many call, windows across frames, the headroom rule.
+ *   base == NULL (bases == NULL, bases[i] == NULL): the frame has no base and the call is exactly its _planes call.
+ *   compress: `base` holds in_size bytes; it is never written.
+ *   decompress: `base` holds base_size bytes and the frame's capacity is min(*out_size, base_size): a chunk that would run past the
+ *     base fails with BZ3_ERR_DATA_TOO_BIG, as one that runs past `out` does, after the chunks before it are committed.  `out` may be
+ *     exactly `base` (the same address: the base is updated in place, and after an error the bytes beyond *out_size are still the
+ *     base's) or must not overlap it.
+ *   BZ3_ERR_INIT before any write (_many: for the whole call, in every rcs[i], every out_sizes[i] = 0): a non-empty base that is not
+ *     device memory of the call's GPU; on decompress an `out` that overlaps its base without starting at the same address; on compress an
+ *     `out` that overlaps the frame's base or its input.  Overlaps between different frames of a _many call are not looked for.
+ * The difference is taken in the launches that move a window's blocks into and out of their slots (planes.hpp): one more read
+ * stream, no pass over the data and no buffer of the size of the input is added.  Decoding against another base than the one the
+ * frame was made with returns other bytes and no error: keep a checksum of the base (bz3_hip_crc32c_device) beside the frame. */
+BZIP3_API int bz3_hip_compress_device_delta(uint32_t block_size, uint32_t elem_size, const void * in, const void * base, void * out,
+                                            size_t in_size, size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device_delta(uint32_t elem_size, const void * in, const void * base, size_t base_size, void * out,
+                                              size_t in_size, size_t * out_size);
+BZIP3_API int bz3_hip_compress_device_delta_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[],
+                                                 const void * const bases[], const size_t in_sizes[], void * const outs[],
+                                                 size_t out_sizes[], int rcs[]);
+BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[],
+                                                   const size_t in_sizes[], const void * const bases[], const size_t base_sizes[],
+                                                   void * const outs[], size_t out_sizes[], int rcs[]);
+/* The checksum of the block headers (crc32sum, src/libbz3.c: CRC-32C, state `init`, no inversion; the codec uses init = 1) over n bytes
+ * of device memory at any alignment, computed on the GPU that owns them.  Returns BZ3_OK with the value in *crc (n == 0: init), or
+ * BZ3_ERR_INIT for a pointer that is not device memory.  Synchronous. */
+BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc);
+/* Test hook: bz3_hip_debug_planes with a base: n (src_off, base_off, dst_off, len, elem_size | inverse << 8) quintuples (host array of
+ * 5 n u64) relative to `src` / `base` / `dst`; base_off = UINT64_MAX: the segment has no base.  A segment with a base stores
+ * split_k(src - base) (inverse 0) or merge_k(src) + base (inverse 1), the base paired with the interleaved side.  `dst` may be `base`
+ * with dst_off == base_off for inverse segments.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
