@@ -89,6 +89,10 @@ def _declare(L, strict=True):
         "bz3_hip_decompress_device_delta_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_crc32c_device": (C.c_int, [vp, sz, u32, C.POINTER(u32)]),
         "bz3_hip_debug_delta": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_decompress_device_range": (C.c_int, [u32, vp, sz, C.c_uint64, vp, sz, vp, C.POINTER(sz)]),
+        "bz3_hip_decompress_device_range_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
+                                                           C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_range": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -522,6 +526,63 @@ def decompress_tensors(frames, outs=None, lib=None, planes=1, bases=None):
     return res
 
 
+def decompress_tensors_range(frames, offsets, nbytes, outs=None, planes=1, bases=None, lib=None):
+    """Bytes [offsets[i], offsets[i] + nbytes[i]) of what frames[i] decodes to, for many frames in ONE call
+    (bz3_hip_decompress_device_range_many): only the chunks that hold bytes of a range are decoded (plus a walk over the chunk headers
+    before the range); that saves GPU work, while one call still takes at least one block's decode time ("Range decode").  Returns uint8 tensors, shorter than nbytes[i]
+    where the range runs past the end of the frame (pread's rule; never an error).  `outs`: contiguous uint8 tensors of at least
+    nbytes[i] bytes to read into; by default views of one allocation.  `planes` as in decompress_tensors.  `bases[i]`: None, or the
+    base's bytes OF THE RANGE (at least nbytes[i] of them: bases[i][j] pairs with byte offsets[i] + j); outs[i] may be bases[i].  The
+    same frame may appear more than once.  Raises Bz3Error with .index / .codes / .outs (per frame the range bytes committed before its
+    error) as decompress_tensors does.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    offsets, nbytes = [int(o) for o in offsets], [int(w) for w in nbytes]
+    if len(offsets) != n or len(nbytes) != n:
+        raise ValueError(f"decompress_tensors_range: {n} frames, {len(offsets)} offsets and {len(nbytes)} sizes")
+    if any(o < 0 for o in offsets) or any(w < 0 for w in nbytes):
+        raise ValueError("decompress_tensors_range: offsets and sizes must not be negative")
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
+    dev = _same_device(frames, "decompress_tensors_range")
+    L = lib or load()
+    if outs is None:
+        outs = _carve(sum(nbytes), nbytes, dev)
+    else:
+        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
+        if len(outs) != n:
+            raise ValueError(f"decompress_tensors_range: {n} frames and {len(outs)} outputs")
+        _same_device(frames + outs, "decompress_tensors_range")
+    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
+        if o.numel() < w or (b is not None and b.numel() < w):
+            raise ValueError(f"decompress_tensors_range: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
+    torch.cuda.synchronize(dev)
+    out_sizes = (C.c_size_t * n)(*nbytes)
+    rcs = (C.c_int * n)()
+    rc = L.bz3_hip_decompress_device_range_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), (C.c_uint64 * n)(*offsets),
+                                                _ptrs_or_null(bases), (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, nbytes)]), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, "bz3_hip_decompress_device_range_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def decompress_tensor_range(frame, offset, nbytes, out=None, planes=1, base=None, lib=None):
+    """Bytes [offset, offset + nbytes) of what `frame` decodes to (bz3_hip_decompress_device_range): the uint8 tensor of the bytes
+    read, shorter than nbytes past the end of the frame.  decompress_tensors_range for one frame; Bz3Error's `.out` holds the range
+    bytes committed before the error."""
+    try:
+        return decompress_tensors_range([frame], [offset], [nbytes], None if out is None else [out], planes=planes, bases=None if base is None else [base], lib=lib)[0]
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_decompress_device_range", e.outs[0]) from None
+
+
 # ---- typed tensors ------------------------------------------------------------------------------------------------------------
 # The byte-plane element size pack_tensor uses when `planes` is None, by dtype name: the component size where the measurements of
 # DESIGN.md ("Typed tensors") show the planes frame smaller than the interleaved one, 1 where they show it larger or no different
@@ -728,6 +789,70 @@ def unpack_tensor(p, out=None, lib=None, base=None, check_base=True):
     return _unpack_many([p], None if out is None else [out], lib, [base], check_base)[0]
 
 
+def _row_bytes(p, what):
+    if not isinstance(p, PackedTensor):
+        raise TypeError("unpack: a PackedTensor is expected")
+    if len(p.shape) == 0:
+        raise ValueError(f"{what}: a 0-d tensor has no rows")
+    return p.nbytes // p.shape[0] if p.shape[0] else 0
+
+
+def _unpack_rows_many(ps, rows, outs, lib, bases):
+    """Rows rows[i] = (start, stop) of dimension 0 of every PackedTensor (None: the whole tensor), in ONE
+    bz3_hip_decompress_device_range_many call."""
+    import torch
+
+    shapes, spans = [], []
+    for i, (p, r) in enumerate(zip(ps, rows)):
+        if not isinstance(p, PackedTensor):
+            raise TypeError("unpack: a PackedTensor is expected")
+        if r is None:
+            shapes.append(tuple(p.shape))
+            spans.append((0, p.nbytes))
+            continue
+        rb = _row_bytes(p, f"tensor {i}")
+        start, stop = int(r[0]), int(r[1])
+        if not 0 <= start <= stop <= p.shape[0]:
+            raise ValueError(f"rows ({start}, {stop}) of a tensor of {p.shape[0]} rows")
+        shapes.append((stop - start, *p.shape[1:]))
+        spans.append((start * rb, (stop - start) * rb))
+    bases = _bases_arg(bases, len(ps))
+    braws = []
+    for i, (p, b, (_, w), shape) in enumerate(zip(ps, bases, spans, shapes)):
+        if p.delta and b is None:
+            raise ValueError(f"unpack: tensor {i} was packed against a base, which is needed to restore it")
+        if not p.delta:
+            b = None
+        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != shape:
+            raise ValueError(f"unpack: base {i} must hold the same rows of the base: {p.dtype} {shape}")
+        braws.append(_base_bytes(b, w, p.frame.device, f"base {i}"))
+    dev = _same_device([p.frame for p in ps], "unpack")
+    if outs is None:
+        raws = _carve(0, [w for _, w in spans], dev)  # every output at a multiple of 16 bytes, so that any dtype can view it
+    else:
+        raws = []
+        for p, o, shape in zip(ps, outs, shapes):
+            if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or tuple(o.shape) != shape or not o.is_contiguous():
+                raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and of the rows' shape")
+            raws.append(_as_bytes(o, "out"))
+    got = decompress_tensors_range([p.frame for p in ps], [o for o, _ in spans], [w for _, w in spans], raws, planes=[p.planes for p in ps], bases=braws, lib=lib)
+    for i, (g, (_, w)) in enumerate(zip(got, spans)):
+        if g.numel() != w:
+            raise Bz3Error(BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} holds {g.numel()} of the {w} bytes of its rows;", g)
+    return list(outs) if outs is not None else [_from_bytes(r, p.dtype, shape) for r, p, shape in zip(raws, ps, shapes)]
+
+
+def unpack_tensor_rows(p, start, stop, out=None, base=None, lib=None):
+    """Rows [start, stop) of dimension 0 of the tensor a PackedTensor holds, in its dtype, of shape (stop - start, *p.shape[1:]), on the
+    frame's GPU: only the chunks of the frame that hold bytes of those rows are decoded (bz3_hip_decompress_device_range), so a
+    tensor-parallel rank that loads 1/N of the rows decodes about 1/N of the chunks.  ValueError for a 0-d tensor and unless
+    0 <= start <= stop <= p.shape[0]; Bz3Error if the frame fails or returns fewer bytes than the rows hold.  `out`: a contiguous
+    tensor of that dtype and shape.  A tensor packed against a base needs `base`: THE SAME ROWS of the base (a GPU tensor of the
+    dtype and of the rows' shape; `out` may be it).  PackedTensor.base_crc covers the whole base and cannot be checked against a slice
+    of it: the caller vouches that these are rows of the right base (another base gives other bytes and no error)."""
+    return _unpack_rows_many([p], [(start, stop)], None if out is None else [out], lib, [base])[0]
+
+
 def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None):
     """pack_tensor for every tensor of a dict, batched: {name: PackedTensor}, each equal to pack_tensor(sd[name], block_size, planes).
     One bz3_hip_compress_device_delta_many call per distinct lossless block size (the C call takes one block size): the tensors whose
@@ -748,12 +873,38 @@ def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None):
     return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib, bases)))
 
 
-def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True):
+def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None):
     """The tensors of pack_state_dict's result, decoded in ONE batched call (bz3_hip_decompress_device_delta_many).  `base`: the dict
     pack_state_dict was given; every tensor packed against a base needs its entry (unpack_tensor's rules and check_base).  With
     inplace=True those base tensors themselves are updated and returned (no second copy of the model in memory); tensors packed
-    without a base are returned in new memory as usual."""
+    without a base are returned in new memory as usual.  `rows`: {name: (start, stop)}: those tensors come back as their rows
+    [start, stop) of dimension 0 alone (unpack_tensor_rows), the names not in it whole, all of them through ONE
+    bz3_hip_decompress_device_range_many call that decodes only the chunks it needs.  `base` is then the whole base dict as ever: check_base checks
+    every base tensor whole against its base_crc (one read of it, for the tensors read by rows too), then their rows are taken here.
+    With inplace=True, ValueError."""
     names = list(packed)
+    if rows is not None:
+        if inplace:
+            raise ValueError("unpack_state_dict: rows and inplace=True do not go together")
+        unknown = [k for k in rows if k not in packed]
+        if unknown:
+            raise ValueError(f"unpack_state_dict: rows for {unknown[0]!r}, which is not in the dict")
+        if not names:
+            return {}
+        ps = [packed[k] for k in names]
+        rws = [rows.get(k) for k in names]
+        bases = []
+        L = lib or load()
+        for k, p, r in zip(names, ps, rws):
+            b = base.get(k) if base is not None and p.delta else None
+            # the whole base is at hand here, for the tensors read by rows too: check it as unpack_tensor does, before anything is decoded
+            if check_base and b is not None and p.base_crc is not None and getattr(b, "dtype", None) == p.dtype and tuple(b.shape) == tuple(p.shape):
+                if base_crc(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}"), L) != p.base_crc:
+                    raise ValueError(f"unpack: base {k!r} is not the tensor this frame was packed against (its checksum differs)")
+            if b is not None and r is not None and len(p.shape) and tuple(b.shape) == tuple(p.shape) and 0 <= int(r[0]) <= int(r[1]) <= p.shape[0]:
+                b = b[int(r[0]) : int(r[1])]
+            bases.append(b)
+        return dict(zip(names, _unpack_rows_many(ps, rws, None, lib, bases)))
     if not names:
         return {}
     ps = [packed[k] for k in names]

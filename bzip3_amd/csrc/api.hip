@@ -2235,26 +2235,54 @@ int device_of(const void * p) {
 // Device tables of one k_copy_segments launch: the segments, then the nseg + 1 tile starts.
 constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg) + 15) & ~(size_t)15) + (nseg + 1) * sizeof(u32); }
 
+// The same for a launch that may hold clipped merges (planes.hpp k_range_segments): behind the tables above, 16-byte aligned, the
+// [a, b) of every segment (two u64 each).
+constexpr size_t range_table_bytes(size_t nseg) { return ((copy_table_bytes(nseg) + 15) & ~(size_t)15) + nseg * 2 * sizeof(u64); }
+
 // Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
 // The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
-void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
+// clips (or nullptr): two u64 per segment, the [a, b) of the segments with PLANES_CLIP; d_tab then holds range_table_bytes(segs.size())
+// bytes, and a launch with such a segment goes to k_range_segments.
+void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr) {
     const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
-    staging.assign(copy_table_bytes(n), 0);
+    if (clips && clips->size() != 2 * n) throw std::length_error("one clip per segment");
+    staging.assign(clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
     if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
     u32 * starts = (u32 *)(staging.data() + seg_bytes);
     u64 tiles = 0;
-    bool planes = false, delta = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
+    bool planes = false, delta = false, clip = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
     for (size_t i = 0; i < n; i++) {
         starts[i] = (u32)tiles;
-        tiles += segment_tiles(segs[i]);
+        if (segs[i].mode & PLANES_CLIP) {
+            if (!clips) throw std::length_error("a clipped segment without its clip");
+            tiles += clip_tiles(segs[i].len, segs[i].mode & 0xff, (*clips)[2 * i], (*clips)[2 * i + 1]);
+            clip = true;
+        } else {
+            tiles += segment_tiles(segs[i]);
+        }
         planes |= (segs[i].mode & 0xff) > 1;
         delta |= segs[i].base != 0;
     }
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
-    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
-    launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+    const size_t clip_off = range_table_bytes(n) - n * 2 * sizeof(u64);
+    if (clip) memcpy(staging.data() + clip_off, clips->data(), n * 2 * sizeof(u64));
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), clip ? staging.size() : copy_table_bytes(n), hipMemcpyHostToDevice, s));
+    if (clip)
+        launch(k_range_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off));
+    else
+        launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+}
+
+// The gather segment of chunk bytes [a, b) of a decoded chunk of s bytes in `slot`, element size k, to dst (and base, or 0), which
+// address the clip's first byte: a whole chunk and every k = 1 clip are ordinary segments, the rest clipped merges (planes.hpp).
+void push_range_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, u64 slot, u64 s, u64 k, u64 a, u64 b, u64 dst, u64 base) {
+    const bool plain = k <= 1 || a == b || (a == 0 && b == s);
+    if (plain) segs.push_back({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
+    else segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base});
+    clips.push_back(plain ? 0 : a);
+    clips.push_back(plain ? 0 : b);
 }
 
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
@@ -2265,13 +2293,13 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Layout of a call's small device buffer, sized for its n frames: staged headers (one 13-byte frame header per frame and one
 // 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
-// header), the walk's arguments, records and tails.
+// header; with room for their clips), the walk's arguments, records and tails.
 struct MetaLayout {
     size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, bytes = 0;
     MetaLayout() = default;
     explicit MetaLayout(size_t frames) : n(frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
-        args = tab + align256(copy_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        args = tab + align256(range_table_bytes(2 * FRAME_WINDOW_MAX + n));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
         bytes = tails + align256(n * sizeof(WalkTail));
@@ -2297,6 +2325,7 @@ struct DeviceFrames {
     size_t stride = 0;
     std::vector<bz3_state *> states;
     std::vector<CopySeg> segs;
+    std::vector<u64> clips;  // empty, or the [a, b) of every segment of `segs` (a range call's gather)
     std::vector<u8> staging;
     ~DeviceFrames() {
         if (device < 0) return;
@@ -2358,9 +2387,10 @@ struct DeviceFrames {
     u8 * slot(size_t k) const { return slab + k * stride; }
     void copy() {  // the segments collected in `segs`, one launch, complete on return
         if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
-        copy_segments(segs, staging, meta + lay.tab, s);
+        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips);
         HIP_CHECK(hipStreamSynchronize(s));
         segs.clear();
+        clips.clear();
     }
     void stage_headers(const std::vector<u8> & h) {
         if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
@@ -2390,7 +2420,10 @@ struct WalkPos {
     u64 off = 0, planned = 0;
     u32 done = 0, block_size = 0, n_blocks = 0;
     WalkArg arg(const u8 * in, size_t in_size, size_t buf_max, u32 limit, u32 rec_base) const {
-        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0};
+        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0, 0, 0};
+    }
+    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base) const {  // the chunks that hold a byte of [lo, hi)
+        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi};
     }
     void take(const WalkTail & t) {
         off = t.off;
@@ -2578,13 +2611,20 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
 // bases (or nullptr): per frame nullptr, or base_sizes[i] bytes that are added to the decoded bytes at the same offsets; such a frame's capacity
 // is the smaller of out_sizes[i] and base_sizes[i], so that the walk refuses a chunk that runs past the base as one that runs past `out`.
 // outs[i] may be bases[i] (planes.hpp, "In place").
+// range (bz3_hip_decompress_device_range[_many]): frame i wants the w = min(out_sizes[i], base_sizes[i]) decoded bytes from offsets[i] on
+// (offsets == nullptr: 0) and nothing is too big.  Its walks are range walks (frame.hpp): chunks that end before the range are
+// header-checked and skipped on the device, headers at or beyond its end are never read, so the windows hold only the chunks that
+// share a byte with their frame's range; the first and the last of them are gathered clipped (push_range_segment), and `committed`
+// counts range bytes.  A frame's walk is over at its last chunk, at a header error or at the end of its range.
 void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
-                       u8 * const * outs, size_t * out_sizes, int * rcs) {
+                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr) {
     struct Frame {
         size_t buf_max = 0, committed = 0;
-        u32 decoded = 0;        // chunks decoded and committed (pos.done: chunks walked)
+        u32 decoded = 0;        // chunks decoded and committed
+        u32 walked = 0;         // chunks the walks recorded, less those given back (whole frames: pos.done)
         int pending = BZ3_OK;   // the header error the walk stopped at
         bool failed = false;    // a chunk of the current window failed
+        u64 lo = 0, hi = 0;     // range: the decoded bytes wanted
     };
     struct Chunk {
         s32 frame;
@@ -2599,6 +2639,11 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
         else live[i] = any = 1;
         fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
+        if (range) {
+            fr[i].lo = offsets ? offsets[i] : 0;
+            fr[i].hi = fr[i].lo + (u64)fr[i].buf_max < fr[i].lo ? UINT64_MAX : fr[i].lo + (u64)fr[i].buf_max;
+            out_sizes[i] = 0;
+        }
     }
     if (!any) return;
     DeviceFrames f;
@@ -2632,12 +2677,42 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 const s32 i = who[q];
                 for (u32 r = 0; r < tails[q].count; r++) win.push_back({i, rec[args[q].rec_base + r]});
                 pos[i].take(tails[q]);
+                fr[i].walked += tails[q].count;
                 if (tails[q].err != BZ3_OK) {
                     fr[i].pending = tails[q].err;
                     stopped = true;
                 }
             }
             if (!stopped) return;  // every frame walked its limit: the window is full or no chunk is left
+        }
+    };
+    // The same for ranges.  How many chunks a range touches is known only once they are walked, so every frame gets a limit of what its
+    // range would take of full blocks (two more for the two ends), the window's size at most, as long as the walk's records last: 256
+    // frames that want one chunk each are one walk and one window.  What a walk finds beyond W goes back to its frames (give_back).
+    auto range_walk_over = [&](s32 i) { return pos[i].done == pos[i].n_blocks || pos[i].planned >= fr[i].hi; };
+    auto collect_range = [&](size_t W) {
+        win.clear();
+        while (win.size() < W) {
+            args.clear();
+            who.clear();
+            u32 base = 0;
+            for (s32 i = cur; i < n && base < WALK_RECORDS; i++) {
+                if (!live[i] || fr[i].pending != BZ3_OK || range_walk_over(i)) continue;
+                const u64 from = std::max(fr[i].lo, pos[i].planned), est = (fr[i].hi - from) / pos[i].block_size + 2;
+                const u32 lim = (u32)std::min<u64>({est, (u64)(pos[i].n_blocks - pos[i].done), (u64)(W - win.size()), (u64)(WALK_RECORDS - base)});
+                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base));
+                who.push_back(i);
+                base += lim;
+            }
+            if (args.empty()) return;
+            f.walk(args, rec, tails);
+            for (size_t q = 0; q < who.size(); q++) {  // (every frame walked its limit or its walk is over: the loop ends)
+                const s32 i = who[q];
+                for (u32 r = 0; r < tails[q].count; r++) win.push_back({i, rec[args[q].rec_base + r]});
+                pos[i].take(tails[q]);
+                fr[i].walked += tails[q].count;
+                if (tails[q].err != BZ3_OK) fr[i].pending = tails[q].err;
+            }
         }
     };
     // Chunks of `win` beyond the first W go back to their frames (the first window is walked before the states exist).
@@ -2647,7 +2722,8 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
             WalkPos & p = pos[c.frame];
             p.off = c.rec.in_off;
             p.planned = c.rec.out_off;
-            p.done--;
+            p.done = c.rec.index;
+            fr[c.frame].walked--;
             fr[c.frame].pending = BZ3_OK;  // found again by a later walk
             win.pop_back();
         }
@@ -2657,11 +2733,14 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
         DeviceGuard g(dev);
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
-        for (s32 i = 0; i < n; i++)
+        for (s32 i = 0; i < n; i++) {
+            if (range && fr[i].buf_max == 0) live[i] = 0;  // nothing wanted: the frame header alone was checked
             if (live[i]) bs_max = std::max(bs_max, pos[i].block_size);
+        }
         if (!bs_max) return;
         // n_blocks is untrusted: the states are sized from the chunks the first walk finds present, never from n_blocks
-        collect(frame_window_limit());
+        if (range) collect_range(frame_window_limit());
+        else collect(frame_window_limit());
         if (!f.init(bs_max, win.empty() ? 1 : win.size())) throw std::runtime_error("no states");
     } catch (...) {
         for (s32 i = 0; i < n; i++)
@@ -2679,7 +2758,8 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         std::vector<u8> hdrs(17 * (size_t)W);
         give_back(W);
         for (bool first = true;; first = false) {
-            if (!first) collect(W);
+            if (!first && range) collect_range(W), give_back(W);
+            else if (!first) collect(W);
             const u32 t = (u32)win.size();
             for (u32 k = 0; k < t; k++) {  // scatter: chunk k to slot k
                 const Chunk & c = win[k];
@@ -2704,9 +2784,16 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                         x.failed = true;
                         continue;
                     }
-                    f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
-                                      bases && bases[c.frame] ? (u64)(bases[c.frame] + c.rec.out_off) : 0});
-                    x.committed = c.rec.out_off + (size_t)c.rec.orig;
+                    if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
+                        const u64 p = c.rec.out_off, a = x.lo > p ? x.lo - p : 0, b = std::min<u64>(x.hi - p, (u64)c.rec.orig), at = p + a - x.lo;
+                        push_range_segment(f.segs, f.clips, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, a, b, (u64)(outs[c.frame] + at),
+                                           bases && bases[c.frame] ? (u64)(bases[c.frame] + at) : 0);
+                        x.committed = (size_t)(p + b - x.lo);
+                    } else {
+                        f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
+                                          bases && bases[c.frame] ? (u64)(bases[c.frame] + c.rec.out_off) : 0});
+                        x.committed = c.rec.out_off + (size_t)c.rec.orig;
+                    }
                     x.decoded++;
                 }
                 f.copy();
@@ -2718,7 +2805,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 Frame & x = fr[i];
                 out_sizes[i] = x.committed;
                 if (x.failed) live[i] = 0;
-                else if (x.decoded == pos[i].done && (x.pending != BZ3_OK || pos[i].done == pos[i].n_blocks)) {
+                else if (x.decoded == x.walked && (x.pending != BZ3_OK || pos[i].done == pos[i].n_blocks || (range && range_walk_over(i)))) {
                     rcs[i] = x.pending;
                     live[i] = 0;
                 } else {
@@ -2939,6 +3026,35 @@ BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t ele
     return first_error(n, rcs);
 }
 
+BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                   const uint64_t offsets[], const void * const bases[], const size_t base_sizes[], void * const outs[],
+                                                   size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        // the call touches w = min(*out_size, base_size) bytes of each at the most: two runs of w bytes overlap iff they start less than w apart
+        const u64 w = out_sizes[i] < base_sizes[i] ? out_sizes[i] : base_sizes[i], x = (u64)outs[i], y = (u64)bases[i];
+        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true,
+                      (const u64 *)offsets);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * base, size_t base_size, void * out,
+                                              size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    int rc = BZ3_OK;
+    return bz3_hip_decompress_device_range_many(1, &elem_size, ins, &in_size, &offset, bases, &base_size, outs, out_size, &rc);
+}
+
 BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
                                                     size_t out_sizes[], int rcs[]) {
     return bz3_hip_decompress_device_delta_many(n, elem_sizes, ins, in_sizes, nullptr, nullptr, outs, out_sizes, rcs);
@@ -3001,6 +3117,43 @@ BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint6
 
 BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
     return debug_move_segments(src, base, dst, segs, n, 5);
+}
+
+// n septuples (src_off, base_off, dst_off, len, elem_size | 1 << 8, a, b): of the merge of the `len` bytes at src_off the bytes [a, b), to
+// dst_off (plus the bytes at base_off unless it is UINT64_MAX), one launch through the segments a range call's gather makes of them.
+BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)7 * i;
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
+        any_base |= q[1] != UINT64_MAX;
+    }
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
+    u8 * d_tab = nullptr;
+    hipStream_t s = nullptr;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        std::vector<CopySeg> v;
+        std::vector<u64> clips;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)7 * i;
+            push_range_segment(v, clips, (u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+        }
+        std::vector<u8> staging;
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_CHECK(hipMalloc((void **)&d_tab, range_table_bytes((size_t)n)));
+        copy_segments(v, staging, d_tab, s, &clips);
+        HIP_CHECK(hipStreamSynchronize(s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    if (s) (void)hipStreamSynchronize(s);
+    if (d_tab) (void)hipFree(d_tab);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
 }
 
 // The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state `init`, no inversion) over n bytes of device memory: crc32c_device on a

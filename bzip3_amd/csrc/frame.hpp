@@ -137,19 +137,27 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
 // behind, planned = output bytes before it); off == 0 is the first visit, which reads and checks the 13-byte frame header
 // first (src/libbz3.c:930-960) and then walks from offset 13.  It walks up to `limit` chunks, writes their records from
 // rec[rec_base] on and its resume state to tails[i].
+//
+// A range walk (WalkArg::range != 0; bz3_hip_decompress_device_range, api.hip) wants only the chunks that hold a byte of the
+// output bytes [lo, hi): the lane stops before it reads a header with planned >= hi, and it advances over a chunk that ends at
+// or before lo (planned + orig <= lo) or is empty with its header checked as any other, but without a record and without using
+// any of `limit`, so a frame may hold any number of such chunks before its range.  The capacity check is not made
+// (the host passes buf_max = SIZE_MAX): a range is clipped, never too big.
 struct WalkChunk {
     u64 in_off;   // offset of the chunk header in the frame
     u64 out_off;  // output bytes of the chunks before it (planned)
     s32 size, orig;
     u8 hdr[17];   // the first 17 bytes of the chunk's coded bytes (zeros beyond the end of the frame)
-    u8 pad[7];
+    u8 pad[3];
+    u32 index;    // the chunk's number in its frame (the walk's `done` when it read the header)
 };
 struct WalkArg {
     u64 in, in_size, buf_max;  // the frame (device address, bytes), the output capacity
     u64 off, planned;          // resume state (off == 0: first visit)
     u32 done, limit, rec_base;
     u32 block_size, n_blocks;  // from the frame header (ignored on a first visit)
-    u32 pad;
+    u32 range;                 // != 0: a range walk over the output bytes [lo, hi)
+    u64 lo, hi;
 };
 struct WalkTail {
     u64 off, planned;  // resume state after the last well-formed chunk read
@@ -182,20 +190,24 @@ __global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg 
         }
     }
     while (err == BZ3_OK && c < a.limit && done < n_blocks) {
+        if (a.range && planned >= a.hi) break;  // headers at or beyond the end of the range are never read
         s32 size = 0, orig = 0;
         err = frame_chunk_check(frame + off, a.in_size - off, block_size, (size_t)a.buf_max, (size_t)planned, &size, &orig);
         if (err != BZ3_OK) break;
-        WalkChunk & w = rec[a.rec_base + c];
-        w.in_off = off;
-        w.out_off = planned;
-        w.size = size;
-        w.orig = orig;
         const u64 data = off + 8;
-        for (u32 k = 0; k < 17; k++) w.hdr[k] = data + k < a.in_size ? frame[data + k] : (u8)0;
+        if (!a.range || (orig > 0 && planned + (u64)orig > a.lo)) {
+            WalkChunk & w = rec[a.rec_base + c];
+            w.in_off = off;
+            w.out_off = planned;
+            w.size = size;
+            w.orig = orig;
+            w.index = done;
+            for (u32 k = 0; k < 17; k++) w.hdr[k] = data + k < a.in_size ? frame[data + k] : (u8)0;
+            c++;
+        }
         off = data + (u64)size;
         planned += (u64)orig;
         done++;
-        c++;
     }
     WalkTail & t = tails[i];
     t.off = off;

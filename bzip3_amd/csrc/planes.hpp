@@ -38,6 +38,23 @@
 //   * delta1_tile reads the base at the destination's own granules (dst == base: the same alignment), each by the thread that then
 //     stores it.
 // Any other overlap of base and destination is the caller's error (api.hip refuses it).
+//
+// Clipped merge (CopySeg::mode & PLANES_CLIP; bz3_hip_decompress_device_range, api.hip).  A range of a frame cuts its first and its
+// last chunk: of merge_k(slot[0, s)) only the bytes [a, b) are wanted, at dst[0, b - a), plus base[0, b - a) where there is a base
+// (dst and base address the clip's first byte; the chunk's byte c pairs with dst[c - a] and base[c - a]).  clip_merge_tile is
+// merge_tile with the chunk's own m = s / k as the plane stride and three changes:
+//   * only the tiles that hold an element byte of [a, b) are launched (clip_first_tile, clip_tiles), the first of them stores the
+//     clip's part of the tail;
+//   * a lane whose 16 elements lie inside [a, b) loads and transposes them as before; a lane whose elements straddle a or b moves
+//     the bytes inside the clip one by one (at most two lanes of a segment), a lane outside it loads nothing.  So every granule
+//     loaded from the slot holds a byte of the chunk, and every granule loaded from the base a byte of base[0, b - a): nothing
+//     around a range's base is relied on (without a base the straddling lanes may take the 16-byte path: all they load is the slot);
+//   * the tiles' store ranges are cut at the 16-byte boundaries of dst as before, and clamped to [dst, dst + min(b, m k) - a).
+// In place (dst == base): the argument above holds word for word with [s0, s1) clamped to the clip.  The bytes a tile stores are its
+// own, they lie within its 256 lanes' elements and inside [a, b), so every one of them was read from the base in phase 1 by a lane
+// of this tile (16-byte path: the lane lies inside the clip; byte path: the byte does), before the barrier; what else phase 1 read
+// of the base belongs to other tiles and lands in LDS outside [s0 - origin, s1 - origin); a tail byte is read and written by one
+// thread.  dst and base share the clip's coordinates, so dst == base pairs every byte with itself.
 #pragma once
 #include "frame.hpp"
 
@@ -48,6 +65,7 @@ constexpr u32 PLANES_LOAD_ELEMS = COPY_THREADS * 16;        // elements a workgr
 constexpr u32 PLANE_STRIDE = PLANES_LOAD_ELEMS + 16;        // LDS bytes per plane (split): phase 2 reads up to 20 bytes from offset < 4080
 constexpr u32 PLANES_LDS_BYTES = 8 * PLANE_STRIDE;          // >= 8 * PLANES_LOAD_ELEMS + 16, the merge layout
 constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = elem_size | PLANES_INVERSE for merge
+constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments alone)
 
 __host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // Workgroups of a split / merge segment: one per PLANES_TILE_ELEMS elements; a block shorter than an element still has its tail.
@@ -368,6 +386,110 @@ __global__ void __launch_bounds__(COPY_THREADS) k_delta_segments(const CopySeg *
     const CopySeg sg = segs[lo];
     const u32 tile = b - tile_start[lo];
     if (!sg.base) {
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
+        else copy_segment_tile(sg, tile);
+    } else if ((sg.mode & 0xff) > 1) {
+        planes_tile<true>(sg, tile, (u8 *)lds);
+    } else {
+        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
+        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+        if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+        else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+    }
+}
+
+// ---- clipped merge ------------------------------------------------------------------------------------------------------------------
+// The tiles of a merge of `len` bytes that hold an element byte of its bytes [a, b), a < b <= len: tiles first .. first + count - 1 of
+// planes_tiles(len, k).  A clip that holds tail bytes only still takes one tile, which stores them.
+__host__ __device__ inline u64 clip_first_tile(u64 len, u64 k, u64 a) {
+    const u64 t = a / (k * PLANES_TILE_ELEMS), n = planes_tiles(len, k);
+    return t < n ? t : n - 1;
+}
+__host__ __device__ inline u64 clip_tiles(u64 len, u64 k, u64 a, u64 b) {
+    const u64 mk = len / k * k, bm = b < mk ? b : mk;  // the clip's element bytes end at bm
+    return bm > a ? (bm - 1) / (k * PLANES_TILE_ELEMS) - a / (k * PLANES_TILE_ELEMS) + 1 : 1;
+}
+
+// Tile clip_first_tile + rel of a merge of the `len` bytes at `src`, of which the bytes [ca, cb) go to dst[0, cb - ca); with D, plus
+// base[0, cb - ca) (which may be `dst`).  See the head of this file.
+template <int K, bool D>
+__device__ __forceinline__ void clip_merge_tile(const u8 * src, const u8 * base, u8 * dst, u64 len, u64 ca, u64 cb, u64 rel, u8 * lds) {
+    const u64 m = len / K, ea = (clip_first_tile(len, K, ca) + rel) * PLANES_TILE_ELEMS;
+    const u64 e = ea + 16 * (u64)threadIdx.x;
+    const u64 bm = cb < m * K ? cb : m * K;
+    const u64 l0 = e * K, l1 = (e + 16) * K;  // the chunk bytes of the lane's elements
+    if (l0 < bm && l1 > ca) {
+        if (e + 16 <= m && (!D || (l0 >= ca && l1 <= cb))) {
+            u32 w[4 * K], p[K][4];
+#pragma unroll
+            for (int q = 0; q < K; q++) {
+                const uint4 v = load16_any((u64)src + q * m + e);
+                p[q][0] = v.x;
+                p[q][1] = v.y;
+                p[q][2] = v.z;
+                p[q][3] = v.w;
+            }
+            interleave<K>(p, w);
+            if (D) {
+                u32 b[4 * K];
+                load_elems16<K>((u64)base + (l0 - ca), b);
+#pragma unroll
+                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+        } else {
+            for (u64 i = e; i < m && i < e + 16; i++)
+                for (int q = 0; q < K; q++) {
+                    const u64 c = i * K + q;
+                    if (c >= ca && c < cb) lds[c - ea * K] = D ? (u8)(src[q * m + i] + base[c - ca]) : src[q * m + i];
+                }
+        }
+    }
+    __syncthreads();
+    if (bm > ca) {
+        const u64 d0 = (u64)dst, dend = d0 + (bm - ca);  // the chunk's byte c lives at d0 + (c - ca)
+        const u64 t0 = ea * K, t1 = (ea + PLANES_TILE_ELEMS) * K;
+        const u64 s0 = t0 <= ca ? d0 : align16_up_to(d0 + (t0 - ca), dend);
+        const u64 s1 = t1 >= bm ? dend : t1 <= ca ? d0 : align16_up_to(d0 + (t1 - ca), dend);
+        store_from_lds<K>(lds, d0 + t0 - ca, s0, s1);  // (the origin may lie below dst: only differences from it are used)
+    }
+    if (rel == 0 && threadIdx.x < len - m * K) {
+        const u64 t = m * K + threadIdx.x;
+        if (t >= ca && t < cb) dst[t - ca] = D ? (u8)(src[t] + base[t - ca]) : src[t];
+    }
+}
+
+// k_delta_segments for a launch in which some segment is a clipped merge: clips[2 i], clips[2 i + 1] are segment i's [a, b) (read for
+// segments with PLANES_CLIP alone); tile_start counts such a segment's workgroups with clip_tiles.  The other segments take what they
+// take in k_delta_segments.  (A kernel of its own, once more: launches without a clip keep the three kernels above as they are.)
+__global__ void __launch_bounds__(COPY_THREADS) k_range_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                 const u64 * __restrict__ clips) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    const u32 tile = b - tile_start[lo];
+    if (sg.mode & PLANES_CLIP) {
+        const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
+        const u8 * src = (const u8 *)sg.src;
+        const u8 * base = (const u8 *)sg.base;
+        u8 * dst = (u8 *)sg.dst;
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (!sg.base) {
         if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
         else copy_segment_tile(sg, tile);
     } else if ((sg.mode & 0xff) > 1) {

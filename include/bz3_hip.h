@@ -210,6 +210,44 @@ BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uin
  * with dst_off == base_off for inverse segments.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
 
+/* Range decode: the bytes [offset, offset + w) of what a frame decodes to, at the cost of the chunks that hold them.  For a frame f and
+ * an element size k let X be what bz3_hip_decompress_device_planes(k, f, ...) writes with unlimited capacity: chunk j (of the frame
+ * header's n_blocks) occupies [p_j, p_j + o_j) of X, o_j from its chunk header, p_j = o_0 + ... + o_{j-1}, T their sum.  w is *out_size
+ * on entry, with a base min(*out_size, base_size); end = offset + w, saturating at 2^64 - 1.  The call is pread(2) on X:
+ *   it writes out[i] = X[offset + i] for 0 <= i < r, r = max(0, min(T, end) - offset) -- with a base (X[offset + i] + base[i]) mod 256 --
+ *   and returns BZ3_OK with *out_size = r.  A range that runs past the end of the frame is short, not an error: this is the ONE
+ *   difference from the full call at offset 0, which reports BZ3_ERR_DATA_TOO_BIG where the range call clips; BZ3_ERR_DATA_TOO_BIG is
+ *   never returned here.
+ *   `base` holds the base's bytes OF THE RANGE: base[i] pairs with out[i].  `out` may be exactly `base` (updated in place) or must not
+ *   overlap it; any other overlap is BZ3_ERR_INIT before any write, as in the _delta calls.  The overlap is judged on the w bytes the
+ *   call can touch of each: out[0, w) and base[0, w), so a generous *out_size beside a small base is no overlap.
+ *   The frame header is always checked, as in the full call (src/libbz3.c:930-960).  The header of chunk j is read and checked iff
+ *   w > 0 and p_j < end, with the three header checks of bz3_decompress that do not concern capacity (:963-980), against the frame's
+ *   block size; headers at or beyond `end` are never read and their errors are not reported.
+ *   Chunk j is DECODED iff [p_j, p_j + o_j) and [offset, end) share a byte.  Chunks before the range are header-checked and skipped: a
+ *   corrupt payload in them is not noticed.  Empty chunks are never decoded.  A decoded chunk is decoded whole: its CRC and every
+ *   per-block check apply as in the full call, with its frame's block size.
+ *   The result is the first event in chunk order, a header error or a failed chunk: its code is returned, the range bytes of the
+ *   chunks before it are committed, *out_size is their count (a prefix of the range), nothing else of `out` is written.
+ *   Nothing outside out[0, r) is ever written; `in` and a base that is not `out` are never written.
+ * No index is stored: the chunk headers before the range are followed on the device by one lane (a few microseconds per chunk).
+ * _many: n independent ranges of n frames (the same frame may appear more than once) on ONE GPU; offsets == NULL is offset 0 for every
+ * frame, elem_sizes, bases and bases[i] may be NULL as in bz3_hip_decompress_device_delta_many, whose whole-call checks, return value,
+ * rcs[], independence of frames, windows across frame boundaries and headroom rule hold here word for word.  The windows hold only the
+ * chunks to be decoded: 256 frames that need one chunk each share one CM launch, and the states of a call are sized from the chunks
+ * its first walk selects.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * base,
+                                              size_t base_size, void * out, size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                   const uint64_t offsets[], const void * const bases[], const size_t base_sizes[],
+                                                   void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: one launch of the gather of a range call: n (src_off, base_off, dst_off, len, elem_size | 1 << 8, a, b) septuples (host
+ * array of 7 n u64) relative to `src` / `base` / `dst`.  Of merge_k(the len bytes at src_off) the bytes [a, b), a <= b <= len, are stored
+ * at dst_off, plus the b - a bytes at base_off unless base_off is UINT64_MAX: base_off and dst_off address the clip's first byte.  `dst`
+ * may be `base` with dst_off == base_off.  The inverse direction only; anything else is BZ3_ERR_INIT.  One launch takes mixed
+ * elem_size.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
