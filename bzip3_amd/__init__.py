@@ -88,6 +88,8 @@ def _declare(L, strict=True):
         "bz3_hip_compress_device_delta_many": (C.c_int, [u32, i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_decompress_device_delta_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_crc32c_device": (C.c_int, [vp, sz, u32, C.POINTER(u32)]),
+        "bz3_hip_crc32c_device_many": (C.c_int, [i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(u32), C.POINTER(u32)]),
+        "bz3_hip_debug_crc_launches": (C.c_uint, [C.c_int]),
         "bz3_hip_debug_delta": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_decompress_device_range": (C.c_int, [u32, vp, sz, C.c_uint64, vp, sz, vp, C.POINTER(sz)]),
         "bz3_hip_decompress_device_range_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
@@ -653,13 +655,15 @@ class PackedTensor:
     """A tensor as pack_tensor leaves it: `frame` (a uint8 GPU tensor holding a .bz3 frame of the tensor's bytes, split into byte planes
     of `planes` bytes per block), and what unpack_tensor needs to restore it: `dtype`, `shape`, `planes`, `block_size` (the one really
     used, see _lossless_block_size) and `nbytes`.  `delta`: the frame holds the byte-wise difference from a base tensor, which
-    unpack_tensor must be given again; `base_crc` is then the checksum of that base's bytes (bz3_hip_crc32c_device, init 1), else None."""
+    unpack_tensor must be given again; `base_crc` is then the checksum of that base's bytes (bz3_hip_crc32c_device, init 1), else None.
+    `crc`: the same checksum of the tensor's own bytes (those the frame decodes to once a base is added and the planes are merged), or
+    None where it was not recorded: what `verify=True` checks after a decode and what the next delta's `base_crc` must equal (check_chain)."""
 
-    __slots__ = ("frame", "dtype", "shape", "planes", "block_size", "nbytes", "delta", "base_crc")
+    __slots__ = ("frame", "dtype", "shape", "planes", "block_size", "nbytes", "delta", "base_crc", "crc")
 
-    def __init__(self, frame, dtype, shape, planes, block_size, nbytes, delta=False, base_crc=None):
+    def __init__(self, frame, dtype, shape, planes, block_size, nbytes, delta=False, base_crc=None, crc=None):
         self.frame, self.dtype, self.shape, self.planes, self.block_size, self.nbytes = frame, dtype, shape, planes, block_size, nbytes
-        self.delta, self.base_crc = delta, base_crc
+        self.delta, self.base_crc, self.crc = delta, base_crc, crc
 
     def __repr__(self):
         d = f", delta against a base of crc {self.base_crc:#010x}" if self.delta and self.base_crc is not None else (", delta" if self.delta else "")
@@ -712,7 +716,41 @@ def base_crc(raw, lib=None):
     return crc.value
 
 
-def _pack_many(xs, block_size, planes, lib, bases=None):
+def crc32c_tensors(ts, inits=None, lib=None):
+    """base_crc for many tensors in ONE call (bz3_hip_crc32c_device_many: at most two kernel launches whatever their number): the list
+    of the checksums of contiguous torch.uint8 tensors on one GPU, result i exactly base_crc(ts[i]) when inits is None.  `inits`: one
+    start state per tensor (default 1, the codec's).  Tensors of size 0 are allowed and yield their start state; tensors may repeat and
+    overlap.  One device synchronisation per call.  [] returns []."""
+    import torch
+
+    ts = [_device_u8(t, f"ts[{i}]") for i, t in enumerate(ts)]
+    if not ts:
+        return []
+    n = len(ts)
+    if inits is not None:
+        inits = [int(v) for v in inits]
+        if len(inits) != n:
+            raise ValueError(f"crc32c_tensors: {len(inits)} start states for {n} tensors")
+    dev = _same_device(ts, "crc32c_tensors")
+    torch.cuda.synchronize(dev)
+    crcs = (C.c_uint32 * n)()
+    rc = (lib or load()).bz3_hip_crc32c_device_many(n, (C.c_void_p * n)(*[t.data_ptr() if t.numel() else None for t in ts]), (C.c_size_t * n)(*[t.numel() for t in ts]),
+                                                    None if inits is None else (C.c_uint32 * n)(*inits), crcs)
+    if rc != BZ3_OK:
+        raise Bz3Error(rc, "bz3_hip_crc32c_device_many")
+    return list(crcs)
+
+
+def _crcs_where(ts, lib):
+    """crc32c_tensors of the entries of `ts` that are not None, in one call; None for the others."""
+    idx = [i for i, t in enumerate(ts) if t is not None]
+    out = [None] * len(ts)
+    for i, c in zip(idx, crc32c_tensors([ts[i] for i in idx], lib=lib)):
+        out[i] = c
+    return out
+
+
+def _pack_many(xs, block_size, planes, lib, bases=None, checksum=True):
     raws = [_as_bytes(x, f"tensor {i}") for i, x in enumerate(xs)]
     braws = [_base_bytes(b, r.numel(), r.device, f"base {i}") for i, (b, r) in enumerate(zip(_bases_arg(bases, len(xs)), raws))]
     ks = [default_planes(x.dtype) if b is None else delta_default_planes(x.dtype) for x, b in zip(xs, braws)] if planes is None else _planes_arg(planes, len(xs))
@@ -720,11 +758,20 @@ def _pack_many(xs, block_size, planes, lib, bases=None):
     dev = _same_device(raws, "pack")
     L = lib or load()
     frames = _compress_many(L, raws, bss, ks, dev, slack=True, bases=braws)
-    crcs = [None if b is None else base_crc(b, L) for b in braws]
-    return [PackedTensor(f, x.dtype, x.shape, k, bs, r.numel(), b is not None, c) for f, x, k, bs, r, b, c in zip(frames, xs, ks, bss, raws, braws, crcs)]
+    crcs = _crcs_where(braws + (raws if checksum else []), L)  # every base and every content checksum of the call in one batched call
+    own = crcs[len(xs) :] if checksum else [None] * len(xs)
+    return [PackedTensor(f, x.dtype, x.shape, k, bs, r.numel(), b is not None, c, o) for f, x, k, bs, r, b, c, o in zip(frames, xs, ks, bss, raws, braws, crcs, own)]
 
 
-def _unpack_many(ps, outs, lib, bases=None, check_base=True):
+def _check_bases(ps, braws, labels, lib):
+    """ValueError for the first base whose checksum is not its tensor's base_crc: one batched call over all of them."""
+    got = _crcs_where([b if b is not None and p.base_crc is not None else None for p, b in zip(ps, braws)], lib)
+    for p, g, label in zip(ps, got, labels):
+        if g is not None and g != p.base_crc:
+            raise ValueError(f"unpack: base {label} is not the tensor this frame was packed against (its checksum differs)")
+
+
+def _unpack_many(ps, outs, lib, bases=None, check_base=True, verify=False, names=None):
     import torch
 
     for p in ps:
@@ -740,9 +787,7 @@ def _unpack_many(ps, outs, lib, bases=None, check_base=True):
         braws.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {i}"))
     L = lib or load()
     if check_base:  # before anything is decoded or written: the codec cannot tell a wrong base, it would return noise
-        for i, (p, b) in enumerate(zip(ps, braws)):
-            if b is not None and p.base_crc is not None and base_crc(b, L) != p.base_crc:
-                raise ValueError(f"unpack: base {i} is not the tensor this frame was packed against (its checksum differs)")
+        _check_bases(ps, braws, range(len(ps)), L)
     if outs is None:
         dev = _same_device([p.frame for p in ps], "unpack")
         # every output at a multiple of 16 bytes, so that any dtype can view it
@@ -759,10 +804,15 @@ def _unpack_many(ps, outs, lib, bases=None, check_base=True):
     for p, g in zip(ps, got):
         if g.numel() != p.nbytes:
             raise ValueError(f"unpack: the frame decodes to {g.numel()} bytes, the tensor has {p.nbytes}")
+    if verify:  # one batched call over the outputs
+        got = _crcs_where([r if p.crc is not None else None for p, r in zip(ps, raws)], L)
+        for i, (p, g) in enumerate(zip(ps, got)):
+            if g is not None and g != p.crc:
+                raise ValueError(f"unpack: the decoded bytes of tensor {i if names is None else repr(names[i])} do not have the checksum recorded when it was packed")
     return res if res is not None else [_from_bytes(r, p.dtype, p.shape) for r, p in zip(raws, ps)]
 
 
-def pack_tensor(x, block_size=16 << 20, planes=None, lib=None, base=None):
+def pack_tensor(x, block_size=16 << 20, planes=None, lib=None, base=None, checksum=True):
     """Losslessly compresses a GPU tensor of any dtype and shape on its GPU: a PackedTensor whose `.frame` is an ordinary .bz3 frame.
     Non-contiguous input is made contiguous; zero-element and 0-d tensors round-trip; a CPU tensor is a TypeError.  `planes`: the
     byte-plane element size (1, 2, 4 or 8: bz3_hip_compress_device_planes), by default DEFAULT_PLANES for x's dtype.  The block size
@@ -776,17 +826,21 @@ def pack_tensor(x, block_size=16 << 20, planes=None, lib=None, base=None):
     block size 16.48 s + 31.08 s for 0.8610.  The tensors unpack_tensor / unpack_state_dict return are views of one allocation per call.
     `base`: an earlier version of x (a GPU tensor of x's size in bytes on x's GPU; another size or GPU: ValueError, the CPU or no tensor:
     TypeError).  The frame then codes the byte-wise difference from it (bz3_hip_compress_device_delta) and the result records
-    delta=True and the base's checksum; `planes` then defaults to DELTA_PLANES (1 for every dtype but float64).  unpack_tensor needs the same base again."""
-    return _pack_many([x], block_size, None if planes is None else [planes], lib, [base])[0]
+    delta=True and the base's checksum; `planes` then defaults to DELTA_PLANES (1 for every dtype but float64).  unpack_tensor needs the same base again.
+    `checksum`: record the checksum of x's own bytes in the result's `.crc` (one more read of x, in the same batched call as the base's
+    checksum); the frame does not depend on it."""
+    return _pack_many([x], block_size, None if planes is None else [planes], lib, [base], checksum)[0]
 
 
-def unpack_tensor(p, out=None, lib=None, base=None, check_base=True):
+def unpack_tensor(p, out=None, lib=None, base=None, check_base=True, verify=False):
     """The tensor a PackedTensor holds, on the frame's GPU, in `out` if given (a contiguous tensor of p.dtype and p.shape).  Raises
     Bz3Error if the frame does not decode and ValueError if it decodes to another number of bytes than p.nbytes.  A tensor packed
     against a base needs `base` (a GPU tensor, the one it was packed against): ValueError without it, for a base of another size, and, unless
     check_base=False, for one whose checksum is not p.base_crc -- all raised before anything is decoded or written, because decoding
-    against another base returns other bytes and no error.  The check reads the base once.  `out` may be `base`: it is updated in place."""
-    return _unpack_many([p], None if out is None else [out], lib, [base], check_base)[0]
+    against another base returns other bytes and no error.  The check reads the base once.  `out` may be `base`: it is updated in place.
+    `verify`: after decoding, ValueError unless the decoded bytes have the checksum p.crc (skipped where p.crc is None).  That is after
+    the write: with `out` being `base`, the base has been overwritten by then."""
+    return _unpack_many([p], None if out is None else [out], lib, [base], check_base, verify)[0]
 
 
 def _row_bytes(p, what):
@@ -853,14 +907,15 @@ def unpack_tensor_rows(p, start, stop, out=None, base=None, lib=None):
     return _unpack_rows_many([p], [(start, stop)], None if out is None else [out], lib, [base])[0]
 
 
-def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None):
+def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None, checksum=True):
     """pack_tensor for every tensor of a dict, batched: {name: PackedTensor}, each equal to pack_tensor(sd[name], block_size, planes).
     One bz3_hip_compress_device_delta_many call per distinct lossless block size (the C call takes one block size): the tensors whose
     size is no multiple of `block_size` share one call and its windows of up to 256 blocks; those whose block size had to move
     (_lossless_block_size) go in one more call per moved size, typically one or two.  All tensors on one GPU.  `planes`: None
     (DEFAULT_PLANES per dtype; DELTA_PLANES for a tensor packed against a base), an int, or {name: int}.  `base`: a dict of earlier versions (the
     previous checkpoint, the model a fine-tune started from): a tensor whose name is in it with the same dtype and shape is packed
-    against it (pack_tensor's `base`), every other one without a base, all in the same calls."""
+    against it (pack_tensor's `base`), every other one without a base, all in the same calls.  `checksum`: record every tensor's own
+    checksum in its `.crc`; these and the bases' checksums are computed by ONE bz3_hip_crc32c_device_many call per pack call."""
     names = list(sd)
     if isinstance(planes, dict):
         planes = [planes[k] for k in names]
@@ -870,10 +925,10 @@ def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None):
     if base is not None:
         bases = [base.get(k) for k in names]
         bases = [b if b is not None and getattr(b, "dtype", None) == sd[k].dtype and getattr(b, "shape", None) == sd[k].shape else None for k, b in zip(names, bases)]
-    return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib, bases)))
+    return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib, bases, checksum)))
 
 
-def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None):
+def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None, verify=False):
     """The tensors of pack_state_dict's result, decoded in ONE batched call (bz3_hip_decompress_device_delta_many).  `base`: the dict
     pack_state_dict was given; every tensor packed against a base needs its entry (unpack_tensor's rules and check_base).  With
     inplace=True those base tensors themselves are updated and returned (no second copy of the model in memory); tensors packed
@@ -881,9 +936,14 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
     [start, stop) of dimension 0 alone (unpack_tensor_rows), the names not in it whole, all of them through ONE
     bz3_hip_decompress_device_range_many call that decodes only the chunks it needs.  `base` is then the whole base dict as ever: check_base checks
     every base tensor whole against its base_crc (one read of it, for the tensors read by rows too), then their rows are taken here.
-    With inplace=True, ValueError."""
+    With inplace=True, ValueError.  All bases are checked by one batched checksum call, before anything is decoded.  `verify`: after
+    decoding, one more batched call over the outputs and a ValueError that names the first tensor whose bytes do not have its `.crc`
+    (tensors without one are skipped); with inplace=True the bases have been overwritten by then.  With `rows`, ValueError: a checksum
+    of the whole cannot vouch for a slice."""
     names = list(packed)
     if rows is not None:
+        if verify:
+            raise ValueError("unpack_state_dict: verify=True and rows do not go together (the checksum covers the whole tensor)")
         if inplace:
             raise ValueError("unpack_state_dict: rows and inplace=True do not go together")
         unknown = [k for k in rows if k not in packed]
@@ -893,24 +953,26 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
             return {}
         ps = [packed[k] for k in names]
         rws = [rows.get(k) for k in names]
-        bases = []
+        bases, whole = [], []
         L = lib or load()
         for k, p, r in zip(names, ps, rws):
             b = base.get(k) if base is not None and p.delta else None
             # the whole base is at hand here, for the tensors read by rows too: check it as unpack_tensor does, before anything is decoded
             if check_base and b is not None and p.base_crc is not None and getattr(b, "dtype", None) == p.dtype and tuple(b.shape) == tuple(p.shape):
-                if base_crc(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}"), L) != p.base_crc:
-                    raise ValueError(f"unpack: base {k!r} is not the tensor this frame was packed against (its checksum differs)")
+                whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}"))
+            else:
+                whole.append(None)
             if b is not None and r is not None and len(p.shape) and tuple(b.shape) == tuple(p.shape) and 0 <= int(r[0]) <= int(r[1]) <= p.shape[0]:
                 b = b[int(r[0]) : int(r[1])]
             bases.append(b)
+        _check_bases(ps, whole, [repr(k) for k in names], L)
         return dict(zip(names, _unpack_rows_many(ps, rws, None, lib, bases)))
     if not names:
         return {}
     ps = [packed[k] for k in names]
     bases = [base.get(k) if base is not None and p.delta else None for k, p in zip(names, ps)]
     if not inplace or not any(p.delta for p in ps):
-        return dict(zip(names, _unpack_many(ps, None, lib, bases, check_base)))
+        return dict(zip(names, _unpack_many(ps, None, lib, bases, check_base, verify, names)))
     # in place: the delta tensors decode into their bases, the others into new memory; one call
     import torch
 
@@ -923,7 +985,195 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
             raise ValueError(f"unpack: {k} was packed against a base of {p.dtype} {tuple(p.shape)}, which is needed to restore it")
         else:
             outs.append(b)
-    return dict(zip(names, _unpack_many(ps, outs, lib, bases, check_base)))
+    return dict(zip(names, _unpack_many(ps, outs, lib, bases, check_base, verify, names)))
+
+
+# ---- chains of checkpoints ----------------------------------------------------------------------------------------------------
+def check_chain(steps):
+    """Validates a chain of packed dicts (pack_state_dict's results, oldest first) from their metadata alone: no GPU, no frame is read.
+    Step 0 must hold no delta tensor; for every delta tensor of step t + 1, step t must hold that name with the same dtype, shape and
+    nbytes, and its `base_crc` must equal steps[t][name].crc.  ValueError names the first violation (the step and the tensor).  Returns
+    the links that could not be checked because one of the two checksums is None: a list of (t, name), the link from step t to t + 1."""
+    unchecked = []
+    for t, step in enumerate(steps):
+        for name, p in step.items():
+            if not isinstance(p, PackedTensor):
+                raise TypeError(f"check_chain: step {t}: {name!r} is not a PackedTensor")
+            if not p.delta:
+                continue
+            if t == 0:
+                raise ValueError(f"check_chain: step 0: {name!r} is a delta tensor, and there is no step before it")
+            q = steps[t - 1].get(name)
+            if q is None:
+                raise ValueError(f"check_chain: step {t}: {name!r} is a delta tensor, and step {t - 1} does not hold that name")
+            if q.dtype != p.dtype or tuple(q.shape) != tuple(p.shape) or q.nbytes != p.nbytes:
+                raise ValueError(f"check_chain: step {t}: {name!r} is {p.dtype} {tuple(p.shape)} of {p.nbytes} bytes, in step {t - 1} it is {q.dtype} {tuple(q.shape)} of {q.nbytes}")
+            if p.base_crc is None or q.crc is None:
+                unchecked.append((t - 1, name))
+            elif p.base_crc != q.crc:
+                raise ValueError(f"check_chain: step {t}: {name!r} was packed against a base of checksum {p.base_crc:#010x}, in step {t - 1} it has {q.crc:#010x}")
+    return unchecked
+
+
+def unpack_chain(steps, verify=True, lib=None):
+    """The tensors of the last of a chain of packed dicts (a full checkpoint, then deltas, oldest first).  check_chain runs first, so a
+    broken chain fails before anything is decoded.  Step 0 is unpacked whole; every later step is unpacked in place against the result so
+    far with check_base=False: the metadata links and the chunk CRCs of the frames stand in for reading every base again.  Tensors of a
+    step that are not deltas come back in new memory and names a step does not hold are dropped.  `verify` goes to the last step's
+    unpack_state_dict: its outputs are checked against their `.crc`.  An empty chain is a ValueError."""
+    steps = list(steps)
+    if not steps:
+        raise ValueError("unpack_chain: no steps")
+    check_chain(steps)
+    last = len(steps) - 1
+    current = unpack_state_dict(steps[0], lib=lib, verify=verify and last == 0)
+    for t in range(1, len(steps)):
+        current = unpack_state_dict(steps[t], lib=lib, base=current, inplace=True, check_base=False, verify=verify and t == last)
+    return current
+
+
+# ---- checkpoint files ---------------------------------------------------------------------------------------------------------
+# b"BZ3TNSR1" | u64 little-endian H | H bytes of UTF-8 JSON, right-padded with spaces so that 16 + H is a multiple of 64 | the data
+# section: the frames in dict order, each at a multiple of 16 bytes from the section's start, zero padding between (DESIGN.md,
+# "Checkpoint files and batched checksums").  Every frame is an ordinary .bz3 frame.
+PACKED_MAGIC = b"BZ3TNSR1"
+_ENTRY_KEYS = ("dtype", "shape", "planes", "block_size", "nbytes", "delta", "base_crc", "crc", "offset", "size")
+
+
+def _opt_int(v):
+    return None if v is None else int(v)
+
+
+def save_packed(path, packed, metadata=None):
+    """Writes a {name: PackedTensor} dict (pack_state_dict's result) and `metadata` (anything json can serialise; default {}) to one file
+    that load_packed reads back.  The frames may be on any device, the CPU included: those of a GPU are gathered into one buffer there
+    and come to the host in ONE copy.  The file is written as path + ".tmp" and then renamed over `path` (os.replace), so a failed save
+    leaves an existing file as it was."""
+    import json
+
+    import torch
+
+    names = list(packed)
+    entries, offs, o = {}, [], 0
+    for k in names:
+        p = packed[k]
+        if not isinstance(k, str) or not isinstance(p, PackedTensor):
+            raise TypeError("save_packed: a dict of str -> PackedTensor is expected")
+        if not isinstance(p.frame, torch.Tensor) or p.frame.dtype != torch.uint8 or p.frame.dim() != 1:
+            raise TypeError(f"save_packed: the frame of {k!r} must be a one-dimensional torch.uint8 tensor")
+        size = p.frame.numel()
+        entries[k] = {"dtype": str(p.dtype).replace("torch.", ""), "shape": [int(d) for d in p.shape], "planes": int(p.planes), "block_size": int(p.block_size),
+                      "nbytes": int(p.nbytes), "delta": bool(p.delta), "base_crc": _opt_int(p.base_crc), "crc": _opt_int(p.crc), "offset": o, "size": size}
+        offs.append(o)
+        o += (size + 15) & ~15
+    head = json.dumps({"version": 1, "metadata": {} if metadata is None else metadata, "tensors": entries}, ensure_ascii=False).encode("utf-8")
+    head += b" " * ((0 - (16 + len(head))) % 64)
+    host = {}
+    for dev in {packed[k].frame.device for k in names}:
+        mine = [k for k in names if packed[k].frame.device == dev]
+        if dev.type == "cpu":
+            host.update({k: packed[k].frame.contiguous() for k in mine})
+        else:  # one gather on the device, one copy to the host
+            parts = torch.cat([packed[k].frame for k in mine]).cpu().split([packed[k].frame.numel() for k in mine])
+            host.update(dict(zip(mine, parts)))
+    tmp = path + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            f.write(PACKED_MAGIC + len(head).to_bytes(8, "little") + head)
+            at = 0
+            for k, off in zip(names, offs):
+                f.write(b"\0" * (off - at))
+                f.write(memoryview(host[k].numpy()))
+                at = off + host[k].numel()
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def _read_packed_header(f, path):
+    """(entries, metadata, offset of the data section, file size) of an open checkpoint file; ValueError for a malformed header."""
+    import json
+    import math
+
+    import torch
+
+    size = os.fstat(f.fileno()).st_size
+    fixed = f.read(16)
+    if len(fixed) < 16 or fixed[:8] != PACKED_MAGIC:
+        raise ValueError(f"{path}: not a packed tensor file (it does not start with {PACKED_MAGIC!r})")
+    hlen = int.from_bytes(fixed[8:], "little")
+    if 16 + hlen > size:
+        raise ValueError(f"{path}: the header of {hlen} bytes runs past the end of the file")
+    try:
+        head = json.loads(f.read(hlen).decode("utf-8"))
+    except ValueError as e:  # UnicodeDecodeError and json.JSONDecodeError are both ValueErrors
+        raise ValueError(f"{path}: the header is not JSON: {e}") from None
+    if not isinstance(head, dict) or head.get("version") != 1:
+        raise ValueError(f"{path}: version {head.get('version') if isinstance(head, dict) else None!r} of the format, this code reads version 1")
+    entries, metadata = head.get("tensors"), head.get("metadata", {})
+    if not isinstance(entries, dict):
+        raise ValueError(f"{path}: the header holds no tensors")
+    for k, e in entries.items():
+        if not isinstance(e, dict) or any(key not in e for key in _ENTRY_KEYS):
+            raise ValueError(f"{path}: the entry of {k!r} is incomplete")
+        dtype = getattr(torch, e["dtype"], None) if isinstance(e["dtype"], str) else None
+        if not isinstance(dtype, torch.dtype):
+            raise ValueError(f"{path}: {k!r} has the unknown dtype {e['dtype']!r}")
+        if e["planes"] not in (1, 2, 4, 8):
+            raise ValueError(f"{path}: {k!r} has planes = {e['planes']!r}, which must be 1, 2, 4 or 8")
+        if not isinstance(e["shape"], list) or any(not isinstance(d, int) or d < 0 for d in e["shape"]):
+            raise ValueError(f"{path}: {k!r} has the shape {e['shape']!r}")
+        if e["nbytes"] != math.prod(e["shape"]) * torch.empty(0, dtype=dtype).element_size():
+            raise ValueError(f"{path}: {k!r} has nbytes = {e['nbytes']!r}, which is not what {e['dtype']} {e['shape']} holds")
+        if any(not isinstance(e[key], int) or isinstance(e[key], bool) or e[key] < 0 for key in ("offset", "size", "block_size")):
+            raise ValueError(f"{path}: {k!r} has a bad offset, size or block size")
+    return entries, metadata, 16 + hlen, size
+
+
+def packed_index(path):
+    """(entries, metadata) of a file save_packed wrote, from its header alone (no frame is read): entries is {name: {"dtype", "shape",
+    "planes", "block_size", "nbytes", "delta", "base_crc", "crc", "offset", "size"}} as the format holds them.  ValueError for a
+    malformed header."""
+    with open(path, "rb") as f:
+        entries, metadata, _, _ = _read_packed_header(f, path)
+    return entries, metadata
+
+
+def load_packed(path, device, names=None):
+    """The {name: PackedTensor} dict a file of save_packed holds, with the frames on `device` (a GPU or "cpu"), ready for
+    unpack_state_dict / unpack_chain.  `names`: load these tensors alone, in this order (a name the file does not hold: KeyError); only
+    their byte ranges are read, into one host buffer that goes to the device in ONE copy; the frames are views of that copy, each at a
+    multiple of 16 bytes.  ValueError for a malformed header and for a selected frame that runs past the end of the file; a corrupt frame
+    body is found by the decoder (Bz3Error from unpack_*), not here."""
+    import torch
+
+    with open(path, "rb") as f:
+        entries, _, data_at, size = _read_packed_header(f, path)
+        names = list(entries) if names is None else list(names)
+        for k in names:
+            if k not in entries:
+                raise KeyError(k)
+            if data_at + entries[k]["offset"] + entries[k]["size"] > size:
+                raise ValueError(f"{path}: the frame of {k!r} runs past the end of the file")
+        offs, o = [], 0
+        for k in names:
+            offs.append(o)
+            o += (entries[k]["size"] + 15) & ~15
+        host = torch.zeros(max(o, 1), dtype=torch.uint8)
+        view = memoryview(host.numpy())
+        for k, a in zip(names, offs):
+            f.seek(data_at + entries[k]["offset"])
+            if f.readinto(view[a : a + entries[k]["size"]]) != entries[k]["size"]:
+                raise ValueError(f"{path}: the frame of {k!r} could not be read whole")
+    buf = host.to(device)
+    out = {}
+    for k, a in zip(names, offs):
+        e = entries[k]
+        out[k] = PackedTensor(buf[a : a + e["size"]], getattr(torch, e["dtype"]), torch.Size(e["shape"]), e["planes"], e["block_size"], e["nbytes"], bool(e["delta"]),
+                              e["base_crc"], e["crc"])
+    return out
 
 
 def shard_blocks(n_blocks, world_size, rank):

@@ -250,6 +250,7 @@ std::atomic<int> g_lean{-1};  // -1 = not read from the environment yet; see bz3
 std::atomic<int> g_front_end_ring{0};  // window | slots << 16 of the last encode_group (bz3_hip_debug_front_end_ring)
 std::atomic<int> g_arena_swaps{0};  // swap buffers served from the arena (bz3_hip_debug_arena_swap_buffers)
 std::atomic<unsigned> g_cm_given_up{0};  // blocks the row-cache CM kernels handed back to the full-model kernels (statistics)
+std::atomic<unsigned> g_crc_launches{0};  // kernels launched by bz3_hip_crc32c_device_many (statistics, bz3_hip_debug_crc_launches)
 std::atomic<unsigned> g_cm_launches{0};  // CM kernel launches (statistics, bz3_hip_debug_cm_launches)
 std::atomic<unsigned> g_cm_routed_full{0};  // blocks sent straight to the full-model kernels by their histogram / payload size (statistics)
 
@@ -3156,53 +3157,63 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
     return rc;
 }
 
-// The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state `init`, no inversion) over n bytes of device memory: crc32c_device on a
-// caller's buffer.  Its kernels read dwords, so the up to three bytes before the first 4-byte boundary are fetched and folded in on the host.
-BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc) {
-    if (!crc) return BZ3_ERR_INIT;
-    if (!n) {
-        *crc = init;
+// The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state init, no inversion) of n buffers in device memory of one GPU, at any
+// alignment: crc32c_device_many (crc32c.hip) on the callers' buffers.  Per call one stream, one allocation (the table, then the n result
+// words), one table upload, one memset, at most two launches and one read-back, whatever n is.
+BZIP3_API int bz3_hip_crc32c_device_many(int32_t n, const void * const * ptrs, const size_t * sizes, const uint32_t * inits, uint32_t * crcs) {
+    if (n < 0 || (n > 0 && (!ptrs || !sizes || !crcs))) return BZ3_ERR_INIT;
+    if (n == 0) return BZ3_OK;
+    int dev = -1;
+    u64 total_seg = 0;
+    std::vector<CrcBuf> tab((size_t)n);
+    for (s32 i = 0; i < n; i++) {
+        tab[(size_t)i] = {sizes[i] ? dev_addr(ptrs[i]) : 0, (u64)sizes[i], inits ? inits[i] : 1u, (u32)total_seg};
+        if (!sizes[i]) continue;
+        const int d = device_of(ptrs[i]);
+        if (d < 0 || (dev >= 0 && d != dev)) return BZ3_ERR_INIT;
+        dev = d;
+        total_seg += crc_many_segments(ptrs[i], (u64)sizes[i]);
+        if (total_seg >= ((u64)1 << 31)) return BZ3_ERR_INIT;  // 32 TiB in one call
+    }
+    if (dev < 0) {  // nothing but empty buffers: no GPU is needed
+        for (s32 i = 0; i < n; i++) crcs[i] = tab[(size_t)i].init;
         return BZ3_OK;
     }
-    const int dev = device_of(p);
     DeviceCtx * ctx = nullptr;
     try {
-        ctx = dev < 0 ? nullptr : get_ctx(dev);
+        ctx = get_ctx(dev);
     } catch (...) {
         ctx = nullptr;
     }
     if (!ctx) return BZ3_ERR_INIT;
     hipStream_t s = nullptr;
-    u32 * d_words = nullptr;
+    u8 * d_mem = nullptr;
     int rc = BZ3_OK;
     try {
         DeviceGuard g(dev);
+        const size_t tab_bytes = align256((size_t)n * sizeof(CrcBuf));
+        std::vector<u32> got((size_t)n);
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_CHECK(hipMalloc((void **)&d_words, 64));
-        const u8 * d = (const u8 *)p;
-        const size_t head = std::min(n, (size_t)((0 - (u64)d) & 3));
-        u32 reg = init;
-        if (head) {
-            u8 h[4] = {0};
-            HIP_CHECK(hipMemcpyAsync(h, d, head, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            for (size_t i = 0; i < head; i++) {
-                reg ^= h[i];
-                for (int k = 0; k < 8; k++) reg = (reg >> 1) ^ (0x82F63B78u & (0u - (reg & 1u)));
-            }
-        }
-        if (n > head) {
-            crc32c_device(d + head, (u64)(n - head), reg, ctx->d_crc, d_words, s);
-            reg = read_word(s, d_words + 1);
-        }
-        *crc = reg;
+        HIP_CHECK(hipMalloc((void **)&d_mem, tab_bytes + (size_t)n * sizeof(u32)));
+        HIP_CHECK(hipMemcpyAsync(d_mem, tab.data(), (size_t)n * sizeof(CrcBuf), hipMemcpyHostToDevice, s));
+        g_crc_launches += crc32c_device_many((const CrcBuf *)d_mem, (u32)n, (u32)total_seg, ctx->d_crc, (u32 *)(d_mem + tab_bytes), s);
+        HIP_CHECK(hipMemcpyAsync(got.data(), d_mem + tab_bytes, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        memcpy(crcs, got.data(), (size_t)n * sizeof(u32));  // nothing is written unless the whole call succeeded
     } catch (...) {
         rc = BZ3_ERR_INIT;
     }
     if (s) (void)hipStreamSynchronize(s);
-    if (d_words) (void)hipFree(d_words);
+    if (d_mem) (void)hipFree(d_mem);
     if (s) (void)hipStreamDestroy(s);
     return rc;
+}
+
+BZIP3_API unsigned bz3_hip_debug_crc_launches(int reset) { return reset ? g_crc_launches.exchange(0) : g_crc_launches.load(); }
+
+// One buffer: the n = 1 case of the call above.
+BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc) {
+    return bz3_hip_crc32c_device_many(1, &p, &n, &init, crc);
 }
 
 // ---- bz3_hip.h: device control, timings ----------------------------------------------------------------

@@ -9,6 +9,8 @@
 // xor-reduced across the wave, shifted to the end of the message by x^e (e assembled from a table of
 // x^(2^b) with a 6-step cross-lane multiply-reduce) and xor-ed into one accumulator word.
 // No lookup tables in LDS, no serial dependency across lanes.  Traffic: 1 byte read per input byte.
+#include <algorithm>
+
 #include "prims.hpp"
 #include "stages.hpp"
 
@@ -107,6 +109,94 @@ void crc32c_device(const u8 * d_data, u64 n, u32 init, const CrcTables * d_table
                d_tables, d_scratch);
     }
     launch(k_crc_finish, dim3(1), dim3(64), 0, s, d_data, n, main_bytes, init, d_tables, d_scratch, d_scratch + 1);
+}
+
+// ---- many buffers in one pass (bz3_hip_crc32c_device_many) ------------------------------------------------------------------
+// Every buffer is cut as above from its first 4-byte boundary on: `head` bytes (0-3) before it, then whole 16 KiB segments, whole
+// 256-byte rows, a byte tail.  The segments of all buffers form one list (CrcBuf::first_seg is the exclusive prefix sum); one wave
+// owns one segment of it, finds its buffer by binary search over the prefix sums and xors its share into that buffer's word of
+// `crcs`.  A second launch, one wave per buffer, adds what is left and leaves the checksum in crcs[i].  No load falls outside
+// [ptr, ptr + size) of any buffer and nothing but `crcs` is written.
+__device__ __forceinline__ u32 crc_head_bytes(u64 ptr, u64 size) {
+    const u64 h = (0 - ptr) & 3;
+    return (u32)(h < size ? h : size);
+}
+
+__global__ void __launch_bounds__(256) k_crc_many_segments(const CrcBuf * __restrict__ bufs, u32 n, u32 total_seg,
+                                                          const CrcTables * __restrict__ t, u32 * __restrict__ crcs) {
+    const u32 g = blockIdx.x * (blockDim.x / WAVE) + wave_id();
+    if (g >= total_seg) return;  // wave-uniform exit
+    u32 lo = 0, hi = n;          // the last buffer whose first segment is <= g (buffers without segments share their successor's)
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (bufs[mid].first_seg <= g) lo = mid;
+        else hi = mid;
+    }
+    const CrcBuf b = bufs[lo];
+    const u32 head = crc_head_bytes(b.ptr, b.size);
+    const u64 body = b.size - head;
+    const u64 nseg = body / (CRC_SEG_WORDS * 4);
+    const u64 l = g - b.first_seg;
+    u32 seg = crc_fold_rows(global_ptr<const u32>(b.ptr + head), l * CRC_SEG_WORDS, CRC_ROWS, t);
+    // shift to the end of the buffer: the later segments, the rows and bytes behind them, and the 32 of U()
+    const u64 e = ((nseg - 1 - l) * CRC_SEG_WORDS * 4 + (body - nseg * CRC_SEG_WORDS * 4)) * 8ull + 32ull;
+    seg = gf_mul(seg, gf_xpow(e, t->pow2));
+    if (lane_id() == 0) atomicXor(crcs + lo, seg);
+}
+
+__global__ void __launch_bounds__(256) k_crc_many_finish(const CrcBuf * __restrict__ bufs, u32 n, const CrcTables * __restrict__ t,
+                                                        u32 * __restrict__ crcs) {
+    const u32 i = blockIdx.x * (blockDim.x / WAVE) + wave_id();
+    if (i >= n) return;  // wave-uniform exit
+    const CrcBuf b = bufs[i];
+    if (b.size == 0) {  // its pointer is never dereferenced
+        if (lane_id() == 0) crcs[i] = b.init;
+        return;
+    }
+    const u8 * data = global_ptr<const u8>(b.ptr);
+    const u32 head = crc_head_bytes(b.ptr, b.size);
+    u32 reg = b.init;
+    if (lane_id() == 0) {
+        for (u32 k = 0; k < head; k++) {
+            reg ^= data[k];
+#pragma unroll
+            for (int j = 0; j < 8; j++) reg = (reg >> 1) ^ (CRC_POLY & (0u - (reg & 1u)));
+        }
+    }
+    reg = __shfl(reg, 0);  // the init of the rest
+    data += head;
+    const u64 body = b.size - head;
+    const u64 main_bytes = body / (CRC_SEG_WORDS * 4) * (CRC_SEG_WORDS * 4);
+    const u64 rest = body - main_bytes;
+    const int rows = (int)(rest / 256);
+    u32 state = crcs[i] ^ gf_mul(reg, gf_xpow(body * 8ull, t->pow2));
+    if (rows > 0) {
+        u32 part = crc_fold_rows(reinterpret_cast<const u32 *>(data), main_bytes / 4, rows, t);
+        part = gf_mul(part, gf_xpow((rest - (u64)rows * 256) * 8ull + 32ull, t->pow2));
+        state ^= part;
+    }
+    if (lane_id() == 0) {  // the byte tail, as in k_crc_finish
+        u32 tail = 0;
+        for (u64 k = main_bytes + (u64)rows * 256; k < body; k++) {
+            tail ^= data[k];
+#pragma unroll
+            for (int j = 0; j < 8; j++) tail = (tail >> 1) ^ (CRC_POLY & (0u - (tail & 1u)));
+        }
+        crcs[i] = state ^ tail;
+    }
+}
+
+u64 crc_many_segments(const void * ptr, u64 size) {
+    const u64 head = std::min<u64>(size, (0 - (u64)(uintptr_t)ptr) & 3);
+    return (size - head) / (CRC_SEG_WORDS * 4);
+}
+
+unsigned crc32c_device_many(const CrcBuf * d_bufs, u32 n, u32 total_seg, const CrcTables * d_tables, u32 * d_crcs, hipStream_t s) {
+    if (!n) return 0;
+    HIP_CHECK(hipMemsetAsync(d_crcs, 0, (size_t)n * sizeof(u32), s));
+    if (total_seg) launch(k_crc_many_segments, dim3((total_seg + 3) / 4), dim3(256), 0, s, d_bufs, n, total_seg, d_tables, d_crcs);
+    launch(k_crc_many_finish, dim3((n + 3) / 4), dim3(256), 0, s, d_bufs, n, d_tables, d_crcs);
+    return total_seg ? 2 : 1;
 }
 
 }  // namespace bz3

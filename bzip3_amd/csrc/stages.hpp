@@ -17,6 +17,18 @@ struct CrcTables {
 void crc_build_tables(CrcTables & t);  // host
 // Result is left in d_scratch[1] (d_scratch: 2 words).
 void crc32c_device(const u8 * d_data, u64 n, u32 init, const CrcTables * d_tables, u32 * d_scratch, hipStream_t s);
+// The same checksum of n buffers at any alignment in at most two launches (bz3_hip_crc32c_device_many).  d_bufs: one CrcBuf per
+// buffer, first_seg the exclusive prefix sum of crc_many_segments() over the buffers and total_seg its total; a buffer of size 0
+// is never dereferenced.  Leaves buffer i's checksum in d_crcs[i] (n words, which the call zeroes first) and returns the number of
+// kernels it launched.  Asynchronous.
+struct CrcBuf {
+    u64 ptr;  // device address as an integer: see prims.hpp global_ptr()
+    u64 size;
+    u32 init;
+    u32 first_seg;
+};
+u64 crc_many_segments(const void * ptr, u64 size);  // host: the 16 KiB segments of a buffer, cut from its first 4-byte boundary on
+unsigned crc32c_device_many(const CrcBuf * d_bufs, u32 n, u32 total_seg, const CrcTables * d_tables, u32 * d_crcs, hipStream_t s);
 
 // ---- mRLE (mrle.hip) -- replaces mrlec / mrled, src/libbz3.c:264-329 -------------------------
 struct MrleEncScratch {

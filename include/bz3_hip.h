@@ -204,6 +204,16 @@ BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t ele
  * of device memory at any alignment, computed on the GPU that owns them.  Returns BZ3_OK with the value in *crc (n == 0: init), or
  * BZ3_ERR_INIT for a pointer that is not device memory.  Synchronous. */
 BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc);
+/* The same checksum of n buffers in ONE pass: crcs[i] is exactly what bz3_hip_crc32c_device(ptrs[i], sizes[i], init_i, &c) returns, with
+ * init_i = inits[i], or 1 (the codec's) for every buffer when inits == NULL.  The buffers may repeat, overlap and have any alignment; a
+ * buffer of size 0 yields its init and its pointer, which may be NULL, is never looked at.  All non-empty buffers are device memory of ONE
+ * GPU, that of the first non-empty one, and the call runs there.  No byte outside [ptrs[i], ptrs[i] + sizes[i]) of any buffer is read and
+ * nothing is written to the buffers.  Per call: one upload of a table of n entries, at most two kernel launches and one read-back of n
+ * words, whatever n is (the single call above is the n = 1 case).  Returns BZ3_OK (also for n == 0), or BZ3_ERR_INIT before anything is
+ * written to crcs: n < 0; ptrs, sizes or crcs NULL with n > 0; a non-empty buffer that is not device memory of that GPU; more than 32 TiB
+ * in one call.  Synchronous. */
+BZIP3_API int bz3_hip_crc32c_device_many(int32_t n, const void * const * ptrs, const size_t * sizes, const uint32_t * inits, uint32_t * crcs);
+BZIP3_API unsigned bz3_hip_debug_crc_launches(int reset); /* statistics: kernels launched by bz3_hip_crc32c_device[_many] since the last reset */
 /* Test hook: bz3_hip_debug_planes with a base: n (src_off, base_off, dst_off, len, elem_size | inverse << 8) quintuples (host array of
  * 5 n u64) relative to `src` / `base` / `dst`; base_off = UINT64_MAX: the segment has no base.  A segment with a base stores
  * split_k(src - base) (inverse 0) or merge_k(src) + base (inverse 1), the base paired with the interleaved side.  `dst` may be `base`
