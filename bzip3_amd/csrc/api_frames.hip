@@ -1,0 +1,1026 @@
+// api_frames.hip -- the device-resident frame API of include/bz3_hip.h (plain, byte planes, delta, range, decoded sizes), its debug entry
+// points and the batched CRC.  The only unit that includes frame.hpp and planes.hpp: their kernels are ordinary definitions.
+#include "api_internal.hpp"
+#include "frame.hpp"
+#include "planes.hpp"
+
+using namespace bz3;
+using namespace bz3::api;
+
+extern "C" {
+
+// ---- device-resident frames (bz3_hip.h: bz3_hip_compress_device[_many] / bz3_hip_decompress_device[_many]) -------------------
+// The frame API above with `in` and `out` in HBM of one GPU, for one frame or many in one call (the single-frame entry
+// points are the n = 1 case).  A window of up to 256 blocks at a time, taken in frame order across frame boundaries: one
+// state per block on the buffers' device and one slab of slots; every move between the caller's buffers and the slots is
+// ONE launch of k_copy_segments (frame.hpp), frame and chunk headers travel as extra segments from a small staged buffer,
+// and on decode the chunk headers of all frames are walked on the device (k_frame_walk_many, one lane per frame) and read
+// back once per window.  The _planes entry points give every frame an element size: its blocks are split into byte planes on
+// the way into their slots and merged on the way out (planes.hpp), in the same launches; elem_sizes == nullptr is 1 everywhere.
+// The _delta entry points give a frame a base of the size of its input as well: a block's segment carries the address of the base bytes
+// that pair with it, which the same launch subtracts before the split and adds after the merge; bases == nullptr is no base anywhere.
+namespace {
+
+// The device that owns `p` if it is device memory, else -1.  (The emulator's device memory is host memory, on device 0.)
+int device_of(const void * p) {
+    if (!p) return -1;
+#ifdef BZ3_EMU
+    return 0;
+#else
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return a.type == hipMemoryTypeDevice ? a.device : -1;
+#endif
+}
+
+// Device tables of one k_copy_segments launch: the segments, then the nseg + 1 tile starts.
+constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg) + 15) & ~(size_t)15) + (nseg + 1) * sizeof(u32); }
+
+// The same for a launch that may hold clipped merges (planes.hpp k_range_segments): behind the tables above, 16-byte aligned, the
+// [a, b) of every segment (two u64 each).
+constexpr size_t range_table_bytes(size_t nseg) { return ((copy_table_bytes(nseg) + 15) & ~(size_t)15) + nseg * 2 * sizeof(u64); }
+
+// Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
+// The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
+// clips (or nullptr): two u64 per segment, the [a, b) of the segments with PLANES_CLIP; d_tab then holds range_table_bytes(segs.size())
+// bytes, and a launch with such a segment goes to k_range_segments.
+void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr) {
+    const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
+    if (clips && clips->size() != 2 * n) throw std::length_error("one clip per segment");
+    staging.assign(clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
+    if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
+    u32 * starts = (u32 *)(staging.data() + seg_bytes);
+    u64 tiles = 0;
+    bool planes = false, delta = false, clip = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
+    for (size_t i = 0; i < n; i++) {
+        starts[i] = (u32)tiles;
+        if (segs[i].mode & PLANES_CLIP) {
+            if (!clips) throw std::length_error("a clipped segment without its clip");
+            tiles += clip_tiles(segs[i].len, segs[i].mode & 0xff, (*clips)[2 * i], (*clips)[2 * i + 1]);
+            clip = true;
+        } else {
+            tiles += segment_tiles(segs[i]);
+        }
+        planes |= (segs[i].mode & 0xff) > 1;
+        delta |= segs[i].base != 0;
+    }
+    if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
+    starts[n] = (u32)tiles;
+    if (!tiles) return;
+    const size_t clip_off = range_table_bytes(n) - n * 2 * sizeof(u64);
+    if (clip) memcpy(staging.data() + clip_off, clips->data(), n * 2 * sizeof(u64));
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), clip ? staging.size() : copy_table_bytes(n), hipMemcpyHostToDevice, s));
+    if (clip)
+        launch(k_range_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off));
+    else
+        launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
+}
+
+// The gather segment of chunk bytes [a, b) of a decoded chunk of s bytes in `slot`, element size k, to dst (and base, or 0), which
+// address the clip's first byte: a whole chunk and every k = 1 clip are ordinary segments, the rest clipped merges (planes.hpp).
+void push_range_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, u64 slot, u64 s, u64 k, u64 a, u64 b, u64 dst, u64 base) {
+    const bool plain = k <= 1 || a == b || (a == 0 && b == s);
+    if (plain) segs.push_back({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
+    else segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base});
+    clips.push_back(plain ? 0 : a);
+    clips.push_back(plain ? 0 : b);
+}
+
+constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
+constexpr size_t WALK_RECORDS = 4096;     // chunk records of one walk (bz3_hip_frame_decoded_sizes_device; a window's walk takes at most FRAME_WINDOW_MAX)
+static_assert(WALK_RECORDS >= FRAME_WINDOW_MAX, "a window's walk must fit the records");
+
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Layout of a call's small device buffer, sized for its n frames: staged headers (one 13-byte frame header per frame and one
+// 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
+// header; with room for their clips), the walk's arguments, records and tails.
+struct MetaLayout {
+    size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, bytes = 0;
+    MetaLayout() = default;
+    explicit MetaLayout(size_t frames) : n(frames) {
+        tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
+        args = tab + align256(range_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        rec = args + align256(n * sizeof(WalkArg));
+        tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
+        bytes = tails + align256(n * sizeof(WalkTail));
+    }
+};
+
+// Blocks per window: FRAME_WINDOW_MAX, or fewer under BZ3_HIP_FRAME_WINDOW (tests: windows that cut through frames).
+size_t frame_window_limit() {
+    size_t limit = FRAME_WINDOW_MAX;
+    if (const char * e = getenv("BZ3_HIP_FRAME_WINDOW"))
+        if (atoi(e) > 0 && (size_t)atoi(e) < limit) limit = (size_t)atoi(e);
+    return limit;
+}
+
+// The device, stream, states, slab and small buffer of one call over n frames.
+struct DeviceFrames {
+    int device = -1;
+    hipStream_t s = nullptr;  // the lead state's stream (its own for the walks before the states exist)
+    bool own_stream = false;
+    u8 * meta = nullptr;
+    MetaLayout lay;
+    u8 * slab = nullptr;
+    size_t stride = 0;
+    std::vector<bz3_state *> states;
+    std::vector<CopySeg> segs;
+    std::vector<u64> clips;  // empty, or the [a, b) of every segment of `segs` (a range call's gather)
+    std::vector<u8> staging;
+    ~DeviceFrames() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        if (s) (void)hipStreamSynchronize(s);
+        for (bz3_state * st : states) state_release(st);
+        if (slab) (void)hipFree(slab);
+        if (meta) (void)hipFree(meta);
+        if (own_stream && s) (void)hipStreamDestroy(s);
+    }
+    bool open(int dev, size_t n) {  // the device, a stream and the small buffer
+        if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
+        device = dev;
+        lay = MetaLayout(n);
+        HIP_CHECK(hipSetDevice(dev));
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        own_stream = true;
+        HIP_CHECK(hipMalloc((void **)&meta, lay.bytes));
+        return true;
+    }
+    // Up to `want` states of block_size (the call's largest) on the device and a slab of as many slots, within the memory the
+    // headroom rule leaves; at least one or false.
+    bool init(u32 block_size, size_t want) {
+        size_t limit = frame_window_limit();
+        const size_t cap = (bz3_bound(block_size) + 4096 + 255) & ~(size_t)255;  // a state's cap (new_state_on)
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            // per block: a slot and a swap buffer (owned or borrowed); beside them the headroom, the stages' workspace and two LZP contexts
+            const size_t fixed = ws_headroom() + workspace_bytes_for((u64)block_size + 64) + 2 * lzp_encode_ctx_bytes((u64)block_size + 128) + ((size_t)64 << 20);
+            const size_t by_mem = free_b > fixed ? (free_b - fixed) / (2 * cap) : 0;
+            if (by_mem < limit) limit = by_mem;
+        }
+        if (want > limit) want = limit;
+        if (want < 1) want = 1;
+        for (size_t i = 0; i < want; i++) {
+            bz3_state * st = new_state_on((int32_t)block_size, device);
+            if (!st) break;
+            states.push_back(st);
+        }
+        while (!states.empty()) {
+            if (hipMalloc((void **)&slab, states.size() * cap) == hipSuccess) break;
+            (void)hipGetLastError();
+            slab = nullptr;
+            const size_t keep = states.size() / 2;
+            while (states.size() > keep) {
+                state_release(states.back());
+                states.pop_back();
+            }
+        }
+        if (states.empty()) return false;
+        stride = cap;
+        HIP_CHECK(hipSetDevice(device));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipStreamDestroy(s));
+        own_stream = false;
+        s = states[0]->stream;
+        return true;
+    }
+    u8 * slot(size_t k) const { return slab + k * stride; }
+    void copy() {  // the segments collected in `segs`, one launch, complete on return
+        if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
+        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips);
+        HIP_CHECK(hipStreamSynchronize(s));
+        segs.clear();
+        clips.clear();
+    }
+    void stage_headers(const std::vector<u8> & h) {
+        if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
+        if (!h.empty()) HIP_CHECK(hipMemcpyAsync(meta + lay.hdr, h.data(), h.size(), hipMemcpyHostToDevice, s));
+    }
+    // One launch of k_frame_walk_many over args.size() frames and one read-back: tails[q] is frame q's resume state, its
+    // records are rec[args[q].rec_base ..].
+    void walk(const std::vector<WalkArg> & args, std::vector<WalkChunk> & rec, std::vector<WalkTail> & tails) {
+        const size_t n = args.size();
+        size_t nrec = 0;
+        for (const WalkArg & a : args) nrec = std::max(nrec, (size_t)a.rec_base + a.limit);
+        if (n > lay.n || nrec > WALK_RECORDS) throw std::length_error("walk larger than its buffer");
+        tails.resize(n);
+        rec.resize(nrec);
+        if (!n) return;
+        HIP_CHECK(hipMemcpyAsync(meta + lay.args, args.data(), n * sizeof(WalkArg), hipMemcpyHostToDevice, s));
+        launch(k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s, (const WalkArg *)(meta + lay.args), (u32)n,
+               (WalkChunk *)(meta + lay.rec), (WalkTail *)(meta + lay.tails));
+        if (nrec) HIP_CHECK(hipMemcpyAsync(rec.data(), meta + lay.rec, nrec * sizeof(WalkChunk), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(tails.data(), meta + lay.tails, n * sizeof(WalkTail), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    }
+};
+
+// Where a frame's walk stands: (off, planned, done) resume it; off == 0 before its header was read.
+struct WalkPos {
+    u64 off = 0, planned = 0;
+    u32 done = 0, block_size = 0, n_blocks = 0;
+    WalkArg arg(const u8 * in, size_t in_size, size_t buf_max, u32 limit, u32 rec_base) const {
+        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0, 0, 0};
+    }
+    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base) const {  // the chunks that hold a byte of [lo, hi)
+        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi};
+    }
+    void take(const WalkTail & t) {
+        off = t.off;
+        planned = t.planned;
+        done = t.done;
+        block_size = t.block_size;
+        n_blocks = t.n_blocks;
+    }
+};
+
+// The frame headers of the frames with live[i]: one walk with limit 0.  A frame with a bad header gets its code in rcs and
+// leaves `live`.
+void walk_frame_headers(DeviceFrames & f, s32 n, const u8 * const * ins, const size_t * in_sizes, std::vector<WalkPos> & pos, std::vector<char> & live, int * rcs) {
+    std::vector<WalkArg> args;
+    std::vector<s32> who;
+    for (s32 i = 0; i < n; i++)
+        if (live[i]) {
+            args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, 0, 0));
+            who.push_back(i);
+        }
+    std::vector<WalkChunk> rec;
+    std::vector<WalkTail> tails;
+    f.walk(args, rec, tails);
+    for (size_t q = 0; q < who.size(); q++) {
+        const s32 i = who[q];
+        if (tails[q].err != BZ3_OK) {
+            rcs[i] = tails[q].err;
+            live[i] = 0;
+        } else {
+            pos[i].take(tails[q]);
+        }
+    }
+}
+
+// ---- compress: n frames whose buffers passed the pointer checks, on device dev --------------------------------------------
+// Blocks go through windows in frame order, across frame boundaries: scatter (one copy launch), run_encode (one CM launch
+// for the window's blocks of all frames), pack (the frame headers of the frames that start in the window, the chunk headers
+// and the coded slots: one copy launch).  Every frame keeps its own output position and error.
+// bases (or nullptr): per frame nullptr, or in_sizes[i] bytes the frame is coded against; block j pairs with base bytes [j bs, j bs + len_j).
+void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes, const u8 * const * ins, const u8 * const * bases, const size_t * in_sizes,
+                     u8 * const * outs, size_t * out_sizes, int * rcs) {
+    struct Frame {
+        u32 bs = 0, nb = 0, next = 0;  // effective block size, blocks, next block to scatter
+        size_t pos = 0, buf_max = 0;   // bytes written, capacity
+        bool live = false, started = false, fin = false;
+    };
+    std::vector<Frame> fr((size_t)n);
+    u32 bs_max = 0;
+    u64 total = 0;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        Frame & x = fr[i];
+        const size_t in_size = in_sizes[i];
+        u32 bs = block_size_arg;
+        if (bs > in_size) bs = (u32)bz3_bound(in_size);  // :877
+        x.bs = bs <= (u32)KiB65 ? (u32)KiB65 : bs;
+        x.nb = (u32)(in_size / x.bs);
+        if (in_size % x.bs) x.nb++;
+        if (x.bs > (u32)MiB511) {  // :879-886 (bz3_new)
+            rcs[i] = BZ3_ERR_INIT;
+            continue;
+        }
+        x.live = true;
+        bs_max = std::max(bs_max, x.bs);
+        total += x.nb;
+    }
+    if (!bs_max) return;
+    DeviceFrames f;
+    bool ok = false;
+    try {
+        ok = f.open(dev, (size_t)n) && f.init(bs_max, (size_t)std::min<u64>(total, FRAME_WINDOW_MAX));
+    } catch (...) {
+        ok = false;
+    }
+    for (s32 i = 0; i < n; i++) {
+        Frame & x = fr[i];
+        if (!x.live) continue;
+        if (!ok) {
+            rcs[i] = BZ3_ERR_INIT;
+            x.live = false;
+            continue;
+        }
+        x.buf_max = out_sizes[i];
+        out_sizes[i] = 0;
+        if (x.buf_max < 13 || x.buf_max < bz3_bound(in_sizes[i])) {  // (bz3_bound(in_size) covers the frame, so no chunk overflows it later)
+            rcs[i] = BZ3_ERR_DATA_TOO_BIG;
+            x.live = false;
+        }
+    }
+    if (!ok) return;
+    try {
+        DeviceGuard g(dev);
+        const u32 W = (u32)f.states.size();
+        std::vector<s32> sizes(W), orig(W), owner(W);
+        std::vector<void *> slots(W);
+        std::vector<s32> heads, touched;
+        std::vector<u8> hdr;
+        s32 cur = 0;  // frames before it are finished
+        for (;;) {
+            while (cur < n && (!fr[cur].live || fr[cur].fin)) cur++;
+            if (cur == n) break;
+            // scatter: the next W blocks in frame order, block k to slot k
+            u32 cnt = 0;
+            heads.clear();
+            touched.clear();
+            for (s32 i = cur; i < n && cnt < W; i++) {
+                Frame & x = fr[i];
+                if (!x.live || x.fin) continue;
+                if (!x.started) heads.push_back(i);
+                touched.push_back(i);
+                for (; x.next < x.nb && cnt < W; x.next++, cnt++) {
+                    s32 size = (s32)x.bs;
+                    if (x.next == x.nb - 1) size = (s32)(in_sizes[i] % x.bs);  // (sic) :914 -- 0 when in_size is a multiple
+                    sizes[cnt] = orig[cnt] = size;
+                    owner[cnt] = i;
+                    slots[cnt] = f.slot(cnt);
+                    f.states[cnt]->block_size = (s32)x.bs;  // every check of the block is made against its own frame's block size
+                    f.states[cnt]->last_error = BZ3_OK;
+                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0,
+                                      bases && bases[i] ? (u64)(bases[i] + (size_t)x.next * x.bs) : 0});
+                }
+            }
+            if (cnt) {
+                f.copy();
+                run_encode(f.states.data(), slots.data(), sizes.data(), (s32)cnt, false);
+            }
+            // pack: frame headers, chunk headers from the staged buffer, the coded slots behind them
+            hdr.clear();
+            for (s32 i : heads) {
+                Frame & x = fr[i];
+                const size_t h = hdr.size();
+                hdr.insert(hdr.end(), {'B', 'Z', '3', 'v', '1'});
+                hdr.resize(h + 13);
+                wr_le32(hdr.data() + h + 5, x.bs);
+                wr_le32(hdr.data() + h + 9, x.nb);
+                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)outs[i], 13});
+                x.pos = 13;
+                x.started = true;
+            }
+            for (u32 k = 0; k < cnt; k++) {
+                const s32 i = owner[k];
+                Frame & x = fr[i];
+                if (!x.live) continue;  // an earlier block of its frame failed in this window
+                if (bz3_last_error(f.states[k]) != BZ3_OK) {  // :917-922
+                    rcs[i] = f.states[k]->last_error;
+                    x.live = false;
+                    continue;
+                }
+                const s32 osz = sizes[k];
+                if (osz < 0 || x.pos + 8 + (size_t)osz > x.buf_max) {  // (never taken: bz3_bound(in_size) covers the frame)
+                    rcs[i] = BZ3_ERR_DATA_TOO_BIG;
+                    x.live = false;
+                    continue;
+                }
+                const size_t h = hdr.size();
+                hdr.resize(h + 8);
+                wr_le32(hdr.data() + h, (u32)osz);
+                wr_le32(hdr.data() + h + 4, (u32)orig[k]);
+                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
+                f.segs.push_back({(u64)f.slot(k), (u64)(outs[i] + x.pos + 8), (u64)osz});
+                x.pos += (size_t)osz + 8;
+            }
+            f.stage_headers(hdr);
+            f.copy();
+            for (s32 i : touched) {
+                out_sizes[i] = fr[i].pos;
+                fr[i].fin = fr[i].live && fr[i].next == fr[i].nb;
+            }
+        }
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].live && !fr[i].fin) rcs[i] = BZ3_ERR_BWT;
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].live && !fr[i].fin) rcs[i] = BZ3_ERR_BWT;
+    }
+}
+
+// ---- decompress: n frames whose buffers passed the pointer checks, on device dev ------------------------------------------
+// One walk reads every frame header.  Then per window: the walk of the next chunks of the frames in order, up to the
+// window's size in all (one launch, one read-back), scatter, run_decode (one CM launch), gather.  Every frame keeps its
+// own resume point, committed size and error: a chunk that fails ends its frame alone, the chunks of the frame before it
+// are committed; a header error found by the walk ends the frame once the chunks before it are committed.
+// bases (or nullptr): per frame nullptr, or base_sizes[i] bytes that are added to the decoded bytes at the same offsets; such a frame's capacity
+// is the smaller of out_sizes[i] and base_sizes[i], so that the walk refuses a chunk that runs past the base as one that runs past `out`.
+// outs[i] may be bases[i] (planes.hpp, "In place").
+// range (bz3_hip_decompress_device_range[_many]): frame i wants the w = min(out_sizes[i], base_sizes[i]) decoded bytes from offsets[i] on
+// (offsets == nullptr: 0) and nothing is too big.  Its walks are range walks (frame.hpp): chunks that end before the range are
+// header-checked and skipped on the device, headers at or beyond its end are never read, so the windows hold only the chunks that
+// share a byte with their frame's range; the first and the last of them are gathered clipped (push_range_segment), and `committed`
+// counts range bytes.  A frame's walk is over at its last chunk, at a header error or at the end of its range.
+void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
+                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr) {
+    struct Frame {
+        size_t buf_max = 0, committed = 0;
+        u32 decoded = 0;        // chunks decoded and committed
+        u32 walked = 0;         // chunks the walks recorded, less those given back (whole frames: pos.done)
+        int pending = BZ3_OK;   // the header error the walk stopped at
+        bool failed = false;    // a chunk of the current window failed
+        u64 lo = 0, hi = 0;     // range: the decoded bytes wanted
+    };
+    struct Chunk {
+        s32 frame;
+        WalkChunk rec;
+    };
+    std::vector<Frame> fr((size_t)n);
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
+        else live[i] = any = 1;
+        fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
+        if (range) {
+            fr[i].lo = offsets ? offsets[i] : 0;
+            fr[i].hi = fr[i].lo + (u64)fr[i].buf_max < fr[i].lo ? UINT64_MAX : fr[i].lo + (u64)fr[i].buf_max;
+            out_sizes[i] = 0;
+        }
+    }
+    if (!any) return;
+    DeviceFrames f;
+    std::vector<Chunk> win;
+    std::vector<WalkArg> args;
+    std::vector<s32> who;
+    std::vector<WalkChunk> rec;
+    std::vector<WalkTail> tails;
+    s32 cur = 0;  // frames before it are finished
+    // The next chunks of the live frames from `cur` on, W at most in all, into `win` (frame order).  A frame's limit is what
+    // is left of it or of the window; only a frame that stops at a header error walks fewer, and then the frames behind
+    // it are walked again with what is left of the window.
+    auto collect = [&](size_t W) {
+        win.clear();
+        while (win.size() < W) {
+            args.clear();
+            who.clear();
+            u32 budget = (u32)(W - win.size()), base = 0;
+            for (s32 i = cur; i < n && budget; i++) {
+                if (!live[i] || fr[i].pending != BZ3_OK || pos[i].done == pos[i].n_blocks) continue;
+                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+                args.push_back(pos[i].arg(ins[i], in_sizes[i], fr[i].buf_max, lim, base));
+                who.push_back(i);
+                base += lim;
+                budget -= lim;
+            }
+            if (args.empty()) return;
+            f.walk(args, rec, tails);
+            bool stopped = false;
+            for (size_t q = 0; q < who.size(); q++) {
+                const s32 i = who[q];
+                for (u32 r = 0; r < tails[q].count; r++) win.push_back({i, rec[args[q].rec_base + r]});
+                pos[i].take(tails[q]);
+                fr[i].walked += tails[q].count;
+                if (tails[q].err != BZ3_OK) {
+                    fr[i].pending = tails[q].err;
+                    stopped = true;
+                }
+            }
+            if (!stopped) return;  // every frame walked its limit: the window is full or no chunk is left
+        }
+    };
+    // The same for ranges.  How many chunks a range touches is known only once they are walked, so every frame gets a limit of what its
+    // range would take of full blocks (two more for the two ends), the window's size at most, as long as the walk's records last: 256
+    // frames that want one chunk each are one walk and one window.  What a walk finds beyond W goes back to its frames (give_back).
+    auto range_walk_over = [&](s32 i) { return pos[i].done == pos[i].n_blocks || pos[i].planned >= fr[i].hi; };
+    auto collect_range = [&](size_t W) {
+        win.clear();
+        while (win.size() < W) {
+            args.clear();
+            who.clear();
+            u32 base = 0;
+            for (s32 i = cur; i < n && base < WALK_RECORDS; i++) {
+                if (!live[i] || fr[i].pending != BZ3_OK || range_walk_over(i)) continue;
+                const u64 from = std::max(fr[i].lo, pos[i].planned), est = (fr[i].hi - from) / pos[i].block_size + 2;
+                const u32 lim = (u32)std::min<u64>({est, (u64)(pos[i].n_blocks - pos[i].done), (u64)(W - win.size()), (u64)(WALK_RECORDS - base)});
+                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base));
+                who.push_back(i);
+                base += lim;
+            }
+            if (args.empty()) return;
+            f.walk(args, rec, tails);
+            for (size_t q = 0; q < who.size(); q++) {  // (every frame walked its limit or its walk is over: the loop ends)
+                const s32 i = who[q];
+                for (u32 r = 0; r < tails[q].count; r++) win.push_back({i, rec[args[q].rec_base + r]});
+                pos[i].take(tails[q]);
+                fr[i].walked += tails[q].count;
+                if (tails[q].err != BZ3_OK) fr[i].pending = tails[q].err;
+            }
+        }
+    };
+    // Chunks of `win` beyond the first W go back to their frames (the first window is walked before the states exist).
+    auto give_back = [&](size_t W) {
+        while (win.size() > W) {
+            const Chunk & c = win.back();
+            WalkPos & p = pos[c.frame];
+            p.off = c.rec.in_off;
+            p.planned = c.rec.out_off;
+            p.done = c.rec.index;
+            fr[c.frame].walked--;
+            fr[c.frame].pending = BZ3_OK;  // found again by a later walk
+            win.pop_back();
+        }
+    };
+    u32 bs_max = 0;
+    try {
+        if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
+        for (s32 i = 0; i < n; i++) {
+            if (range && fr[i].buf_max == 0) live[i] = 0;  // nothing wanted: the frame header alone was checked
+            if (live[i]) bs_max = std::max(bs_max, pos[i].block_size);
+        }
+        if (!bs_max) return;
+        // n_blocks is untrusted: the states are sized from the chunks the first walk finds present, never from n_blocks
+        if (range) collect_range(frame_window_limit());
+        else collect(frame_window_limit());
+        if (!f.init(bs_max, win.empty() ? 1 : win.size())) throw std::runtime_error("no states");
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_INIT;
+        return;
+    }
+    for (s32 i = 0; i < n; i++)
+        if (live[i]) out_sizes[i] = 0;
+    try {
+        DeviceGuard g(dev);
+        const u32 W = (u32)f.states.size();
+        std::vector<s32> sizes(W), orig(W);
+        std::vector<size_t> caps(W);
+        std::vector<void *> slots(W);
+        std::vector<u8> hdrs(17 * (size_t)W);
+        give_back(W);
+        for (bool first = true;; first = false) {
+            if (!first && range) collect_range(W), give_back(W);
+            else if (!first) collect(W);
+            const u32 t = (u32)win.size();
+            for (u32 k = 0; k < t; k++) {  // scatter: chunk k to slot k
+                const Chunk & c = win[k];
+                sizes[k] = c.rec.size;
+                orig[k] = c.rec.orig;
+                slots[k] = f.slot(k);
+                caps[k] = bz3_bound(pos[c.frame].block_size);
+                f.states[k]->block_size = (s32)pos[c.frame].block_size;  // every check of the block is made against its own frame's block size
+                f.states[k]->last_error = BZ3_OK;
+                memcpy(hdrs.data() + 17 * (size_t)k, c.rec.hdr, 17);
+                f.segs.push_back({(u64)(ins[c.frame] + c.rec.in_off + 8), (u64)f.slot(k), (u64)c.rec.size});
+            }
+            if (t) {
+                f.copy();
+                run_decode(f.states.data(), slots.data(), caps.data(), sizes.data(), orig.data(), hdrs.data(), (s32)t, false);
+                for (u32 k = 0; k < t; k++) {  // gather: per frame, the chunks before its first failure
+                    const Chunk & c = win[k];
+                    Frame & x = fr[c.frame];
+                    if (x.failed) continue;
+                    if (bz3_last_error(f.states[k]) != BZ3_OK) {  // :989-993
+                        rcs[c.frame] = f.states[k]->last_error;
+                        x.failed = true;
+                        continue;
+                    }
+                    if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
+                        const u64 p = c.rec.out_off, a = x.lo > p ? x.lo - p : 0, b = std::min<u64>(x.hi - p, (u64)c.rec.orig), at = p + a - x.lo;
+                        push_range_segment(f.segs, f.clips, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, a, b, (u64)(outs[c.frame] + at),
+                                           bases && bases[c.frame] ? (u64)(bases[c.frame] + at) : 0);
+                        x.committed = (size_t)(p + b - x.lo);
+                    } else {
+                        f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
+                                          bases && bases[c.frame] ? (u64)(bases[c.frame] + c.rec.out_off) : 0});
+                        x.committed = c.rec.out_off + (size_t)c.rec.orig;
+                    }
+                    x.decoded++;
+                }
+                f.copy();
+            }
+            // a frame ends at a failed chunk, or once every chunk it walked is committed and the walk is over (all chunks, or a header error)
+            bool left = false;
+            for (s32 i = cur; i < n; i++) {
+                if (!live[i]) continue;
+                Frame & x = fr[i];
+                out_sizes[i] = x.committed;
+                if (x.failed) live[i] = 0;
+                else if (x.decoded == x.walked && (x.pending != BZ3_OK || pos[i].done == pos[i].n_blocks || (range && range_walk_over(i)))) {
+                    rcs[i] = x.pending;
+                    live[i] = 0;
+                } else {
+                    left = true;
+                }
+            }
+            while (cur < n && !live[cur]) cur++;
+            if (!left) break;
+        }
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_BWT;
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_BWT;
+    }
+}
+
+// ---- decoded sizes: n frames' chunk headers, walked in rounds of up to WALK_RECORDS chunks over all frames -------------------
+void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t * in_sizes, size_t * decoded, int * rcs) {
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        decoded[i] = 0;
+        rcs[i] = BZ3_OK;
+        if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;
+        else live[i] = any = 1;
+    }
+    if (!any) return;
+    try {
+        DeviceFrames f;
+        if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // a block size bz3_new refuses: BZ3_ERR_INIT, what bz3_decompress reports for it
+        std::vector<WalkArg> args;
+        std::vector<s32> who;
+        std::vector<WalkChunk> rec;
+        std::vector<WalkTail> tails;
+        for (;;) {
+            args.clear();
+            who.clear();
+            u32 budget = (u32)WALK_RECORDS, base = 0;
+            for (s32 i = 0; i < n && budget; i++) {
+                if (!live[i]) continue;
+                if (pos[i].done == pos[i].n_blocks) {
+                    live[i] = 0;
+                    continue;
+                }
+                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+                args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, lim, base));
+                who.push_back(i);
+                base += lim;
+                budget -= lim;
+            }
+            if (args.empty()) break;
+            f.walk(args, rec, tails);
+            for (size_t q = 0; q < who.size(); q++) {
+                const s32 i = who[q];
+                pos[i].take(tails[q]);
+                decoded[i] = pos[i].planned;
+                if (tails[q].err != BZ3_OK) {
+                    rcs[i] = tails[q].err;
+                    live[i] = 0;
+                }
+            }
+        }
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) rcs[i] = BZ3_ERR_INIT;
+    }
+}
+
+// ---- the entry points' argument checks ------------------------------------------------------------------------------------
+// The GPU of a call: every non-empty buffer (a[i] with a_sizes[i] > 0, likewise b) must be device memory of the GPU the first
+// one lives on.  -1: no buffer is non-empty; -2: one is not.
+int frames_device(s32 n, const void * const * a, const size_t * a_sizes, const void * const * b, const size_t * b_sizes) {
+    int dev = -1;
+    auto check = [&](const void * p) {
+        const int d = device_of(p);
+        if (d < 0 || (dev >= 0 && d != dev)) return false;
+        dev = d;
+        return true;
+    };
+    for (s32 i = 0; i < n; i++) {
+        if (a_sizes[i] && !check(a[i])) return -2;
+        if (b && b_sizes[i] && !check(b[i])) return -2;
+    }
+    return dev;
+}
+
+// Whole-call failure: every frame gets `rc` and size 0.
+int fail_frames(s32 n, int * rcs, size_t * sizes, int rc) {
+    for (s32 i = 0; i < n; i++) {
+        if (rcs) rcs[i] = rc;
+        if (sizes) sizes[i] = 0;
+    }
+    return rc;
+}
+
+int first_error(s32 n, const int * rcs) {
+    for (s32 i = 0; i < n; i++)
+        if (rcs[i] != BZ3_OK) return rcs[i];
+    return BZ3_OK;
+}
+
+// Do [a, a + a_size) and [b, b + b_size) share a byte?
+bool ranges_overlap(const void * a, size_t a_size, const void * b, size_t b_size) {
+    const u64 x = (u64)a, y = (u64)b;
+    return a_size && b_size && x < y + b_size && y < x + a_size;
+}
+
+bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
+    for (s32 i = 0; i < n; i++)
+        if (!planes_elem_size_ok(elem_sizes[i])) return false;
+    return true;
+}
+
+}  // namespace
+
+BZIP3_API int bz3_hip_compress_device_delta(uint32_t block_size, uint32_t elem_size, const void * in, const void * base, void * out, size_t in_size,
+                                            size_t * out_size) {
+    if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
+    const int dev = device_of(out);
+    if (dev < 0 || (in_size && device_of(in) != dev)) return BZ3_ERR_INIT;
+    if (base && in_size && (device_of(base) != dev || ranges_overlap(out, *out_size, base, in_size) || ranges_overlap(out, *out_size, in, in_size))) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    const u8 * bases[1] = {(const u8 *)base};
+    u8 * outs[1] = {(u8 *)out};
+    int rc = BZ3_OK;
+    compress_frames(dev, block_size, 1, &elem_size, ins, bases, &in_size, outs, out_size, &rc);
+    return rc;
+}
+
+BZIP3_API int bz3_hip_compress_device_planes(uint32_t block_size, uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_compress_device_delta(block_size, elem_size, in, nullptr, out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_compress_device(uint32_t block_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_compress_device_planes(block_size, 1, in, out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_decompress_device_delta(uint32_t elem_size, const void * in, const void * base, size_t base_size, void * out, size_t in_size,
+                                              size_t * out_size) {
+    if (!planes_elem_size_ok(elem_size)) return BZ3_ERR_INIT;
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0 || (*out_size && device_of(out) != dev)) return BZ3_ERR_INIT;
+    if (base && base_size && (device_of(base) != dev || (base != out && ranges_overlap(out, *out_size, base, base_size)))) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    const u8 * bases[1] = {(const u8 *)base};
+    u8 * outs[1] = {(u8 *)out};
+    int rc = BZ3_OK;
+    decompress_frames(dev, 1, &elem_size, ins, &in_size, bases, &base_size, outs, out_size, &rc);
+    return rc;
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes(uint32_t elem_size, const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_decompress_device_delta(elem_size, in, nullptr, 0, out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_decompress_device(const void * in, void * out, size_t in_size, size_t * out_size) {
+    return bz3_hip_decompress_device_planes(1, in, out, in_size, out_size);
+}
+
+BZIP3_API int bz3_hip_frame_decoded_size_device(const void * in, size_t in_size, size_t * decoded_size) {
+    *decoded_size = 0;
+    if (in_size < 13) return BZ3_ERR_MALFORMED_HEADER;
+    const int dev = device_of(in);
+    if (dev < 0) return BZ3_ERR_INIT;
+    const u8 * ins[1] = {(const u8 *)in};
+    int rc = BZ3_OK;
+    decoded_sizes_frames(dev, 1, ins, &in_size, decoded_size, &rc);
+    return rc;
+}
+
+// (elem_sizes == NULL: element size 1 for every frame, as bz3_hip.h says; bases == NULL: no frame has a base.  The calls without _delta pass them.)
+BZIP3_API int bz3_hip_compress_device_delta_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const void * const bases[],
+                                                 const size_t in_sizes[], void * const outs[], size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: in_sizes[i] bytes of the same GPU that the frame's output overlaps neither with it nor with the input
+        if (!bases[i] || !in_sizes[i]) continue;
+        if (device_of(bases[i]) != dev || ranges_overlap(outs[i], out_sizes[i], bases[i], in_sizes[i]) || ranges_overlap(outs[i], out_sizes[i], ins[i], in_sizes[i]))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    compress_frames(dev, block_size, n, elem_sizes, (const u8 * const *)ins, (const u8 * const *)bases, in_sizes, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_compress_device_planes_many(uint32_t block_size, int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                  void * const outs[], size_t out_sizes[], int rcs[]) {
+    return bz3_hip_compress_device_delta_many(block_size, n, elem_sizes, ins, nullptr, in_sizes, outs, out_sizes, rcs);
+}
+
+BZIP3_API int bz3_hip_compress_device_many(uint32_t block_size, int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                           size_t out_sizes[], int rcs[]) {
+    return bz3_hip_compress_device_planes_many(block_size, n, nullptr, ins, in_sizes, outs, out_sizes, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                   const void * const bases[], const size_t base_sizes[], void * const outs[], size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        if (device_of(bases[i]) != dev || (bases[i] != outs[i] && ranges_overlap(outs[i], out_sizes[i], bases[i], base_sizes[i])))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                   const uint64_t offsets[], const void * const bases[], const size_t base_sizes[], void * const outs[],
+                                                   size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        // the call touches w = min(*out_size, base_size) bytes of each at the most: two runs of w bytes overlap iff they start less than w apart
+        const u64 w = out_sizes[i] < base_sizes[i] ? out_sizes[i] : base_sizes[i], x = (u64)outs[i], y = (u64)bases[i];
+        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true,
+                      (const u64 *)offsets);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * base, size_t base_size, void * out,
+                                              size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    int rc = BZ3_OK;
+    return bz3_hip_decompress_device_range_many(1, &elem_size, ins, &in_size, &offset, bases, &base_size, outs, out_size, &rc);
+}
+
+BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
+                                                    size_t out_sizes[], int rcs[]) {
+    return bz3_hip_decompress_device_delta_many(n, elem_sizes, ins, in_sizes, nullptr, nullptr, outs, out_sizes, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_many(int32_t n, const void * const ins[], const size_t in_sizes[], void * const outs[], size_t out_sizes[],
+                                             int rcs[]) {
+    return bz3_hip_decompress_device_planes_many(n, nullptr, ins, in_sizes, outs, out_sizes, rcs);
+}
+
+BZIP3_API int bz3_hip_frame_decoded_sizes_device(int32_t n, const void * const ins[], const size_t in_sizes[], size_t decoded_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !decoded_sizes || !rcs) return fail_frames(n, rcs, decoded_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, nullptr, nullptr);
+    if (dev == -2) return fail_frames(n, rcs, decoded_sizes, BZ3_ERR_INIT);
+    decoded_sizes_frames(dev, n, (const u8 * const *)ins, in_sizes, decoded_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+namespace {
+// What a single-shot call owns: a non-blocking stream and one device allocation on the current device.  However the call ends, the
+// stream is waited for, then the allocation freed, then the stream destroyed.
+struct ScratchStream {
+    hipStream_t s = nullptr;
+    u8 * mem = nullptr;
+    ScratchStream() = default;
+    ScratchStream(const ScratchStream &) = delete;
+    ScratchStream & operator=(const ScratchStream &) = delete;
+    void open(size_t bytes) {
+        HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_CHECK(hipMalloc((void **)&mem, bytes));
+    }
+    ~ScratchStream() {
+        if (s) (void)hipStreamSynchronize(s);
+        if (mem) (void)hipFree(mem);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+// n segments of `width` u64 each relative to src / base / dst, one launch: (src_off, dst_off, len[, elem_size | inverse << 8]), or with
+// width 5 (src_off, base_off, dst_off, len, elem_size | inverse << 8), base_off = UINT64_MAX for a segment without a base.
+int32_t debug_move_segments(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, int width) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    for (s32 i = 0; width >= 4 && i < n; i++) {
+        const u64 mode = segs[width * i + width - 1];
+        if (!planes_elem_size_ok(mode & 0xff) || (mode >> 9)) return BZ3_ERR_INIT;
+    }
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (width == 5 && device_of(base) != dev)) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        std::vector<CopySeg> v((size_t)n);
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)width * i;
+            if (width == 5) v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[2], q[3], q[4], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]};
+            else v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[1], q[2], width == 4 ? q[3] : 0, 0};
+        }
+        std::vector<u8> staging;
+        sc.open(copy_table_bytes((size_t)n));
+        copy_segments(v, staging, sc.mem, sc.s);
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    return rc;
+}
+}  // namespace
+
+BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 3); }
+
+BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 4); }
+
+BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    return debug_move_segments(src, base, dst, segs, n, 5);
+}
+
+// n septuples (src_off, base_off, dst_off, len, elem_size | 1 << 8, a, b): of the merge of the `len` bytes at src_off the bytes [a, b), to
+// dst_off (plus the bytes at base_off unless it is UINT64_MAX), one launch through the segments a range call's gather makes of them.
+BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)7 * i;
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
+        any_base |= q[1] != UINT64_MAX;
+    }
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        std::vector<CopySeg> v;
+        std::vector<u64> clips;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)7 * i;
+            push_range_segment(v, clips, (u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+        }
+        std::vector<u8> staging;
+        sc.open(range_table_bytes((size_t)n));
+        copy_segments(v, staging, sc.mem, sc.s, &clips);
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    return rc;
+}
+
+// The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state init, no inversion) of n buffers in device memory of one GPU, at any
+// alignment: crc32c_device_many (crc32c.hip) on the callers' buffers.  Per call one stream, one allocation (the table, then the n result
+// words), one table upload, one memset, at most two launches and one read-back, whatever n is.
+BZIP3_API int bz3_hip_crc32c_device_many(int32_t n, const void * const * ptrs, const size_t * sizes, const uint32_t * inits, uint32_t * crcs) {
+    if (n < 0 || (n > 0 && (!ptrs || !sizes || !crcs))) return BZ3_ERR_INIT;
+    if (n == 0) return BZ3_OK;
+    int dev = -1;
+    u64 total_seg = 0;
+    std::vector<CrcBuf> tab((size_t)n);
+    for (s32 i = 0; i < n; i++) {
+        tab[(size_t)i] = {sizes[i] ? dev_addr(ptrs[i]) : 0, (u64)sizes[i], inits ? inits[i] : 1u, (u32)total_seg};
+        if (!sizes[i]) continue;
+        const int d = device_of(ptrs[i]);
+        if (d < 0 || (dev >= 0 && d != dev)) return BZ3_ERR_INIT;
+        dev = d;
+        total_seg += crc_many_segments(ptrs[i], (u64)sizes[i]);
+        if (total_seg >= ((u64)1 << 31)) return BZ3_ERR_INIT;  // 32 TiB in one call
+    }
+    if (dev < 0) {  // nothing but empty buffers: no GPU is needed
+        for (s32 i = 0; i < n; i++) crcs[i] = tab[(size_t)i].init;
+        return BZ3_OK;
+    }
+    DeviceCtx * ctx = nullptr;
+    try {
+        ctx = get_ctx(dev);
+    } catch (...) {
+        ctx = nullptr;
+    }
+    if (!ctx) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        const size_t tab_bytes = align256((size_t)n * sizeof(CrcBuf));
+        std::vector<u32> got((size_t)n);
+        sc.open(tab_bytes + (size_t)n * sizeof(u32));
+        HIP_CHECK(hipMemcpyAsync(sc.mem, tab.data(), (size_t)n * sizeof(CrcBuf), hipMemcpyHostToDevice, sc.s));
+        g_crc_launches += crc32c_device_many((const CrcBuf *)sc.mem, (u32)n, (u32)total_seg, ctx->d_crc, (u32 *)(sc.mem + tab_bytes), sc.s);
+        HIP_CHECK(hipMemcpyAsync(got.data(), sc.mem + tab_bytes, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, sc.s));
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+        memcpy(crcs, got.data(), (size_t)n * sizeof(u32));  // nothing is written unless the whole call succeeded
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    return rc;
+}
+
+BZIP3_API unsigned bz3_hip_debug_crc_launches(int reset) { return reset ? g_crc_launches.exchange(0) : g_crc_launches.load(); }
+
+// One buffer: the n = 1 case of the call above.
+BZIP3_API int bz3_hip_crc32c_device(const void * p, size_t n, uint32_t init, uint32_t * crc) {
+    return bz3_hip_crc32c_device_many(1, &p, &n, &init, crc);
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// frame.hpp -- kernels of the device-resident frame API (bz3_hip_compress_device / bz3_hip_decompress_device, api.hip).
+// frame.hpp -- kernels of the device-resident frame API (bz3_hip_compress_device / bz3_hip_decompress_device, api_frames.hip).
 //
 // A frame (src/libbz3.c:876-997) is a 13-byte header, then per block an 8-byte chunk header (coded size, original size)
 // and the coded bytes.  Moving a window of blocks between the caller's buffers and the states' slots is a list of
@@ -8,26 +8,10 @@
 // in one read-back.
 #pragma once
 #include "../../include/libbz3.h"
+#include "frame_check.hpp"
 #include "hipx.hpp"
 
 namespace bz3 {
-
-// The four checks of one chunk header in bz3_decompress (src/libbz3.c:963-985), in the reference's order.  `p` points at
-// the chunk header, `in_left` bytes of the frame remain from there, `planned` bytes of output precede the chunk.
-// Shared by the host loop (bz3_decompress) and the device walk (k_frame_walk_many), so the rules exist once.
-__host__ __device__ inline int frame_chunk_check(const u8 * p, size_t in_left, u32 block_size, size_t buf_max, size_t planned,
-                                                 s32 * size, s32 * orig_size) {
-    if (in_left < 8) return BZ3_ERR_MALFORMED_HEADER;  // :963
-    const s32 sz = (s32)((u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24));
-    if (sz < 0 || (u32)sz > block_size) return BZ3_ERR_MALFORMED_HEADER;  // :969
-    if (in_left < (size_t)sz + 8) return BZ3_ERR_TRUNCATED_DATA;         // :974
-    const s32 orig = (s32)((u32)p[4] | ((u32)p[5] << 8) | ((u32)p[6] << 16) | ((u32)p[7] << 24));
-    if (orig < 0) return BZ3_ERR_MALFORMED_HEADER;                        // :980
-    if (buf_max < planned + (size_t)orig) return BZ3_ERR_DATA_TOO_BIG;   // :985
-    *size = sz;
-    *orig_size = orig;
-    return BZ3_OK;
-}
 
 // ---- k_copy_segments -------------------------------------------------------------------------------------------------
 // One segment: `len` bytes from absolute device address `src` to `dst`.  Segments of one launch do not overlap on the
@@ -138,7 +122,7 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
 // first (src/libbz3.c:930-960) and then walks from offset 13.  It walks up to `limit` chunks, writes their records from
 // rec[rec_base] on and its resume state to tails[i].
 //
-// A range walk (WalkArg::range != 0; bz3_hip_decompress_device_range, api.hip) wants only the chunks that hold a byte of the
+// A range walk (WalkArg::range != 0; bz3_hip_decompress_device_range, api_frames.hip) wants only the chunks that hold a byte of the
 // output bytes [lo, hi): the lane stops before it reads a header with planned >= hi, and it advances over a chunk that ends at
 // or before lo (planned + orig <= lo) or is empty with its header checked as any other, but without a record and without using
 // any of `limit`, so a frame may hold any number of such chunks before its range.  The capacity check is not made

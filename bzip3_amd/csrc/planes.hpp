@@ -1,4 +1,4 @@
-// planes.hpp -- byte-plane split / merge of a frame's blocks (bz3_hip_compress_device_planes / bz3_hip_decompress_device_planes, api.hip).
+// planes.hpp -- byte-plane split / merge of a frame's blocks (bz3_hip_compress_device_planes / bz3_hip_decompress_device_planes, api_frames.hip).
 //
 // For a block of s bytes of k-byte elements, m = s / k:
 //     split_k(b)[q m + e] = b[e k + q]   (0 <= q < k, 0 <= e < m),     split_k(b)[j] = b[j]   (m k <= j < s: the tail stays in place)
@@ -18,7 +18,7 @@
 // granules at the two ends of a plane (split) or of the block (merge) and for the tail.  As in copy_tile, no granule is loaded that
 // holds no byte of the segment, and no byte outside the segment's destination is written.
 //
-// Delta segments (CopySeg::base != 0; bz3_hip_*_device_delta, api.hip).  D(x, b)[i] = (x[i] - b[i]) mod 256 for every byte.  A split
+// Delta segments (CopySeg::base != 0; bz3_hip_*_device_delta, api_frames.hip).  D(x, b)[i] = (x[i] - b[i]) mod 256 for every byte.  A split
 // segment with a base stores split_k(src - base), a merge segment merge_k(src) + base; the base lies on the interleaved (caller's)
 // side, at the offsets of that side, with an alignment of its own.  The difference is taken in phase 1, on the registers that hold
 // the interleaved bytes (before the transpose of a split, after the one of a merge), four bytes per operation (sub_bytes /
@@ -37,9 +37,9 @@
 //   * a tail byte is read and written by one thread, in that order, and used by no other;
 //   * delta1_tile reads the base at the destination's own granules (dst == base: the same alignment), each by the thread that then
 //     stores it.
-// Any other overlap of base and destination is the caller's error (api.hip refuses it).
+// Any other overlap of base and destination is the caller's error (api_frames.hip refuses it).
 //
-// Clipped merge (CopySeg::mode & PLANES_CLIP; bz3_hip_decompress_device_range, api.hip).  A range of a frame cuts its first and its
+// Clipped merge (CopySeg::mode & PLANES_CLIP; bz3_hip_decompress_device_range, api_frames.hip).  A range of a frame cuts its first and its
 // last chunk: of merge_k(slot[0, s)) only the bytes [a, b) are wanted, at dst[0, b - a), plus base[0, b - a) where there is a base
 // (dst and base address the clip's first byte; the chunk's byte c pairs with dst[c - a] and base[c - a]).  clip_merge_tile is
 // merge_tile with the chunk's own m = s / k as the plane stride and three changes:

@@ -7,7 +7,7 @@
 
 namespace bz3 {
 
-// Bump allocator over a device scratch buffer (the per-device workspace owned by api.cpp).
+// Bump allocator over a device scratch buffer (the per-device workspace owned by api_context.hip).
 struct Arena {
     char * base = nullptr;
     size_t cap = 0, used = 0;

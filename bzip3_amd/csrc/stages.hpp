@@ -1,5 +1,5 @@
 // stages.hpp -- host-side entry points of the per-stage HIP pipelines (all asynchronous on a stream
-// unless stated).  One function per reference stage; api.cpp strings them together exactly in the
+// unless stated).  One function per reference stage; api_encode.hip and api_decode.hip string them together exactly in the
 // order of bz3_encode_block / bz3_decode_block (reference src/libbz3.c:585-654, :656-809).
 #pragma once
 #include "hipx.hpp"

@@ -79,7 +79,7 @@ BZIP3_API void bz3_hip_set_workspace_headroom(long long bytes);
 BZIP3_API size_t bz3_hip_workspace_headroom(void);
 /* Statistics: how often the rule had to be enforced since the last reset -- returns the pool trims, *releases receives the workspace releases. */
 BZIP3_API unsigned bz3_hip_debug_headroom_events(int reset, unsigned * releases);
-/* tests only: LZP contexts the encoder's front-end ring may hold (api.hip ring_contexts_for), the arena's slack beyond a request, and the bytes the
+/* tests only: LZP contexts the encoder's front-end ring may hold (api_internal.hpp ring_contexts_for), the arena's slack beyond a request, and the bytes the
  * library holds cached on `device` right now (workspace + idle pooled swap buffers). */
 BZIP3_API size_t bz3_hip_debug_ring_contexts(size_t free_bytes, size_t have, size_t need, size_t fixed, size_t ctx_bytes, size_t cap, int lean, size_t headroom);
 BZIP3_API size_t bz3_hip_debug_arena_slack(size_t bytes);
@@ -314,7 +314,7 @@ BZIP3_API int bz3_hip_decode_stream(int in_fd, int out_fd, int32_t blocks_per_ba
 
 /* Profiling: `copies` identical CM decode jobs in one launch through the current CM kernel variant; returns the launch
  * time in milliseconds, `out` receives the n (>= 256) decoded bytes of copy 0; with BZ3_CM_DEBUG=3 `counters` (u64[16] per
- * copy, may be NULL) receives the decoder's phase cycle counters instead of valid output (bzip3_amd/csrc/api.hip). */
+ * copy, may be NULL) receives the decoder's phase cycle counters instead of valid output (bzip3_amd/csrc/api_hooks.hip). */
 BZIP3_API float bz3_hip_stage_cm_decode_many(const uint8_t * in, int32_t in_size, uint8_t * out, int32_t n, int32_t copies, uint64_t * counters);
 
 /* The same for the encoder: `copies` identical CM encode jobs in one launch; *coded = coded size of copy 0, its bytes in `out`

@@ -5,12 +5,14 @@ without a GPU.  The bzip3_amd package never loads this library."""
 import hashlib
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "bzip3_amd", "csrc")
 OUT = os.path.join(HERE, "libbz3_emu_TESTONLY.so")
-SOURCES = ["sort.hip", "crc32c.hip", "mrle.hip", "lzp.hip", "bwt.hip", "unbwt.hip", "cm.hip", "api.hip", "stream.hip"]
+sys.path.insert(0, ROOT)
+from bzip3_amd.build import SOURCES  # noqa: E402  (one list of sources for both builds; importing the package loads no library)
 
 
 def build():
@@ -35,7 +37,7 @@ def build():
     for s in srcs:
         o = os.path.join(HERE, "build" + tag, os.path.basename(s) + ".o")
         objs.append(o)
-        cmd = ["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-DBZ3_EMU", *defs, *(["-DBZ3_EMU_WATCH"] if os.environ.get("BZ3_EMU_WATCH") else []), "-I", HERE, "-I", CSRC, "-x", "c++", "-c", s, "-o", o,
+        cmd = ["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-DBZ3_EMU", "-DBZ3_EMU_API_UNITS", *defs, *(["-DBZ3_EMU_WATCH"] if os.environ.get("BZ3_EMU_WATCH") else []), "-I", HERE, "-I", CSRC, "-x", "c++", "-c", s, "-o", o,
                "-Wno-unknown-pragmas", "-Wno-attributes"]
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     for s, p in procs:

@@ -138,7 +138,7 @@ def test_prototypes_equal_the_reference_header_when_it_is_here():
 
 
 def test_cu_partition_masks_are_disjoint_and_balanced(lib):
-    """The decoder's CU partition (api.hip DeviceCtx::cu_masks): the reserved CUs and the rest are disjoint, cover the device, and the reserved ones are
+    """The decoder's CU partition (api_context.hip DeviceCtx::cu_masks): the reserved CUs and the rest are disjoint, cover the device, and the reserved ones are
     spread evenly whichever way the driver deals mask bits to the eight XCDs -- in blocks of 32 bits or round robin (bit i -> XCD i mod 8)."""
     import ctypes as C
 
@@ -159,7 +159,7 @@ def test_cu_partition_masks_are_disjoint_and_balanced(lib):
 
 
 def test_headroom_rule_sizing_arithmetic(lib):
-    """VERDICT r05 item 2: the headroom rule (include/bz3_hip.h bz3_hip_set_workspace_headroom; api.hip ring_contexts_for / DeviceCtx::arena_slack).  The ring of
+    """VERDICT r05 item 2: the headroom rule (include/bz3_hip.h bz3_hip_set_workspace_headroom; api_internal.hpp ring_contexts_for / DeviceCtx::arena_slack).  The ring of
     LZP contexts is sized so that the arena it lives in -- request + slack -- and the swap buffers its blocks borrow leave `headroom` bytes of the device free;
     round 5 had a fixed 6 GiB margin that an unbounded 1/16 slack (5 GB of an 80 GB arena) consumed."""
     GiB = 1 << 30

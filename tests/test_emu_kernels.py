@@ -377,7 +377,7 @@ print("ok")
 
 
 def test_cm_policy_by_batch_size_routes_and_hands_blocks_back(oracle):
-    """The default policy picks the CM kernels by batch size (api.hip cm_variant_for): with BZ3_HIP_CUS=2 a batch of 4 blocks takes the
+    """The default policy picks the CM kernels by batch size (api_internal.hpp cm_variant_for): with BZ3_HIP_CUS=2 a batch of 4 blocks takes the
     two-per-CU row-cache kernels, a batch of 5 the three-per-CU kernels.  Round 5: blocks that cannot fit a row cache go STRAIGHT to the
     whole-model kernel inside the same call -- on encode by the BWT's histogram (more than a quarter of the bytes outside the 40 most frequent values: the random
     block and the 112-value one), on decode by a payload that hardly shrank (the random block); the 112-value block, which shrinks by 14 %, still reaches
@@ -640,7 +640,7 @@ o = Oracle()
 assert lib.bz3_hip_device_count() == 2
 bs = 65 * 1024
 t = datagen.shakespeare()
-n = 30  # 15 blocks per device: each group runs its front end through a ring of four context slots (api.hip pipeline_shape)
+n = 30  # 15 blocks per device: each group runs its front end through a ring of four context slots (api_encode.hip pipeline_shape)
 blocks = [t[i * 3000 : i * 3000 + 2500 + 7 * i] for i in range(n - 1)] + [b"tiny"]
 states = (C.c_void_p * n)(*[lib.bz3_new(bs) for _ in range(n)])
 assert sorted(lib.bz3_hip_state_device(s) for s in states) == [0] * 15 + [1] * 15
@@ -677,7 +677,7 @@ print("ok")
 
 
 def test_front_end_ring_follows_the_memory_and_shrinks_when_the_arena_does_not_fit():
-    """Shape of the encoder's front-end ring (api.hip pipeline_shape / encode_group): four context slots when the memory holds at
+    """Shape of the encoder's front-end ring (api_encode.hip pipeline_shape / encode_group): four context slots when the memory holds at
     least three blocks per slot and the batch is large enough, two otherwise; when the workspace allocation fails although
     hipMemGetInfo promised the room (BZ3_EMU_MALLOC_LIMIT: allocations above the limit fail with hipErrorOutOfMemory), the ring
     shrinks -- first to two slots, then window by window -- instead of failing the batch, and the blocks still equal the oracle's."""
@@ -738,7 +738,7 @@ print("ok")
 
 
 def test_keep_workspace_mode_reuses_the_arena_across_a_round_trip():
-    """BZ3_HIP_KEEP_WS=1 (experiment for round 5, api.hip keep_workspace): a lean batch's workspace is NOT handed back when the encode call ends, the
+    """BZ3_HIP_KEEP_WS=1 (experiment for round 5, api_internal.hpp keep_workspace): a lean batch's workspace is NOT handed back when the encode call ends, the
     decode call that follows reuses it and carves the swap buffers of its tail windows from it (the pool serves what does not fit); blocks and
     error codes are what they are without the switch.  Two round trips of 7 small lean blocks through windows of 2 x 3 (BZ3_HIP_TAIL_PIPE), a
     failing block among them on the second.  (That the workspace of a LARGE batch stays is the `released` bit of
@@ -794,7 +794,7 @@ print("ok")
 
 
 def test_auto_cm_policy_and_encode_many_hook(oracle):
-    """The automatic CM policy by batch size (api.hip cm_variant_for; BZ3_HIP_CUS=2 pretends the GPU has two CUs): up to one block per CU
+    """The automatic CM policy by batch size (api_internal.hpp cm_variant_for; BZ3_HIP_CUS=2 pretends the GPU has two CUs): up to one block per CU
     the whole-model kernels (0), up to two per CU the 96-row pair (1), beyond that the three-per-CU pair (2); a forced mode wins.  And the profiling hook that launches N copies of one CM encode job returns the oracle's bytes."""
     import subprocess
 
@@ -828,7 +828,7 @@ print("ok")
 @pytest.mark.parametrize("pipe", [None, "1,4", "5,3", "40,2"], ids=["auto", "w1s4", "w5s3", "w40s2"])
 def test_pipelined_windows_of_a_large_batch(emu, oracle, pipe, monkeypatch):
     """A batch larger than the encoder's front-end windows (the LZP drivers of window k run on a side stream of the device beside the
-    preparation of the next windows and the completion of the previous ones, over a ring of 2-4 context slots: api.hip pipeline_shape /
+    preparation of the next windows and the completion of the previous ones, over a ring of 2-4 context slots: api_encode.hip pipeline_shape /
     encode_group) and than the decoder's tail windows (32 blocks: LZP decoders beside the next window's inverse BWTs): every block equals
     the oracle's both ways, with LZP applied, declined and skipped.  BZ3_HIP_LZP_PIPE = "window,slots" forces the ring's shape: windows of
     one block (36 windows through 4 slots), a ragged last window through 3 slots, a single window larger than the batch."""
@@ -874,7 +874,7 @@ def test_pipelined_windows_of_a_large_batch(emu, oracle, pipe, monkeypatch):
 @pytest.mark.parametrize("pipe", [None, "1,4", "3,3", "5,2"], ids=["auto", "w1s4", "w3s3", "w5s2"])
 def test_two_thread_front_end(emu, oracle, pipe, monkeypatch):
     """Round 6: bz3_hip_set_front_end_duo(1) -- phase A of the encoder's front end (CRC, mRLE, LZP preparation) on a second host thread and stream, up to
-    slots - 1 windows ahead of phase B (LZP emission, BWT, header) on the calling thread, swap buffers of lean states handed back behind events (api.hip
+    slots - 1 windows ahead of phase B (LZP emission, BWT, header) on the calling thread, swap buffers of lean states handed back behind events (api_encode.hip
     encode_group).  36 blocks (LZP applied, declined, stored; one with an invalid size, which fails alone) through forced ring shapes, classic and lean
     states, twice in a row (the second call reuses pool and arena): the oracle's bytes, and the ring reports the two-thread form."""
     if pipe:

@@ -225,7 +225,7 @@ def test_batch_api_host_buffers(gpu_lib, oracle, text):
 @pytest.mark.parametrize("pipe", [None, "1,4", "5,3", "6,2", "3,8"], ids=["auto", "w1s4", "w5s3", "w6s2", "w3s8"])
 def test_front_end_and_tail_rings_on_gpu(gpu_lib, oracle, text, pipe, monkeypatch):
     """The encoder's front end and the decoder's tail run their serial LZP kernels on side streams over a ring of context slots
-    (api.hip encode_group / decode_group).  Under the CPU emulator kernels run at launch, so only here do the side streams really
+    (api_encode.hip encode_group / api_decode.hip decode_group).  Under the CPU emulator kernels run at launch, so only here do the side streams really
     overlap the group's stream: 40 blocks (LZP applied, declined, stored) through forced ring shapes -- windows of one block
     through four slots, a ragged last window through three, round 2's two slots of six, eight slots (all eight side streams: an experiment's
     shape; a GPU-filling batch's tail takes four slots of 16 blocks by default) -- and the automatic one, classic and lean states: the
@@ -809,7 +809,7 @@ def test_kept_workspace_leaves_the_headroom_to_the_host_program(gpu_lib, text):
 
 @pytest.mark.parametrize("pipe", [None, "1,4", "5,3", "6,2"], ids=["auto", "w1s4", "w5s3", "w6s2"])
 def test_two_thread_front_end_on_gpu(gpu_lib, oracle, text, pipe, monkeypatch):
-    """Round 6: the encoder's front end on two host threads and two streams (bz3_hip_set_front_end_duo(1); api.hip encode_group) -- only on the GPU do the
+    """Round 6: the encoder's front end on two host threads and two streams (bz3_hip_set_front_end_duo(1); api_encode.hip encode_group) -- only on the GPU do the
     two streams really overlap.  120 blocks of up to 1.5 MiB (LZP applied, declined, stored, random), classic and lean states, three encode calls in a row
     (the later ones reuse the pool's swap buffers, which phase A may only touch behind phase B's events), forced ring shapes: the oracle's bytes, and the
     decoder gives the plaintext back."""

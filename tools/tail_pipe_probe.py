@@ -1,4 +1,4 @@
-"""Shape of the decoder's tail pipeline (api.hip decode_group: windows of blocks whose serial LZP decoders run on side streams while the
+"""Shape of the decoder's tail pipeline (api_decode.hip decode_group: windows of blocks whose serial LZP decoders run on side streams while the
 inverse BWTs of the following windows and the mRLE / CRC stages of the preceding ones run on the group's stream).
 One batch of `blocks` text blocks of `MiB` each is encoded once on the GPU; the coded blocks are stashed in device memory and decoded
 again under every "window,slots" setting given (BZ3_HIP_TAIL_PIPE; "default" = what decode_group picks itself), `trials` times each.
