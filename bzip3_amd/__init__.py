@@ -95,6 +95,10 @@ def _declare(L, strict=True):
         "bz3_hip_decompress_device_range_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
                                                            C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_range": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_decompress_device_strided": (C.c_int, [u32, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, vp, sz, vp, C.POINTER(sz)]),
+        "bz3_hip_decompress_device_strided_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
+                                                             C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_strided": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -585,6 +589,72 @@ def decompress_tensor_range(frame, offset, nbytes, out=None, planes=1, base=None
         raise Bz3Error(e.code, "bz3_hip_decompress_device_range", e.outs[0]) from None
 
 
+def decompress_tensors_strided(frames, offsets, runs, strides, counts, outs=None, planes=1, bases=None, lib=None):
+    """A strided byte set of what every frame decodes to, for many frames in ONE call (bz3_hip_decompress_device_strided_many): of frame i
+    the counts[i] runs of runs[i] bytes whose starts lie strides[i] bytes apart from offsets[i] on, one after the other -- a slice along
+    any dimension of a row-major tensor.  Only the chunks that hold a byte of a run are decoded: chunks that lie wholly in a gap between
+    two runs are skipped like those before the first run.  Returns uint8 tensors, shorter than counts[i] * runs[i] where the set runs
+    past the end of the frame (pread's rule; never an error).  `outs`: contiguous uint8 tensors of at least counts[i] * runs[i] bytes to
+    read into; by default views of one allocation.  `planes` as in
+    decompress_tensors.  `bases[i]`: None, or the base's bytes OF THE SLICE in output order (bases[i][t] pairs with output byte t; at
+    least as many as are asked for); outs[i] may be bases[i].  ValueError for a negative number, for strides[i] < runs[i] where
+    counts[i] > 1 and runs[i] > 0, and for a set that does not fit 64 bits.  The same frame may appear more than once.  Raises Bz3Error
+    with .index / .codes / .outs (per frame the bytes committed before its error) as decompress_tensors does.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    cols = [[int(v) for v in col] for col in (offsets, runs, strides, counts)]
+    if any(len(col) != n for col in cols):
+        raise ValueError(f"decompress_tensors_strided: {n} frames and {[len(col) for col in cols]} offsets, runs, strides and counts")
+    params = list(zip(*cols))
+    for i, (o, r, s, c) in enumerate(params):
+        if min(o, r, s, c) < 0:
+            raise ValueError("decompress_tensors_strided: offsets, runs, strides and counts must not be negative")
+        if r and c and ((c > 1 and s < r) or c * r >= 1 << 64 or o + (c - 1) * s + r >= 1 << 64):
+            raise ValueError(f"decompress_tensors_strided: ({o}, {r}, {s}, {c}) of frame {i} is no strided range")
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
+    dev = _same_device(frames, "decompress_tensors_strided")
+    L = lib or load()
+    nbytes = [r * c for _, r, _, c in params]
+    if outs is None:
+        outs = _carve(sum(nbytes), nbytes, dev)
+    else:
+        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
+        if len(outs) != n:
+            raise ValueError(f"decompress_tensors_strided: {n} frames and {len(outs)} outputs")
+        _same_device(frames + outs, "decompress_tensors_strided")
+    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
+        if o.numel() < w or (b is not None and b.numel() < w):
+            raise ValueError(f"decompress_tensors_strided: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
+    caps = nbytes
+    torch.cuda.synchronize(dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    rc = L.bz3_hip_decompress_device_strided_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                                  (C.c_uint64 * (4 * n))(*[v for p in params for v in p]), _ptrs_or_null(bases),
+                                                  (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, caps)]), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, "bz3_hip_decompress_device_strided_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def decompress_tensor_strided(frame, offset, run, stride, count, out=None, planes=1, base=None, lib=None):
+    """`count` runs of `run` bytes, `stride` bytes apart from `offset` on, of what `frame` decodes to (bz3_hip_decompress_device_strided):
+    decompress_tensors_strided for one frame; Bz3Error's `.out` holds the bytes committed before the error."""
+    try:
+        return decompress_tensors_strided([frame], [offset], [run], [stride], [count], None if out is None else [out], planes=planes, bases=None if base is None else [base],
+                                          lib=lib)[0]
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_decompress_device_strided", e.outs[0]) from None
+
+
 # ---- typed tensors ------------------------------------------------------------------------------------------------------------
 # The byte-plane element size pack_tensor uses when `planes` is None, by dtype name: the component size where the measurements of
 # DESIGN.md ("Typed tensors") show the planes frame smaller than the interleaved one, 1 where they show it larger or no different
@@ -755,6 +825,8 @@ def _pack_many(xs, block_size, planes, lib, bases=None, checksum=True):
     braws = [_base_bytes(b, r.numel(), r.device, f"base {i}") for i, (b, r) in enumerate(zip(_bases_arg(bases, len(xs)), raws))]
     ks = [default_planes(x.dtype) if b is None else delta_default_planes(x.dtype) for x, b in zip(xs, braws)] if planes is None else _planes_arg(planes, len(xs))
     bss = [_lossless_block_size(r.numel(), block_size, k) for r, k in zip(raws, ks)]
+    if any(bs % k for bs, k in zip(bss, ks)):  # every chunk starts an element: what keeps typed slices on the 16-byte path of the strided merge
+        raise AssertionError("a lossless block size must be a multiple of the element size")
     dev = _same_device(raws, "pack")
     L = lib or load()
     frames = _compress_many(L, raws, bss, ks, dev, slack=True, bases=braws)
@@ -907,6 +979,93 @@ def unpack_tensor_rows(p, start, stop, out=None, base=None, lib=None):
     return _unpack_rows_many([p], [(start, stop)], None if out is None else [out], lib, [base])[0]
 
 
+def _slice_of(p, sl, what):
+    """(shape, (offset, run, stride, count)) of the slice sl = (dim, start, stop) of a PackedTensor; None is the whole tensor."""
+    if not isinstance(p, PackedTensor):
+        raise TypeError("unpack: a PackedTensor is expected")
+    shape = tuple(p.shape)
+    if sl is None:
+        return shape, (0, p.nbytes, p.nbytes, 1)
+    dim, start, stop = (int(v) for v in sl)
+    if not shape:
+        raise ValueError(f"{what}: a 0-d tensor has no dimension to slice")
+    if not -len(shape) <= dim < len(shape):
+        raise ValueError(f"{what}: dimension {dim} of a tensor of {len(shape)} dimensions")
+    dim %= len(shape)
+    if not 0 <= start <= stop <= shape[dim]:
+        raise ValueError(f"{what}: ({start}, {stop}) of a dimension of {shape[dim]}")
+    numel, inner, count = 1, 1, 1
+    for d, v in enumerate(shape):
+        numel *= v
+        if d > dim:
+            inner *= v
+        if d < dim:
+            count *= v
+    inner *= p.nbytes // numel if numel else 0  # the element's bytes (a complex element whole)
+    return shape[:dim] + (stop - start,) + shape[dim + 1 :], (start * inner, (stop - start) * inner, shape[dim] * inner, count)
+
+
+def _unpack_slices_many(ps, slices, outs, lib, bases):
+    """The slices slices[i] = (dim, start, stop) of every PackedTensor (None: the whole tensor), in ONE
+    bz3_hip_decompress_device_strided_many call.  bases[i]: the same slice of the base."""
+    import torch
+
+    shapes, params = [], []
+    for i, (p, sl) in enumerate(zip(ps, slices)):
+        shape, q = _slice_of(p, sl, f"tensor {i}")
+        shapes.append(shape)
+        params.append(q)
+    bases = _bases_arg(bases, len(ps))
+    braws = []
+    for i, (p, b, q, shape) in enumerate(zip(ps, bases, params, shapes)):
+        if p.delta and b is None:
+            raise ValueError(f"unpack: tensor {i} was packed against a base, which is needed to restore it")
+        if not p.delta:
+            b = None
+        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != shape:
+            raise ValueError(f"unpack: base {i} must hold the same slice of the base: {p.dtype} {shape}")
+        braws.append(_base_bytes(b, q[1] * q[3], p.frame.device, f"base {i}"))
+    dev = _same_device([p.frame for p in ps], "unpack")
+    if outs is None:
+        raws = _carve(0, [q[1] * q[3] for q in params], dev)  # every output at a multiple of 16 bytes, so that any dtype can view it
+    else:
+        raws = []
+        for p, o, shape in zip(ps, outs, shapes):
+            if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or tuple(o.shape) != shape or not o.is_contiguous():
+                raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and of the slice's shape")
+            raws.append(_as_bytes(o, "out"))
+    got = decompress_tensors_strided([p.frame for p in ps], *zip(*params), raws, planes=[p.planes for p in ps], bases=braws, lib=lib)
+    for i, (g, q) in enumerate(zip(got, params)):
+        if g.numel() != q[1] * q[3]:
+            raise Bz3Error(BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} holds {g.numel()} of the {q[1] * q[3]} bytes of its slice;", g)
+    whole = [i for i, sl in enumerate(slices) if sl is None]
+    if whole:  # a tensor that comes back whole must be all its frame decodes to (unpack_tensor fails with BZ3_ERR_DATA_TOO_BIG on a longer frame): one walk over those frames' chunk headers
+        n = len(whole)
+        need, rcs = (C.c_size_t * n)(), (C.c_int * n)()
+        (lib or load()).bz3_hip_frame_decoded_sizes_device(n, _ptrs([ps[i].frame for i in whole]), (C.c_size_t * n)(*[ps[i].frame.numel() for i in whole]), need, rcs)
+        for i, d in zip(whole, need):
+            if d != ps[i].nbytes:
+                raise Bz3Error(BZ3_ERR_DATA_TOO_BIG if d > ps[i].nbytes else BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} decodes to {d} bytes, the tensor has {ps[i].nbytes};")
+    return list(outs) if outs is not None else [_from_bytes(r, p.dtype, shape) for r, p, shape in zip(raws, ps, shapes)]
+
+
+def unpack_tensor_slice(p, dim, start, stop, out=None, base=None, lib=None):
+    """x.narrow(dim, start, stop - start) of the tensor x a PackedTensor holds, contiguous, in p.dtype, on the frame's GPU, without the
+    whole tensor ever existing there (bz3_hip_decompress_device_strided).  With e the element's bytes and inner = e * prod(shape[dim + 1:])
+    the slice is prod(shape[:dim]) runs of (stop - start) * inner bytes, shape[dim] * inner bytes apart, from byte start * inner on.  Only
+    the chunks of the frame that hold a byte of a run are decoded: a slice of dimension 0 decodes about its share of the chunks
+    (unpack_tensor_rows, whose result this is for dim = 0); a slice of an inner dimension decodes every chunk unless
+    shape[dim] * inner exceeds the block size, so that whole chunks fall between two runs -- what it always saves is the full-size
+    buffer and the second copy.  Runs shorter than 16 elements of p.planes bytes are gathered byte by byte: correct and
+    slow.  A negative `dim` counts from the end.  ValueError for a 0-d tensor, a bad `dim`, and unless
+    0 <= start <= stop <= p.shape[dim]; Bz3Error if the frame fails or returns fewer bytes than the slice holds.  `out`: a contiguous
+    tensor of p.dtype and of the slice's shape.  A tensor packed against a base needs `base`: THE SAME SLICE of the base, of the dtype and
+    of the slice's shape; it may have any strides (base.narrow(dim, start, stop - start) will do) and is then read through a contiguous
+    copy; `out` may be it when it is contiguous.  PackedTensor.base_crc covers the whole base and cannot be checked against a slice of it:
+    the caller vouches that this is a slice of the right base."""
+    return _unpack_slices_many([p], [(dim, start, stop)], None if out is None else [out], lib, [base])[0]
+
+
 def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None, checksum=True):
     """pack_tensor for every tensor of a dict, batched: {name: PackedTensor}, each equal to pack_tensor(sd[name], block_size, planes).
     One bz3_hip_compress_device_delta_many call per distinct lossless block size (the C call takes one block size): the tensors whose
@@ -928,7 +1087,7 @@ def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None, c
     return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib, bases, checksum)))
 
 
-def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None, verify=False):
+def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None, verify=False, slices=None):
     """The tensors of pack_state_dict's result, decoded in ONE batched call (bz3_hip_decompress_device_delta_many).  `base`: the dict
     pack_state_dict was given; every tensor packed against a base needs its entry (unpack_tensor's rules and check_base).  With
     inplace=True those base tensors themselves are updated and returned (no second copy of the model in memory); tensors packed
@@ -939,8 +1098,45 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
     With inplace=True, ValueError.  All bases are checked by one batched checksum call, before anything is decoded.  `verify`: after
     decoding, one more batched call over the outputs and a ValueError that names the first tensor whose bytes do not have its `.crc`
     (tensors without one are skipped); with inplace=True the bases have been overwritten by then.  With `rows`, ValueError: a checksum
-    of the whole cannot vouch for a slice."""
+    of the whole cannot vouch for a slice.  `slices`: {name: (dim, start, stop)}: those tensors come back as
+    x.narrow(dim, start, stop - start) (unpack_tensor_slice), the names in `rows` as their rows and the others whole, all of them through
+    ONE bz3_hip_decompress_device_strided_many call.  `base`, check_base, verify and inplace are as with `rows`: the whole base dict,
+    every base checked whole, its slice taken here; ValueError with verify=True or inplace=True.  A name in both `rows` and `slices`:
+    ValueError.  slices=None runs what the function ran before it had the argument."""
     names = list(packed)
+    if slices is not None:
+        if verify:
+            raise ValueError("unpack_state_dict: verify=True and slices do not go together (the checksum covers the whole tensor)")
+        if inplace:
+            raise ValueError("unpack_state_dict: slices and inplace=True do not go together")
+        want = {k: (0, int(r[0]), int(r[1])) for k, r in (rows or {}).items()}
+        for k, sl in slices.items():
+            if k in want:
+                raise ValueError(f"unpack_state_dict: {k!r} is in both rows and slices")
+            want[k] = sl
+        unknown = [k for k in want if k not in packed]
+        if unknown:
+            raise ValueError(f"unpack_state_dict: a slice of {unknown[0]!r}, which is not in the dict")
+        if not names:
+            return {}
+        import torch
+
+        ps = [packed[k] for k in names]
+        sls = [want.get(k) for k in names]
+        shapes = [_slice_of(p, sl, repr(k))[0] for k, p, sl in zip(names, ps, sls)]  # (every slice is validated before anything is read)
+        bases, whole = [], []
+        L = lib or load()
+        for k, p, sl in zip(names, ps, sls):
+            b = base.get(k) if base is not None and p.delta else None
+            fits = isinstance(b, torch.Tensor) and b.dtype == p.dtype and tuple(b.shape) == tuple(p.shape)
+            # the whole base is at hand here, for the sliced tensors too: check it as unpack_tensor does, before anything is decoded
+            whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}") if check_base and fits and p.base_crc is not None else None)
+            if fits and sl is not None:
+                dim = int(sl[0]) % len(p.shape)
+                b = b.narrow(dim, int(sl[1]), int(sl[2]) - int(sl[1]))
+            bases.append(b)
+        _check_bases(ps, whole, [repr(k) for k in names], L)
+        return dict(zip(names, _unpack_slices_many(ps, sls, None, lib, bases)))
     if rows is not None:
         if verify:
             raise ValueError("unpack_state_dict: verify=True and rows do not go together (the checksum covers the whole tensor)")

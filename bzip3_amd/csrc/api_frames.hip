@@ -43,21 +43,32 @@ constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg)
 // [a, b) of every segment (two u64 each).
 constexpr size_t range_table_bytes(size_t nseg) { return ((copy_table_bytes(nseg) + 15) & ~(size_t)15) + nseg * 2 * sizeof(u64); }
 
+// The same for a launch that may hold strided merges (planes.hpp k_strided_segments): behind the clips, the STRIDED_PARAMS u64 of every segment.
+constexpr size_t strided_table_bytes(size_t nseg) { return range_table_bytes(nseg) + nseg * STRIDED_PARAMS * sizeof(u64); }
+
 // Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
 // The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
 // clips (or nullptr): two u64 per segment, the [a, b) of the segments with PLANES_CLIP; d_tab then holds range_table_bytes(segs.size())
 // bytes, and a launch with such a segment goes to k_range_segments.
-void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr) {
+// periods (or nullptr; only beside clips): STRIDED_PARAMS u64 per segment, read for the segments with PLANES_STRIDED; d_tab then holds
+// strided_table_bytes(segs.size()) bytes, and a launch with such a segment goes to k_strided_segments.
+void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr,
+                   const std::vector<u64> * periods = nullptr) {
     const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
     if (clips && clips->size() != 2 * n) throw std::length_error("one clip per segment");
-    staging.assign(clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
+    if (periods && (!clips || periods->size() != STRIDED_PARAMS * n)) throw std::length_error("one period per segment");
+    staging.assign(periods ? strided_table_bytes(n) : clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
     if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
     u32 * starts = (u32 *)(staging.data() + seg_bytes);
     u64 tiles = 0;
-    bool planes = false, delta = false, clip = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
+    bool planes = false, delta = false, clip = false, strided = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
     for (size_t i = 0; i < n; i++) {
         starts[i] = (u32)tiles;
-        if (segs[i].mode & PLANES_CLIP) {
+        if (segs[i].mode & PLANES_STRIDED) {
+            if (!periods) throw std::length_error("a strided segment without its period");
+            tiles += strided_tiles((*periods)[STRIDED_PARAMS * i + 4], segs[i].mode & 0xff);
+            strided = true;
+        } else if (segs[i].mode & PLANES_CLIP) {
             if (!clips) throw std::length_error("a clipped segment without its clip");
             tiles += clip_tiles(segs[i].len, segs[i].mode & 0xff, (*clips)[2 * i], (*clips)[2 * i + 1]);
             clip = true;
@@ -72,8 +83,12 @@ void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging,
     if (!tiles) return;
     const size_t clip_off = range_table_bytes(n) - n * 2 * sizeof(u64);
     if (clip) memcpy(staging.data() + clip_off, clips->data(), n * 2 * sizeof(u64));
-    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), clip ? staging.size() : copy_table_bytes(n), hipMemcpyHostToDevice, s));
-    if (clip)
+    if (strided) memcpy(staging.data() + range_table_bytes(n), periods->data(), n * STRIDED_PARAMS * sizeof(u64));
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), strided ? strided_table_bytes(n) : clip ? range_table_bytes(n) : copy_table_bytes(n), hipMemcpyHostToDevice, s));
+    if (strided)
+        launch(k_strided_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off),
+               (const u64 *)(d_tab + range_table_bytes(n)));
+    else if (clip)
         launch(k_range_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off));
     else
         launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
@@ -89,6 +104,28 @@ void push_range_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, u
     clips.push_back(plain ? 0 : b);
 }
 
+// The same for a chunk of which a strided range wants the nbytes bytes c(u) (planes.hpp, "Strided merge"; first in [1, run], stride >= run):
+// one contiguous piece (nbytes <= first) is the clipped or whole segment above, anything else a strided merge.  `periods` holds STRIDED_PARAMS u64 per segment.
+void push_strided_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, std::vector<u64> & periods, u64 slot, u64 s, u64 k, u64 c0, u64 first, u64 run, u64 stride,
+                          u64 nbytes, u64 dst, u64 base) {
+    const bool strided = nbytes > first;
+    if (!strided) {
+        push_range_segment(segs, clips, slot, s, k, c0, c0 + nbytes, dst, base);
+    } else {
+        segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_STRIDED, base});
+        clips.insert(clips.end(), {0, 0});
+    }
+    periods.insert(periods.end(), {strided ? c0 : 0, strided ? first : 0, strided ? run : 0, strided ? stride : 0, strided ? nbytes : 0});
+}
+
+// The last chunk byte a strided merge reads, c(nbytes - 1) for nbytes > 0, or UINT64_MAX where it does not fit 64 bits.
+u64 strided_last_byte(u64 c0, u64 first, u64 run, u64 stride, u64 nbytes) {
+    const u64 u = nbytes - 1;
+    unsigned __int128 c = (unsigned __int128)c0 + u;
+    if (u >= first) c += (unsigned __int128)((u - first) / run + 1) * (stride - run);
+    return c > UINT64_MAX ? UINT64_MAX : (u64)c;
+}
+
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
 constexpr size_t WALK_RECORDS = 4096;     // chunk records of one walk (bz3_hip_frame_decoded_sizes_device; a window's walk takes at most FRAME_WINDOW_MAX)
 static_assert(WALK_RECORDS >= FRAME_WINDOW_MAX, "a window's walk must fit the records");
@@ -97,13 +134,13 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Layout of a call's small device buffer, sized for its n frames: staged headers (one 13-byte frame header per frame and one
 // 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
-// header; with room for their clips), the walk's arguments, records and tails.
+// header; with room for their clips and periods), the walk's arguments, records and tails.
 struct MetaLayout {
     size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, bytes = 0;
     MetaLayout() = default;
     explicit MetaLayout(size_t frames) : n(frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
-        args = tab + align256(range_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        args = tab + align256(strided_table_bytes(2 * FRAME_WINDOW_MAX + n));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
         bytes = tails + align256(n * sizeof(WalkTail));
@@ -130,6 +167,7 @@ struct DeviceFrames {
     std::vector<bz3_state *> states;
     std::vector<CopySeg> segs;
     std::vector<u64> clips;  // empty, or the [a, b) of every segment of `segs` (a range call's gather)
+    std::vector<u64> periods;  // empty, or the STRIDED_PARAMS of every segment of `segs` (a strided call's gather)
     std::vector<u8> staging;
     ~DeviceFrames() {
         if (device < 0) return;
@@ -191,10 +229,11 @@ struct DeviceFrames {
     u8 * slot(size_t k) const { return slab + k * stride; }
     void copy() {  // the segments collected in `segs`, one launch, complete on return
         if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
-        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips);
+        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips, periods.empty() ? nullptr : &periods);
         HIP_CHECK(hipStreamSynchronize(s));
         segs.clear();
         clips.clear();
+        periods.clear();
     }
     void stage_headers(const std::vector<u8> & h) {
         if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
@@ -211,8 +250,10 @@ struct DeviceFrames {
         rec.resize(nrec);
         if (!n) return;
         HIP_CHECK(hipMemcpyAsync(meta + lay.args, args.data(), n * sizeof(WalkArg), hipMemcpyHostToDevice, s));
-        launch(k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s, (const WalkArg *)(meta + lay.args), (u32)n,
-               (WalkChunk *)(meta + lay.rec), (WalkTail *)(meta + lay.tails));
+        bool period = false;
+        for (const WalkArg & a : args) period |= a.count > 1;
+        launch(period ? k_frame_walk_strided : k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s,
+               (const WalkArg *)(meta + lay.args), (u32)n, (WalkChunk *)(meta + lay.rec), (WalkTail *)(meta + lay.tails));
         if (nrec) HIP_CHECK(hipMemcpyAsync(rec.data(), meta + lay.rec, nrec * sizeof(WalkChunk), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(tails.data(), meta + lay.tails, n * sizeof(WalkTail), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -226,8 +267,9 @@ struct WalkPos {
     WalkArg arg(const u8 * in, size_t in_size, size_t buf_max, u32 limit, u32 rec_base) const {
         return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0, 0, 0};
     }
-    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base) const {  // the chunks that hold a byte of [lo, hi)
-        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi};
+    // the chunks that hold a byte of [lo, hi); with count > 1, of the `count` runs of `run` bytes that start `stride` apart from lo on
+    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base, u64 run = 0, u64 stride = 0, u64 count = 0) const {
+        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi, run, stride, count};
     }
     void take(const WalkTail & t) {
         off = t.off;
@@ -420,8 +462,14 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
 // header-checked and skipped on the device, headers at or beyond its end are never read, so the windows hold only the chunks that
 // share a byte with their frame's range; the first and the last of them are gathered clipped (push_range_segment), and `committed`
 // counts range bytes.  A frame's walk is over at its last chunk, at a header error or at the end of its range.
+// periods (bz3_hip_decompress_device_strided[_many]; only with range; valid as bz3_hip.h demands): per frame (run, stride, count), the frame
+// wants the first w = min(out_sizes[i], base_sizes[i], count run) of the bytes phi(t) = offsets[i] + (t / run) stride + t % run.  A request
+// of one run (after the cut at w) or with stride == run is the contiguous range (offset, w) and takes the range path untouched.  Every
+// other one walks with its period (frame.hpp), so that its windows hold only the chunks that meet a run, up to end = phi(w - 1) + 1; in
+// the gather a chunk [p, p + o) holds the output bytes [t_a, t_b) = [below(p), below(p + o)), below(x) the number of t < w with phi(t) < x,
+// which are contiguous in `out` and one segment (push_strided_segment); `committed` is t_b.
 void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
-                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr) {
+                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr, const u64 * periods = nullptr) {
     struct Frame {
         size_t buf_max = 0, committed = 0;
         u32 decoded = 0;        // chunks decoded and committed
@@ -429,6 +477,12 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         int pending = BZ3_OK;   // the header error the walk stopped at
         bool failed = false;    // a chunk of the current window failed
         u64 lo = 0, hi = 0;     // range: the decoded bytes wanted
+        u64 run = 0, stride = 0, count = 0;  // count > 1: of [lo, hi) only `count` runs of `run` bytes, `stride` apart; buf_max = w
+        u64 below(u64 x) const {             // the number of t < buf_max with phi(t) < x
+            if (x <= lo) return 0;
+            const u64 d = x - lo, i = d / stride, r = d % stride;
+            return std::min<u64>(i >= count ? count * run : i * run + std::min(r, run), buf_max);
+        }
     };
     struct Chunk {
         s32 frame;
@@ -437,7 +491,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     std::vector<Frame> fr((size_t)n);
     std::vector<WalkPos> pos((size_t)n);
     std::vector<char> live((size_t)n, 0);
-    bool any = false;
+    bool any = false, any_period = false;
     for (s32 i = 0; i < n; i++) {
         rcs[i] = BZ3_OK;
         if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
@@ -445,7 +499,16 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
         if (range) {
             fr[i].lo = offsets ? offsets[i] : 0;
+            if (periods) {
+                const u64 run = periods[3 * i], stride = periods[3 * i + 1], W = periods[3 * i + 2] * run;
+                const u64 w = fr[i].buf_max = (size_t)std::min<u64>(fr[i].buf_max, W), runs = w ? (w - 1) / run + 1 : 0;
+                if (runs > 1 && stride != run) {
+                    fr[i].run = run, fr[i].stride = stride, fr[i].count = runs;
+                    any_period = true;
+                }
+            }
             fr[i].hi = fr[i].lo + (u64)fr[i].buf_max < fr[i].lo ? UINT64_MAX : fr[i].lo + (u64)fr[i].buf_max;
+            if (fr[i].count) fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + (fr[i].buf_max - (fr[i].count - 1) * fr[i].run);  // phi(w - 1) + 1
             out_sizes[i] = 0;
         }
     }
@@ -504,7 +567,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 if (!live[i] || fr[i].pending != BZ3_OK || range_walk_over(i)) continue;
                 const u64 from = std::max(fr[i].lo, pos[i].planned), est = (fr[i].hi - from) / pos[i].block_size + 2;
                 const u32 lim = (u32)std::min<u64>({est, (u64)(pos[i].n_blocks - pos[i].done), (u64)(W - win.size()), (u64)(WALK_RECORDS - base)});
-                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base));
+                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base, fr[i].run, fr[i].stride, fr[i].count));
                 who.push_back(i);
                 base += lim;
             }
@@ -588,10 +651,17 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                         x.failed = true;
                         continue;
                     }
-                    if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
+                    if (range && x.count) {  // the chunk's bytes c(u) are the output bytes [ta, tb)
+                        const u64 p = c.rec.out_off, ta = x.below(p), tb = x.below(p + (u64)c.rec.orig);
+                        const u64 c0 = x.lo + (ta / x.run) * x.stride + ta % x.run - p;
+                        push_strided_segment(f.segs, f.clips, f.periods, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, c0, x.run - ta % x.run, x.run,
+                                             x.stride, tb - ta, (u64)(outs[c.frame] + ta), bases && bases[c.frame] ? (u64)(bases[c.frame] + ta) : 0);
+                        x.committed = (size_t)tb;
+                    } else if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
                         const u64 p = c.rec.out_off, a = x.lo > p ? x.lo - p : 0, b = std::min<u64>(x.hi - p, (u64)c.rec.orig), at = p + a - x.lo;
                         push_range_segment(f.segs, f.clips, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, a, b, (u64)(outs[c.frame] + at),
                                            bases && bases[c.frame] ? (u64)(bases[c.frame] + at) : 0);
+                        if (any_period) f.periods.insert(f.periods.end(), STRIDED_PARAMS, 0);
                         x.committed = (size_t)(p + b - x.lo);
                     } else {
                         f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
@@ -849,6 +919,46 @@ BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t ele
     return first_error(n, rcs);
 }
 
+// params: per frame (offset, run, stride, count).  The whole-call checks of the range call, then the validity of every period; the overlap of
+// `out` and a base is judged on the w = min(out_sizes[i], base_sizes[i], count run) bytes the call can touch of each.
+BZIP3_API int bz3_hip_decompress_device_strided_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                     const uint64_t params[], const void * const bases[], const size_t base_sizes[], void * const outs[],
+                                                     size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    std::vector<u64> offsets((size_t)n), periods(3 * (size_t)n);
+    for (s32 i = 0; i < n; i++) {
+        const u64 offset = params[4 * i], run = params[4 * i + 1], stride = params[4 * i + 2], count = params[4 * i + 3];
+        offsets[(size_t)i] = offset;
+        periods[3 * (size_t)i] = run, periods[3 * (size_t)i + 1] = stride, periods[3 * (size_t)i + 2] = count;
+        if (run == 0 || count == 0) continue;  // W = 0
+        const unsigned __int128 W = (unsigned __int128)count * run, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + run;
+        if ((count > 1 && stride < run) || W > UINT64_MAX || last > UINT64_MAX) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], periods[3 * (size_t)i] * periods[3 * (size_t)i + 2]}), x = (u64)outs[i], y = (u64)bases[i];
+        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true, offsets.data(),
+                      periods.data());
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_strided(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t run, uint64_t stride, uint64_t count,
+                                                const void * base, size_t base_size, void * out, size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    const uint64_t params[4] = {offset, run, stride, count};
+    int rc = BZ3_OK;
+    return bz3_hip_decompress_device_strided_many(1, &elem_size, ins, &in_size, params, bases, &base_size, outs, out_size, &rc);
+}
+
 BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * base, size_t base_size, void * out,
                                               size_t * out_size) {
     if (!out_size) return BZ3_ERR_INIT;
@@ -962,6 +1072,41 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
         std::vector<u8> staging;
         sc.open(range_table_bytes((size_t)n));
         copy_segments(v, staging, sc.mem, sc.s, &clips);
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    return rc;
+}
+
+// n tuples of 10 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, c0, first, run, stride, nbytes): of the merge of the `len` bytes at
+// src_off the nbytes bytes c(u) (planes.hpp, "Strided merge"), to dst_off (plus the bytes at base_off unless it is UINT64_MAX), one launch through
+// the segments a strided call's gather makes of them.  stride == run is not normalised away here: it reaches the kernel.
+BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)10 * i;
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || q[3] >= ((u64)1 << 31)) return BZ3_ERR_INIT;
+        if (q[9] && (q[7] == 0 || q[6] == 0 || q[6] > q[7] || q[8] < q[7] || strided_last_byte(q[5], q[6], q[7], q[8], q[9]) >= q[3])) return BZ3_ERR_INIT;
+        any_base |= q[1] != UINT64_MAX;
+    }
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        std::vector<CopySeg> v;
+        std::vector<u64> clips, periods;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)10 * i;
+            push_strided_segment(v, clips, periods, (u64)src + q[0], q[3], q[4] & 0xff, q[9] ? q[5] : 0, q[6], q[7], q[8], q[9], (u64)dst + q[2],
+                                 q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+        }
+        std::vector<u8> staging;
+        sc.open(strided_table_bytes((size_t)n));
+        copy_segments(v, staging, sc.mem, sc.s, &clips, &periods);
         HIP_CHECK(hipStreamSynchronize(sc.s));
     } catch (...) {
         rc = BZ3_ERR_INIT;

@@ -127,6 +127,13 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
 // or before lo (planned + orig <= lo) or is empty with its header checked as any other, but without a record and without using
 // any of `limit`, so a frame may hold any number of such chunks before its range.  The capacity check is not made
 // (the host passes buf_max = SIZE_MAX): a range is clipped, never too big.
+//
+// A range walk with a period (WalkArg::count > 1; bz3_hip_decompress_device_strided, api_frames.hip) wants the output bytes of `count`
+// runs of `run` bytes that start `stride` bytes apart from lo on (stride >= run > 0), the last of them cut at hi.  A chunk is recorded
+// iff it meets a run: i0 is the first run that ends behind the chunk's first byte, and the chunk meets it iff that run exists and
+// starts before the chunk's end.  A chunk that lies in a gap between two runs is header-checked and skipped like one before the range.
+// One 64-bit division per chunk, on the one lane that follows the chain.  A launch in which no frame has a period is
+// k_frame_walk_many as it was; one with such a frame is k_frame_walk_strided, where a lane with count <= 1 executes the walk above.
 struct WalkChunk {
     u64 in_off;   // offset of the chunk header in the frame
     u64 out_off;  // output bytes of the chunks before it (planned)
@@ -142,6 +149,7 @@ struct WalkArg {
     u32 block_size, n_blocks;  // from the frame header (ignored on a first visit)
     u32 range;                 // != 0: a range walk over the output bytes [lo, hi)
     u64 lo, hi;
+    u64 run, stride, count;    // count > 1: only the chunks that meet one of `count` runs of `run` bytes, `stride` apart from lo on
 };
 struct WalkTail {
     u64 off, planned;  // resume state after the last well-formed chunk read
@@ -154,8 +162,9 @@ struct WalkTail {
 static_assert(sizeof(WalkChunk) % 16 == 0 && sizeof(WalkArg) % 8 == 0 && sizeof(WalkTail) % 8 == 0, "walk records are packed arrays");
 constexpr u32 WALK_THREADS = 64;
 
-__global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
-                                                                  WalkTail * __restrict__ tails) {
+// PERIOD: some frame of the launch walks with a period (k_frame_walk_strided); without it the fields of the period are never looked at.
+template <bool PERIOD>
+__device__ __forceinline__ void frame_walk(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec, WalkTail * __restrict__ tails) {
     const u32 i = blockIdx.x * WALK_THREADS + threadIdx.x;
     if (i >= n) return;
     const WalkArg a = args[i];
@@ -179,7 +188,12 @@ __global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg 
         err = frame_chunk_check(frame + off, a.in_size - off, block_size, (size_t)a.buf_max, (size_t)planned, &size, &orig);
         if (err != BZ3_OK) break;
         const u64 data = off + 8;
-        if (!a.range || (orig > 0 && planned + (u64)orig > a.lo)) {
+        bool wanted = !a.range || (orig > 0 && planned + (u64)orig > a.lo);
+        if (PERIOD && wanted && a.count > 1) {
+            const u64 i0 = planned < a.lo + a.run ? 0 : (planned - a.lo - a.run) / a.stride + 1;
+            wanted = i0 < a.count && a.lo + i0 * a.stride < planned + (u64)orig;
+        }
+        if (wanted) {
             WalkChunk & w = rec[a.rec_base + c];
             w.in_off = off;
             w.out_off = planned;
@@ -201,6 +215,18 @@ __global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg 
     t.err = err;
     t.block_size = block_size;
     t.n_blocks = n_blocks;
+}
+
+__global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
+                                                                  WalkTail * __restrict__ tails) {
+    frame_walk<false>(args, n, rec, tails);
+}
+
+// k_frame_walk_many for a launch in which some frame walks with a period.  (A kernel of its own, as the segment kernels of planes.hpp are:
+// the walks without a period keep the code and the registers they had.)
+__global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_strided(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
+                                                                     WalkTail * __restrict__ tails) {
+    frame_walk<true>(args, n, rec, tails);
 }
 
 }  // namespace bz3

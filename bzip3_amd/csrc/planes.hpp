@@ -55,6 +55,31 @@
 // of this tile (16-byte path: the lane lies inside the clip; byte path: the byte does), before the barrier; what else phase 1 read
 // of the base belongs to other tiles and lands in LDS outside [s0 - origin, s1 - origin); a tail byte is read and written by one
 // thread.  dst and base share the clip's coordinates, so dst == base pairs every byte with itself.
+//
+// Strided merge (CopySeg::mode & PLANES_STRIDED; bz3_hip_decompress_device_strided, api_frames.hip).  A strided range wants of a chunk a
+// periodic set of its bytes: chunk byte c0, the `first` bytes from it on (the rest of the run c0 lies in), then runs of `run` bytes
+// whose starts lie `stride` bytes apart, nbytes in all.  In the output they are CONTIGUOUS, dst[0, nbytes), so the chunk is one segment
+// with one destination range, whatever the number of runs in it.  Destination byte u comes from chunk byte
+//     c(u) = c0 + u                                                    (u < first)
+//     c(u) = c0 + first + (stride - run) + (v / run) stride + v % run  (v = u - first)
+// and chunk byte c lives at slot[(c % k) m + c / k] for c < m k (m = len / k), at slot[c] in the tail: merge_k.  strided_tile tiles the
+// DESTINATION: a workgroup owns the destination bytes [4080 k t, 4080 k (t + 1)) cut at dst's 16-byte boundaries as merge_tile's are,
+// lane l fills LDS with the 16 k destination bytes from 4080 k t + 16 k l on, in destination order, and phase 2 is store_from_lds.  A
+// lane whose 16 k bytes are 16 whole elements of one run (they lie inside one run, inside [0, nbytes) and inside the element part of
+// the chunk, and the first of them is byte 0 of an element) takes k plane granules and interleave<K> (k = 1: one load16_any) and, with a base, load_elems16 of the
+// base and add_bytes; every other lane (one that crosses a run boundary, the chunk's tail or the segment's end, or whose bytes do not
+// start an element) moves its bytes one by one.  RUNS SHORTER THAN 16 ELEMENTS THEREFORE GO WHOLLY THROUGH THE BYTE PATH: correct and
+// slow ("Strided range decode").  A lane divides once (32 bits: every quantity is below the chunk's 2^31 bytes; a run
+// longer than that is clamped, which changes no c(u)) and then steps.  Every granule loaded from the slot holds a byte of the chunk, every
+// granule loaded from the base a byte of base[0, nbytes) -- the byte path loads bytes -- and nothing outside dst[0, nbytes) is written.
+// In place (dst == base): dst and base share the segment's coordinates, so dst == base pairs every byte with itself.  The bytes a tile
+// stores, [s0, s1), are its own (the tiles' store ranges partition dst[0, nbytes), the segments' destinations are disjoint); they lie
+// within the destination bytes of its 256 lanes, [4080 k t, 4080 k t + 4096 k) (s1 <= dst + 4080 k (t + 1) + 15), so every one of
+// them was read from the base in phase 1 by a lane of this tile (16-byte path: the lane's 16 k bytes lie inside [0, nbytes); byte
+// path: the byte does), before the barrier, and is stored in phase 2, after it.  load_elems16 keeps of the aligned granules it reads
+// only the lane's own 16 k bytes, so what else phase 1 takes from the base are the 256th lane's bytes and the bytes below s0, which
+// belong to other tiles, may have been overwritten already and land in LDS outside [s0 - origin, s1 - origin), where phase 2 never
+// reads.
 #pragma once
 #include "frame.hpp"
 
@@ -66,6 +91,8 @@ constexpr u32 PLANE_STRIDE = PLANES_LOAD_ELEMS + 16;        // LDS bytes per pla
 constexpr u32 PLANES_LDS_BYTES = 8 * PLANE_STRIDE;          // >= 8 * PLANES_LOAD_ELEMS + 16, the merge layout
 constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = elem_size | PLANES_INVERSE for merge
 constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments alone)
+constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments alone)
+constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
 
 __host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // Workgroups of a split / merge segment: one per PLANES_TILE_ELEMS elements; a block shorter than an element still has its tail.
@@ -499,6 +526,134 @@ __global__ void __launch_bounds__(COPY_THREADS) k_range_segments(const CopySeg *
         const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
         if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
         else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+    }
+}
+
+// ---- strided merge ------------------------------------------------------------------------------------------------------------------
+// Workgroups of a strided merge of nbytes destination bytes: one per PLANES_TILE_ELEMS k of them.
+__host__ __device__ inline u64 strided_tiles(u64 nbytes, u64 k) { return (nbytes + k * PLANES_TILE_ELEMS - 1) / (k * PLANES_TILE_ELEMS); }
+
+// Tile `tile` of a strided merge of the `len` < 2^31 bytes at `src`: destination bytes [0, nbytes) from the chunk bytes c(u) (the head of
+// this file; gap = stride - run), to dst; with D, plus base[0, nbytes) (which may be `dst`).
+template <int K, bool D>
+__device__ __forceinline__ void strided_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, u32 c0, u32 first, u32 run, u32 gap, u32 nbytes, u32 tile, u8 * lds) {
+    const u32 m = len / K, ua = tile * (PLANES_TILE_ELEMS * K);
+    const u32 u0 = ua + 16 * K * threadIdx.x;
+    if (u0 < nbytes) {
+        u32 c, left;  // the chunk byte of destination byte u0, and what is left of its run
+        if (u0 < first) {
+            c = c0 + u0;
+            left = first - u0;
+        } else {
+            const u32 v = u0 - first, q = v / run;
+            c = c0 + u0 + (q + 1) * gap;
+            left = run - (v - q * run);
+        }
+        if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
+            u32 w[4 * K];
+            if constexpr (K == 1) {
+                const uint4 v = load16_any((u64)src + c);
+                w[0] = v.x;
+                w[1] = v.y;
+                w[2] = v.z;
+                w[3] = v.w;
+            } else {
+                u32 p[K][4];
+#pragma unroll
+                for (int q = 0; q < K; q++) {
+                    const uint4 v = load16_any((u64)src + (u64)q * m + c / K);
+                    p[q][0] = v.x;
+                    p[q][1] = v.y;
+                    p[q][2] = v.z;
+                    p[q][3] = v.w;
+                }
+                interleave<K>(p, w);
+            }
+            if (D) {
+                u32 b[4 * K];
+                load_elems16<K>((u64)base + u0, b);
+#pragma unroll
+                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+        } else {
+            const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
+            for (u32 u = u0; u < u1; u++) {
+                const u8 x = src[c < m * K ? (c % K) * m + c / K : c];
+                lds[u - ua] = D ? (u8)(x + base[u]) : x;
+                c++;
+                if (--left == 0) {
+                    c += gap;
+                    left = run;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const u64 d0 = (u64)dst, dend = d0 + nbytes;
+    const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ua, dend);
+    const u64 s1 = ua + PLANES_TILE_ELEMS * K >= nbytes ? dend : align16_up_to(d0 + ua + PLANES_TILE_ELEMS * K, dend);
+    store_from_lds<K>(lds, d0 + ua, s0, s1);  // at most 255 K + 1 granules
+}
+
+// k_range_segments for a launch in which some segment is a strided merge: periods[5 i .. 5 i + 4] are segment i's c0, first, run, stride
+// and nbytes (read for segments with PLANES_STRIDED alone); tile_start counts such a segment's workgroups with strided_tiles.  The other
+// segments take what they take in k_range_segments.  (A kernel of its own, as the three before it: launches without a strided segment
+// keep the four kernels above as they are.)
+__global__ void __launch_bounds__(COPY_THREADS) k_strided_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                   const u64 * __restrict__ clips, const u64 * __restrict__ periods) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    const u32 tile = b - tile_start[lo];
+    const u8 * src = (const u8 *)sg.src;
+    const u8 * base = (const u8 *)sg.base;
+    u8 * dst = (u8 *)sg.dst;
+    if (sg.mode & PLANES_STRIDED) {
+        const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
+        const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
+        const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)
+        const u32 gap = nbytes > first ? (u32)(pp[3] - pp[2]) : 0;
+        const u32 len = (u32)sg.len;
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (sg.mode & PLANES_CLIP) {
+        const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (!sg.base) {
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
+        else copy_segment_tile(sg, tile);
+    } else if ((sg.mode & 0xff) > 1) {
+        planes_tile<true>(sg, tile, (u8 *)lds);
+    } else {
+        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
+        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+        if (sg.mode & PLANES_INVERSE) delta1_tile<true>(src, base, dst, sg.len, g_first, g_last);
+        else delta1_tile<false>(src, base, dst, sg.len, g_first, g_last);
     }
 }
 

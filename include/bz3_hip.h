@@ -258,6 +258,48 @@ BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t ele
  * elem_size.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
 
+/* Strided range decode: a slice along any dimension of what a frame decodes to -- `count` runs of `run` bytes whose starts lie `stride`
+ * bytes apart from `offset` on -- at the cost of the chunks that hold a byte of a run.  X, p_j, o_j and T are as in the range contract
+ * above.  W = count * run; w = min(*out_size, W), with a base min(*out_size, base_size, W); for t < w
+ *     phi(t) = offset + (t / run) * stride + t % run,
+ * which is strictly increasing; end = phi(w - 1) + 1.  The call is pread(2) of the bytes phi(0), phi(1), ... of X:
+ *   it writes out[t] = X[phi(t)] for t < r -- with a base (X[phi(t)] + base[t]) mod 256 --, r the number of t < w with phi(t) < T (a
+ *   prefix, because phi increases), and returns BZ3_OK with *out_size = r.  BZ3_ERR_DATA_TOO_BIG is never returned.
+ *   `base` holds the base's bytes OF THE SLICE, in output order: base[t] pairs with out[t].  `out` may be exactly `base`; any other
+ *   overlap of out[0, w) and base[0, w) is BZ3_ERR_INIT before any write.
+ *   Validity (a violation is BZ3_ERR_INIT for the whole call before any write, exactly as a bad elem_size is): stride >= run wherever
+ *   count > 1 and run > 0; count * run must not overflow 64 bits; offset + (count - 1) * stride + run must not overflow 64 bits.  run == 0
+ *   or count == 0 is allowed and means W = 0 (nothing else of such a period is looked at): the frame header alone is checked, as for
+ *   w = 0 in the range call.
+ *   The frame header is always checked.  The header of chunk j is read and checked iff w > 0 and p_j < end, with the three checks of
+ *   the range call.  Chunk j is DECODED iff o_j > 0 and [p_j, p_j + o_j) holds phi(t) for some t < w; it is then decoded whole, with
+ *   its CRC and every per-block check.  A chunk that lies before the first run, or IN A GAP BETWEEN TWO RUNS, is header-checked and
+ *   skipped: a corrupt payload there is not noticed.
+ *   The result is the first event in chunk order, a header error or a failed chunk: its code is returned, the output bytes t with
+ *   phi(t) below that chunk's p_j are committed (a prefix), *out_size is their count, nothing else of `out` is written.
+ *   Equivalence: a request with count == 1 or with stride == run is the contiguous range (offset, W): it returns byte for byte what
+ *   bz3_hip_decompress_device_range returns for *out_size = min(*out_size, W), with the same return code and *out_size, through the
+ *   same launches.
+ * Within a decoded chunk the wanted bytes are gathered by one launch per window (planes.hpp k_strided_segments), a chunk being one
+ * segment however many runs it holds.  Runs of 16 elements or more move 16 elements per lane; shorter ones byte by byte.
+ * _many follows bz3_hip_decompress_device_range_many word for word: n independent frames on ONE GPU (the same frame may appear more than
+ * once), NULL elem_sizes, bases and bases[i] as there, the same whole-call checks, rcs[], windows across frames and headroom rule.
+ * params holds four u64 per frame: offset, run, stride, count; NULL params is BZ3_ERR_INIT.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_decompress_device_strided(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t run,
+                                                uint64_t stride, uint64_t count, const void * base, size_t base_size, void * out,
+                                                size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device_strided_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                     const uint64_t params[], const void * const bases[], const size_t base_sizes[],
+                                                     void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: one launch of the gather of a strided call: n tuples of 10 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, c0,
+ * first, run, stride, nbytes) relative to `src` / `base` / `dst`.  Of merge_k(the len bytes at src_off) the nbytes bytes c(0), c(1), ...
+ * are stored at dst_off, plus the nbytes bytes at base_off unless base_off is UINT64_MAX: c(u) = c0 + u for u < first, else with
+ * v = u - first, c(u) = c0 + first + (stride - run) + (v / run) * stride + v % run; 1 <= first <= run <= stride.  A tuple with
+ * nbytes <= first is one contiguous piece and becomes the clipped or whole segment of bz3_hip_debug_range; stride == run is not
+ * normalised away and reaches the strided kernel.  `dst` may be `base` with dst_off == base_off.  BZ3_ERR_INIT for a tuple whose last
+ * chunk byte c(nbytes - 1) is not below len, for len >= 2^31 and for what bz3_hip_debug_range refuses.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
