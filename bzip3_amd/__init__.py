@@ -99,6 +99,10 @@ def _declare(L, strict=True):
         "bz3_hip_decompress_device_strided_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
                                                              C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_strided": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_decompress_device_select": (C.c_int, [u32, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), vp, sz, vp, C.POINTER(sz)]),
+        "bz3_hip_decompress_device_select_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)),
+                                                            C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_select": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), C.c_uint64]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -655,6 +659,80 @@ def decompress_tensor_strided(frame, offset, run, stride, count, out=None, plane
         raise Bz3Error(e.code, "bz3_hip_decompress_device_strided", e.outs[0]) from None
 
 
+def decompress_tensors_select(frames, offsets, strides, counts, pieces, outs=None, planes=1, bases=None, lib=None):
+    """An index set of what every frame decodes to, for many frames in ONE call (bz3_hip_decompress_device_select_many): of frame i
+    counts[i] periods whose starts lie strides[i] bytes apart from offsets[i] on, and of every period the pieces pieces[i], a sequence of
+    (start, len) relative to the period's start, ascending and disjoint -- an index_select along any dimension of a row-major tensor
+    with a strictly increasing index.  Only the chunks that hold a byte of a piece are decoded, each of them once however many pieces it
+    holds; chunks that lie wholly in a gap between two pieces are skipped like those before the first.  Returns uint8 tensors, shorter
+    than counts[i] * sum(len) where the set runs past the end of the frame (pread's rule; never an error).  `outs`: contiguous uint8
+    tensors of at least counts[i] * sum(len) bytes to read into; by default views of one allocation.  `planes` as in decompress_tensors.
+    `bases[i]`: None, or the base's bytes OF THE INDEX SET in output order (at least as many as are asked for); outs[i] may be bases[i].
+    ValueError for a negative number, for pieces that overlap or descend, for a last piece that ends behind strides[i] where
+    counts[i] > 1, and for a set that does not fit 64 bits.  The same frame may appear more than once.  Raises Bz3Error with .index /
+    .codes / .outs (per frame the bytes committed before its error) as decompress_tensors does.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
+    lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
+    if any(len(col) != n for col in cols) or len(lists) != n:
+        raise ValueError(f"decompress_tensors_select: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists")
+    params = list(zip(*cols))
+    nbytes = []
+    for i, ((o, s, c), pl) in enumerate(zip(params, lists)):
+        if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
+            raise ValueError("decompress_tensors_select: offsets, strides, counts and pieces must not be negative")
+        if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
+            raise ValueError(f"decompress_tensors_select: the pieces of frame {i} do not ascend")
+        L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
+        if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
+            raise ValueError(f"decompress_tensors_select: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
+        nbytes.append(c * L)
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
+    dev = _same_device(frames, "decompress_tensors_select")
+    L = lib or load()
+    if outs is None:
+        outs = _carve(sum(nbytes), nbytes, dev)
+    else:
+        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
+        if len(outs) != n:
+            raise ValueError(f"decompress_tensors_select: {n} frames and {len(outs)} outputs")
+        _same_device(frames + outs, "decompress_tensors_select")
+    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
+        if o.numel() < w or (b is not None and b.numel() < w):
+            raise ValueError(f"decompress_tensors_select: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
+    torch.cuda.synchronize(dev)
+    out_sizes = (C.c_size_t * n)(*nbytes)
+    rcs = (C.c_int * n)()
+    arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
+    rc = L.bz3_hip_decompress_device_select_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                                 (C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]),
+                                                 (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs]), _ptrs_or_null(bases),
+                                                 (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, nbytes)]), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, "bz3_hip_decompress_device_select_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def decompress_tensor_select(frame, offset, stride, count, pieces, out=None, planes=1, base=None, lib=None):
+    """Of `count` periods, `stride` bytes apart from `offset` on, the pieces (start, len) of what `frame` decodes to
+    (bz3_hip_decompress_device_select): decompress_tensors_select for one frame; Bz3Error's `.out` holds the bytes committed before the
+    error."""
+    try:
+        return decompress_tensors_select([frame], [offset], [stride], [count], [pieces], None if out is None else [out], planes=planes, bases=None if base is None else [base],
+                                         lib=lib)[0]
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_decompress_device_select", e.outs[0]) from None
+
+
 # ---- typed tensors ------------------------------------------------------------------------------------------------------------
 # The byte-plane element size pack_tensor uses when `planes` is None, by dtype name: the component size where the measurements of
 # DESIGN.md ("Typed tensors") show the planes frame smaller than the interleaved one, 1 where they show it larger or no different
@@ -1005,40 +1083,35 @@ def _slice_of(p, sl, what):
     return shape[:dim] + (stop - start,) + shape[dim + 1 :], (start * inner, (stop - start) * inner, shape[dim] * inner, count)
 
 
-def _unpack_slices_many(ps, slices, outs, lib, bases):
-    """The slices slices[i] = (dim, start, stop) of every PackedTensor (None: the whole tensor), in ONE
-    bz3_hip_decompress_device_strided_many call.  bases[i]: the same slice of the base."""
+def _unpack_parts_many(ps, shapes, sizes, whole, outs, lib, bases, what, decode):
+    """What the partial unpack calls share.  Tensor i comes back with shapes[i] from the sizes[i] bytes that decode(raws, braws) reads
+    into the uint8 views raws (a list of the tensors it got, shorter where a frame ran out); bases[i]: the same part of the base, `what`
+    its name in messages; whole: the tensors that come back whole."""
     import torch
 
-    shapes, params = [], []
-    for i, (p, sl) in enumerate(zip(ps, slices)):
-        shape, q = _slice_of(p, sl, f"tensor {i}")
-        shapes.append(shape)
-        params.append(q)
     bases = _bases_arg(bases, len(ps))
     braws = []
-    for i, (p, b, q, shape) in enumerate(zip(ps, bases, params, shapes)):
+    for i, (p, b, w, shape) in enumerate(zip(ps, bases, sizes, shapes)):
         if p.delta and b is None:
             raise ValueError(f"unpack: tensor {i} was packed against a base, which is needed to restore it")
         if not p.delta:
             b = None
         elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != shape:
-            raise ValueError(f"unpack: base {i} must hold the same slice of the base: {p.dtype} {shape}")
-        braws.append(_base_bytes(b, q[1] * q[3], p.frame.device, f"base {i}"))
+            raise ValueError(f"unpack: base {i} must hold the same {what} of the base: {p.dtype} {shape}")
+        braws.append(_base_bytes(b, w, p.frame.device, f"base {i}"))
     dev = _same_device([p.frame for p in ps], "unpack")
     if outs is None:
-        raws = _carve(0, [q[1] * q[3] for q in params], dev)  # every output at a multiple of 16 bytes, so that any dtype can view it
+        raws = _carve(0, sizes, dev)  # every output at a multiple of 16 bytes, so that any dtype can view it
     else:
         raws = []
         for p, o, shape in zip(ps, outs, shapes):
             if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or tuple(o.shape) != shape or not o.is_contiguous():
-                raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and of the slice's shape")
+                raise TypeError(f"unpack: `out` must be a contiguous tensor of the packed dtype and of the {what}'s shape")
             raws.append(_as_bytes(o, "out"))
-    got = decompress_tensors_strided([p.frame for p in ps], *zip(*params), raws, planes=[p.planes for p in ps], bases=braws, lib=lib)
-    for i, (g, q) in enumerate(zip(got, params)):
-        if g.numel() != q[1] * q[3]:
-            raise Bz3Error(BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} holds {g.numel()} of the {q[1] * q[3]} bytes of its slice;", g)
-    whole = [i for i, sl in enumerate(slices) if sl is None]
+    got = decode(raws, braws)
+    for i, (g, w) in enumerate(zip(got, sizes)):
+        if g.numel() != w:
+            raise Bz3Error(BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} holds {g.numel()} of the {w} bytes of its {what};", g)
     if whole:  # a tensor that comes back whole must be all its frame decodes to (unpack_tensor fails with BZ3_ERR_DATA_TOO_BIG on a longer frame): one walk over those frames' chunk headers
         n = len(whole)
         need, rcs = (C.c_size_t * n)(), (C.c_int * n)()
@@ -1047,6 +1120,19 @@ def _unpack_slices_many(ps, slices, outs, lib, bases):
             if d != ps[i].nbytes:
                 raise Bz3Error(BZ3_ERR_DATA_TOO_BIG if d > ps[i].nbytes else BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} decodes to {d} bytes, the tensor has {ps[i].nbytes};")
     return list(outs) if outs is not None else [_from_bytes(r, p.dtype, shape) for r, p, shape in zip(raws, ps, shapes)]
+
+
+def _unpack_slices_many(ps, slices, outs, lib, bases):
+    """The slices slices[i] = (dim, start, stop) of every PackedTensor (None: the whole tensor), in ONE
+    bz3_hip_decompress_device_strided_many call.  bases[i]: the same slice of the base."""
+    shapes, params = [], []
+    for i, (p, sl) in enumerate(zip(ps, slices)):
+        shape, q = _slice_of(p, sl, f"tensor {i}")
+        shapes.append(shape)
+        params.append(q)
+    frames, planes = [p.frame for p in ps], [p.planes for p in ps]
+    return _unpack_parts_many(ps, shapes, [q[1] * q[3] for q in params], [i for i, sl in enumerate(slices) if sl is None], outs, lib, bases, "slice",
+                              lambda raws, braws: decompress_tensors_strided(frames, *zip(*params), raws, planes=planes, bases=braws, lib=lib))
 
 
 def unpack_tensor_slice(p, dim, start, stop, out=None, base=None, lib=None):
@@ -1064,6 +1150,105 @@ def unpack_tensor_slice(p, dim, start, stop, out=None, base=None, lib=None):
     copy; `out` may be it when it is contiguous.  PackedTensor.base_crc covers the whole base and cannot be checked against a slice of it:
     the caller vouches that this is a slice of the right base."""
     return _unpack_slices_many([p], [(dim, start, stop)], None if out is None else [out], lib, [base])[0]
+
+
+def _index_list(index, what):
+    """`index` (a list, a numpy array or a 1-D integer tensor; a device tensor is copied to the host) as a list of ints."""
+    if hasattr(index, "detach") and hasattr(index, "cpu"):  # a torch tensor
+        if index.dim() != 1 or index.is_floating_point() or index.is_complex() or str(index.dtype) == "torch.bool":
+            raise ValueError(f"{what}: the index must be a 1-D integer tensor")
+        return [int(v) for v in index.detach().cpu().tolist()]
+    if hasattr(index, "ndim") and hasattr(index, "tolist"):  # a numpy array
+        if index.ndim != 1 or index.dtype.kind not in "iu":
+            raise ValueError(f"{what}: the index must be a 1-D integer array")
+        return [int(v) for v in index.tolist()]
+    out = []
+    for v in index:
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{what}: the index must hold integers")
+        out.append(int(v))
+    return out
+
+
+def _index_of(p, sel, what):
+    """(shape, (offset, stride, count, pieces), index) of sel = (dim, index), an index_select of a PackedTensor along `dim` with a strictly
+    increasing index: runs of consecutive indices are one piece each.  (shape, strided request, None) for sel = None, the whole
+    tensor, and for a slice (dim, start, stop), as one piece."""
+    if sel is None or len(sel) == 3:
+        shape, (o, r, s, c) = _slice_of(p, sel, what)
+        return shape, (o, s, c, [(0, r)]), None
+    shape, (_, _, stride, count) = _slice_of(p, (sel[0], 0, 0), what)  # (validates p and dim)
+    dim = int(sel[0]) % len(p.shape)
+    size = p.shape[dim]
+    inner = stride // size if size else 0
+    idx = _index_list(sel[1], what)
+    if any(not 0 <= i < size for i in idx):
+        raise ValueError(f"{what}: index out of range for a dimension of {size}")
+    if any(a >= b for a, b in zip(idx, idx[1:])):
+        raise ValueError(f"{what}: the index must be strictly increasing here")
+    pieces = []
+    for i in idx:
+        if pieces and pieces[-1][0] + pieces[-1][1] == i * inner:
+            pieces[-1] = (pieces[-1][0], pieces[-1][1] + inner)
+        else:
+            pieces.append((i * inner, inner))
+    return tuple(p.shape[:dim]) + (len(idx),) + tuple(p.shape[dim + 1 :]), (0, stride, count if idx else 0, pieces), idx
+
+
+def _unpack_index_many(ps, sels, outs, lib, bases):
+    """For every PackedTensor sels[i] = (dim, index) (strictly increasing), a slice (dim, start, stop) or None (the whole tensor), in ONE
+    bz3_hip_decompress_device_select_many call.  bases[i]: the same index_select of the base."""
+    shapes, reqs = [], []
+    for i, (p, sel) in enumerate(zip(ps, sels)):
+        shape, q, _ = _index_of(p, sel, f"tensor {i}")
+        shapes.append(shape)
+        reqs.append(q)
+    frames, planes = [p.frame for p in ps], [p.planes for p in ps]
+    return _unpack_parts_many(ps, shapes, [q[2] * sum(l for _, l in q[3]) for q in reqs], [i for i, sel in enumerate(sels) if sel is None], outs, lib, bases, "part",
+                              lambda raws, braws: decompress_tensors_select(frames, *zip(*reqs), raws, planes=planes, bases=braws, lib=lib))
+
+
+def _sorted_unique(index, what):
+    """(the index as a list, its sorted unique values, for every entry its place among those; None where the index is strictly increasing)."""
+    idx = _index_list(index, what)
+    if all(a < b for a, b in zip(idx, idx[1:])):
+        return idx, idx, None
+    uniq = sorted(set(idx))
+    where = {v: j for j, v in enumerate(uniq)}
+    return idx, uniq, [where[v] for v in idx]
+
+
+def unpack_tensor_index(p, dim, index, out=None, base=None, lib=None):
+    """x.index_select(dim, index) of the tensor x a PackedTensor holds, contiguous, in p.dtype, on the frame's GPU, without the whole tensor
+    ever existing there (bz3_hip_decompress_device_select): chosen experts of an [E, ...] tensor, rows of an embedding table, columns.
+    `index`: a list, a numpy array or a 1-D integer tensor (a device tensor is copied to the host; the call is synchronous anyway) with
+    values in [0, p.shape[dim]), else ValueError.  With e the element's bytes and inner = e * prod(shape[dim + 1:]), every run of
+    consecutive indices i .. i + n - 1 is one piece (i * inner, n * inner) of prod(shape[:dim]) periods shape[dim] * inner bytes apart.
+    Only the chunks of the frame that hold a byte of a piece are decoded, each once however many pieces it holds.  Pieces shorter than 16
+    elements of p.planes bytes are gathered byte by byte: correct and slow.  An index that is not strictly increasing (a permutation,
+    duplicates) decodes its sorted unique values and finishes with one torch.index_select on that result, which then exists beside the
+    output.  A negative `dim` counts from the end.  `out`: a contiguous tensor of p.dtype and of the result's shape.  A tensor packed
+    against a base needs `base`: THE SAME index_select of the base, of the dtype and the result's shape (any strides; `out` may be it
+    when it is contiguous); there the index must be strictly increasing, else ValueError.  PackedTensor.base_crc covers the whole base
+    and cannot be checked against a part of it: the caller vouches that this is the right base.  An empty index returns an empty tensor
+    of the result's shape.  Bz3Error if the frame fails or returns fewer bytes than asked of it."""
+    import torch
+
+    idx, uniq, where = _sorted_unique(index, "unpack_tensor_index")
+    if where is None:
+        return _unpack_index_many([p], [(dim, idx)], None if out is None else [out], lib, [base])[0]
+    if isinstance(p, PackedTensor) and p.delta:
+        raise ValueError("unpack_tensor_index: a tensor packed against a base takes a strictly increasing index (its base is given in the index's order)")
+    part = _unpack_index_many([p], [(dim, uniq)], None, lib, [None])[0]
+    d = int(dim) % len(p.shape)
+    shape = tuple(p.shape[:d]) + (len(idx),) + tuple(p.shape[d + 1 :])
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != p.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and of the result's shape")
+    order = torch.tensor(where, dtype=torch.int64, device=part.device)
+    if out is None:
+        return torch.index_select(part, d, order)
+    torch.index_select(part, d, order, out=out)
+    return out
 
 
 def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None, checksum=True):
@@ -1087,7 +1272,7 @@ def pack_state_dict(sd, block_size=16 << 20, planes=None, lib=None, base=None, c
     return dict(zip(names, _pack_many([sd[k] for k in names], block_size, planes, lib, bases, checksum)))
 
 
-def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None, verify=False, slices=None):
+def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=True, rows=None, verify=False, slices=None, index=None):
     """The tensors of pack_state_dict's result, decoded in ONE batched call (bz3_hip_decompress_device_delta_many).  `base`: the dict
     pack_state_dict was given; every tensor packed against a base needs its entry (unpack_tensor's rules and check_base).  With
     inplace=True those base tensors themselves are updated and returned (no second copy of the model in memory); tensors packed
@@ -1102,8 +1287,63 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
     x.narrow(dim, start, stop - start) (unpack_tensor_slice), the names in `rows` as their rows and the others whole, all of them through
     ONE bz3_hip_decompress_device_strided_many call.  `base`, check_base, verify and inplace are as with `rows`: the whole base dict,
     every base checked whole, its slice taken here; ValueError with verify=True or inplace=True.  A name in both `rows` and `slices`:
-    ValueError.  slices=None runs what the function ran before it had the argument."""
+    ValueError.  slices=None runs what the function ran before it had the argument.  `index`: {name: (dim, index)}: those tensors come back
+    as x.index_select(dim, index) (unpack_tensor_index; an index that is not strictly increasing is sorted and made unique for the decode
+    and restored by one torch.index_select, which a tensor packed against a base does not allow), the names in `rows` and `slices` as
+    there and the others whole, all of them through ONE bz3_hip_decompress_device_select_many call.  `base`, check_base, verify and
+    inplace are as with `slices`.  A name in more than one of `rows`, `slices` and `index`: ValueError.  index=None runs what the function
+    ran before it had the argument."""
     names = list(packed)
+    if index is not None:
+        if verify:
+            raise ValueError("unpack_state_dict: verify=True and index do not go together (the checksum covers the whole tensor)")
+        if inplace:
+            raise ValueError("unpack_state_dict: index and inplace=True do not go together")
+        want = {k: (0, int(r[0]), int(r[1])) for k, r in (rows or {}).items()}
+        for k, sl in (slices or {}).items():
+            if k in want:
+                raise ValueError(f"unpack_state_dict: {k!r} is in both rows and slices")
+            want[k] = tuple(sl)
+        order = {}
+        for k, (dim, idx) in index.items():
+            if k in want:
+                raise ValueError(f"unpack_state_dict: {k!r} is in index and in rows or slices")
+            if k in packed:
+                _, uniq, order[k] = _sorted_unique(idx, repr(k))
+                want[k] = (dim, uniq)
+            else:
+                want[k] = (dim, idx)
+        unknown = [k for k in want if k not in packed]
+        if unknown:
+            raise ValueError(f"unpack_state_dict: a part of {unknown[0]!r}, which is not in the dict")
+        if not names:
+            return {}
+        import torch
+
+        ps = [packed[k] for k in names]
+        sels = [want.get(k) for k in names]
+        for k, p, sel in zip(names, ps, sels):  # (every request is validated before anything is read)
+            _index_of(p, sel, repr(k))
+            if order.get(k) is not None and p.delta:
+                raise ValueError(f"unpack_state_dict: {k!r} was packed against a base and takes a strictly increasing index")
+        bases, whole = [], []
+        L = lib or load()
+        for k, p, sel in zip(names, ps, sels):
+            b = base.get(k) if base is not None and p.delta else None
+            fits = isinstance(b, torch.Tensor) and b.dtype == p.dtype and tuple(b.shape) == tuple(p.shape)
+            # the whole base is at hand here, for the tensors read in part too: check it as unpack_tensor does, before anything is decoded
+            whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}") if check_base and fits and p.base_crc is not None else None)
+            if fits and sel is not None and len(sel) == 3:
+                b = b.narrow(int(sel[0]) % len(p.shape), int(sel[1]), int(sel[2]) - int(sel[1]))
+            elif fits and sel is not None:
+                b = b.index_select(int(sel[0]) % len(p.shape), torch.tensor(sel[1], dtype=torch.int64, device=b.device))
+            bases.append(b)
+        _check_bases(ps, whole, [repr(k) for k in names], L)
+        got = dict(zip(names, _unpack_index_many(ps, sels, None, lib, bases)))
+        for k, where in order.items():
+            if where is not None:
+                got[k] = torch.index_select(got[k], int(index[k][0]) % len(packed[k].shape), torch.tensor(where, dtype=torch.int64, device=got[k].device))
+        return got
     if slices is not None:
         if verify:
             raise ValueError("unpack_state_dict: verify=True and slices do not go together (the checksum covers the whole tensor)")

@@ -46,25 +46,35 @@ constexpr size_t range_table_bytes(size_t nseg) { return ((copy_table_bytes(nseg
 // The same for a launch that may hold strided merges (planes.hpp k_strided_segments): behind the clips, the STRIDED_PARAMS u64 of every segment.
 constexpr size_t strided_table_bytes(size_t nseg) { return range_table_bytes(nseg) + nseg * STRIDED_PARAMS * sizeof(u64); }
 
+// The same for a launch that may hold select merges (planes.hpp k_select_segments): behind the periods, the SELECT_PARAMS u64 of every segment.
+constexpr size_t select_table_bytes(size_t nseg) { return strided_table_bytes(nseg) + nseg * SELECT_PARAMS * sizeof(u64); }
+
 // Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
 // The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
 // clips (or nullptr): two u64 per segment, the [a, b) of the segments with PLANES_CLIP; d_tab then holds range_table_bytes(segs.size())
 // bytes, and a launch with such a segment goes to k_range_segments.
 // periods (or nullptr; only beside clips): STRIDED_PARAMS u64 per segment, read for the segments with PLANES_STRIDED; d_tab then holds
 // strided_table_bytes(segs.size()) bytes, and a launch with such a segment goes to k_strided_segments.
+// selects (or nullptr; only beside periods): SELECT_PARAMS u64 per segment, read for the segments with PLANES_SELECT; d_tab then holds
+// select_table_bytes(segs.size()) bytes, and a launch with such a segment goes to k_select_segments.
 void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr,
-                   const std::vector<u64> * periods = nullptr) {
+                   const std::vector<u64> * periods = nullptr, const std::vector<u64> * selects = nullptr) {
     const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
     if (clips && clips->size() != 2 * n) throw std::length_error("one clip per segment");
     if (periods && (!clips || periods->size() != STRIDED_PARAMS * n)) throw std::length_error("one period per segment");
-    staging.assign(periods ? strided_table_bytes(n) : clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
+    if (selects && (!periods || selects->size() != SELECT_PARAMS * n)) throw std::length_error("one piece list per segment");
+    staging.assign(selects ? select_table_bytes(n) : periods ? strided_table_bytes(n) : clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
     if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
     u32 * starts = (u32 *)(staging.data() + seg_bytes);
     u64 tiles = 0;
-    bool planes = false, delta = false, clip = false, strided = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
+    bool planes = false, delta = false, clip = false, strided = false, select = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
     for (size_t i = 0; i < n; i++) {
         starts[i] = (u32)tiles;
-        if (segs[i].mode & PLANES_STRIDED) {
+        if (segs[i].mode & PLANES_SELECT) {
+            if (!selects) throw std::length_error("a select segment without its piece list");
+            tiles += strided_tiles((*selects)[SELECT_PARAMS * i + 4], segs[i].mode & 0xff);
+            select = true;
+        } else if (segs[i].mode & PLANES_STRIDED) {
             if (!periods) throw std::length_error("a strided segment without its period");
             tiles += strided_tiles((*periods)[STRIDED_PARAMS * i + 4], segs[i].mode & 0xff);
             strided = true;
@@ -84,8 +94,13 @@ void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging,
     const size_t clip_off = range_table_bytes(n) - n * 2 * sizeof(u64);
     if (clip) memcpy(staging.data() + clip_off, clips->data(), n * 2 * sizeof(u64));
     if (strided) memcpy(staging.data() + range_table_bytes(n), periods->data(), n * STRIDED_PARAMS * sizeof(u64));
-    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), strided ? strided_table_bytes(n) : clip ? range_table_bytes(n) : copy_table_bytes(n), hipMemcpyHostToDevice, s));
-    if (strided)
+    if (select) memcpy(staging.data() + strided_table_bytes(n), selects->data(), n * SELECT_PARAMS * sizeof(u64));
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), select ? select_table_bytes(n) : strided ? strided_table_bytes(n) : clip ? range_table_bytes(n) : copy_table_bytes(n),
+                             hipMemcpyHostToDevice, s));
+    if (select)
+        launch(k_select_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off),
+               (const u64 *)(d_tab + range_table_bytes(n)), (const u64 *)(d_tab + strided_table_bytes(n)));
+    else if (strided)
         launch(k_strided_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off),
                (const u64 *)(d_tab + range_table_bytes(n)));
     else if (clip)
@@ -126,6 +141,67 @@ u64 strided_last_byte(u64 c0, u64 first, u64 run, u64 stride, u64 nbytes) {
     return c > UINT64_MAX ? UINT64_MAX : (u64)c;
 }
 
+// A request's piece list as its walk and its gather want it (frame.hpp, planes.hpp): the pieces that are not empty, neighbours joined, as
+// m + 1 pairs (s_j, P_j), the last one closing the table with P_m = L.
+struct PieceTable {
+    std::vector<u64> tab;
+    u64 m = 0, L = 0;
+    u64 given_end = 0;  // s + l of the last piece of the list as it was given (empty or not), 0 for no piece: what bz3_hip.h's checks speak of
+    u64 s(u64 j) const { return tab[2 * j]; }
+    u64 P(u64 j) const { return tab[2 * j + 1]; }
+    u64 l(u64 j) const { return P(j + 1) - P(j); }
+    u64 last_end() const { return m ? s(m - 1) + l(m - 1) : 0; }
+    // `pieces`: m_in pairs (s_j, l_j).  False for a list that bz3_hip.h calls invalid.
+    bool take(const u64 * pieces, u64 m_in) {
+        tab.clear();
+        m = L = given_end = 0;
+        if (m_in && !pieces) return false;
+        u64 end = 0, kept_end = 0;  // of the piece before, of the last piece kept
+        for (u64 j = 0; j < m_in; j++) {
+            const u64 sj = pieces[2 * j], lj = pieces[2 * j + 1];
+            if (sj + lj < sj || (j && sj < end)) return false;
+            if (lj && m && sj == kept_end) {
+                L += lj;  // joins the piece before it
+            } else if (lj) {
+                tab.push_back(sj);
+                tab.push_back(L);
+                L += lj;
+                m++;
+            }
+            if (L < lj) return false;  // (count * L would not fit either)
+            end = sj + lj;
+            if (lj) kept_end = end;
+        }
+        given_end = end;
+        tab.push_back(0);
+        tab.push_back(L);
+        return true;
+    }
+    // The wanted bytes of a period below its byte r.
+    u64 below(u64 r) const {
+        const u32 j = first_piece_behind(tab.data(), (u32)m, r);
+        return j == m ? L : P(j) + (r > s(j) ? r - s(j) : 0);
+    }
+};
+
+// The gather segment of a decoded chunk of s bytes in `slot` of which a select request wants the nbytes > 0 bytes c(u) (planes.hpp, "Select merge":
+// rel, stride, q0, r0 < L, the table t at device address d_tab): a share within one piece is the clipped or whole segment of a range call, anything
+// else a select merge.  `selects` holds SELECT_PARAMS u64 per segment, `periods` STRIDED_PARAMS.
+void push_select_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, std::vector<u64> & periods, std::vector<u64> & selects, u64 slot, u64 s, u64 k, u64 rel,
+                         u64 stride, const PieceTable & t, u64 d_tab, u64 q0, u64 r0, u64 nbytes, u64 dst, u64 base) {
+    const u64 j = piece_of(t.tab.data(), (u32)t.m, r0);
+    const bool select = nbytes > t.P(j + 1) - r0;
+    if (!select) {
+        const u64 c0 = rel + q0 * stride + t.s(j) + (r0 - t.P(j));
+        push_range_segment(segs, clips, slot, s, k, c0, c0 + nbytes, dst, base);
+    } else {
+        segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_SELECT, base});
+        clips.insert(clips.end(), {0, 0});
+    }
+    periods.insert(periods.end(), STRIDED_PARAMS, 0);
+    selects.insert(selects.end(), {select ? rel : 0, select ? stride : 0, select ? q0 : 0, select ? r0 : 0, select ? nbytes : 0, select ? d_tab : 0, select ? t.m : 0});
+}
+
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
 constexpr size_t WALK_RECORDS = 4096;     // chunk records of one walk (bz3_hip_frame_decoded_sizes_device; a window's walk takes at most FRAME_WINDOW_MAX)
 static_assert(WALK_RECORDS >= FRAME_WINDOW_MAX, "a window's walk must fit the records");
@@ -134,16 +210,19 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Layout of a call's small device buffer, sized for its n frames: staged headers (one 13-byte frame header per frame and one
 // 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
-// header; with room for their clips and periods), the walk's arguments, records and tails.
+// header; with room for their clips and periods), the walk's arguments, records and tails.  A call that walks with piece tables
+// (piece_bytes > 0 of them, uploaded once per call) has them behind the tails and room for the piece-list parameters in its copy tables;
+// every other call has the layout and the size it had.
 struct MetaLayout {
-    size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, bytes = 0;
+    size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, pieces = 0, bytes = 0;
     MetaLayout() = default;
-    explicit MetaLayout(size_t frames) : n(frames) {
+    explicit MetaLayout(size_t frames, size_t piece_bytes = 0) : n(frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
-        args = tab + align256(strided_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        args = tab + align256(piece_bytes ? select_table_bytes(2 * FRAME_WINDOW_MAX + n) : strided_table_bytes(2 * FRAME_WINDOW_MAX + n));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
-        bytes = tails + align256(n * sizeof(WalkTail));
+        pieces = tails + align256(n * sizeof(WalkTail));
+        bytes = pieces + align256(piece_bytes);
     }
 };
 
@@ -168,6 +247,7 @@ struct DeviceFrames {
     std::vector<CopySeg> segs;
     std::vector<u64> clips;  // empty, or the [a, b) of every segment of `segs` (a range call's gather)
     std::vector<u64> periods;  // empty, or the STRIDED_PARAMS of every segment of `segs` (a strided call's gather)
+    std::vector<u64> selects;  // empty, or the SELECT_PARAMS of every segment of `segs` (a select call's gather)
     std::vector<u8> staging;
     ~DeviceFrames() {
         if (device < 0) return;
@@ -178,10 +258,10 @@ struct DeviceFrames {
         if (meta) (void)hipFree(meta);
         if (own_stream && s) (void)hipStreamDestroy(s);
     }
-    bool open(int dev, size_t n) {  // the device, a stream and the small buffer
+    bool open(int dev, size_t n, size_t piece_bytes = 0) {  // the device, a stream and the small buffer
         if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
         device = dev;
-        lay = MetaLayout(n);
+        lay = MetaLayout(n, piece_bytes);
         HIP_CHECK(hipSetDevice(dev));
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         own_stream = true;
@@ -229,11 +309,12 @@ struct DeviceFrames {
     u8 * slot(size_t k) const { return slab + k * stride; }
     void copy() {  // the segments collected in `segs`, one launch, complete on return
         if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
-        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips, periods.empty() ? nullptr : &periods);
+        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips, periods.empty() ? nullptr : &periods, selects.empty() ? nullptr : &selects);
         HIP_CHECK(hipStreamSynchronize(s));
         segs.clear();
         clips.clear();
         periods.clear();
+        selects.clear();
     }
     void stage_headers(const std::vector<u8> & h) {
         if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
@@ -250,9 +331,9 @@ struct DeviceFrames {
         rec.resize(nrec);
         if (!n) return;
         HIP_CHECK(hipMemcpyAsync(meta + lay.args, args.data(), n * sizeof(WalkArg), hipMemcpyHostToDevice, s));
-        bool period = false;
-        for (const WalkArg & a : args) period |= a.count > 1;
-        launch(period ? k_frame_walk_strided : k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s,
+        bool period = false, select = false;
+        for (const WalkArg & a : args) period |= a.count > 1, select |= a.m > 0;
+        launch(select ? k_frame_walk_select : period ? k_frame_walk_strided : k_frame_walk_many, dim3((u32)((n + WALK_THREADS - 1) / WALK_THREADS)), dim3(WALK_THREADS), 0, s,
                (const WalkArg *)(meta + lay.args), (u32)n, (WalkChunk *)(meta + lay.rec), (WalkTail *)(meta + lay.tails));
         if (nrec) HIP_CHECK(hipMemcpyAsync(rec.data(), meta + lay.rec, nrec * sizeof(WalkChunk), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(tails.data(), meta + lay.tails, n * sizeof(WalkTail), hipMemcpyDeviceToHost, s));
@@ -265,11 +346,12 @@ struct WalkPos {
     u64 off = 0, planned = 0;
     u32 done = 0, block_size = 0, n_blocks = 0;
     WalkArg arg(const u8 * in, size_t in_size, size_t buf_max, u32 limit, u32 rec_base) const {
-        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0, 0, 0};
+        return WalkArg{(u64)in, (u64)in_size, (u64)buf_max, off, planned, done, limit, rec_base, block_size, n_blocks, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     }
     // the chunks that hold a byte of [lo, hi); with count > 1, of the `count` runs of `run` bytes that start `stride` apart from lo on
-    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base, u64 run = 0, u64 stride = 0, u64 count = 0) const {
-        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi, run, stride, count};
+    // with m > 0, of the `count` periods `stride` apart from lo on, the m pieces of the table at device address `pieces`
+    WalkArg range_arg(const u8 * in, size_t in_size, u64 lo, u64 hi, u32 limit, u32 rec_base, u64 run = 0, u64 stride = 0, u64 count = 0, u64 pieces = 0, u32 m = 0) const {
+        return WalkArg{(u64)in, (u64)in_size, (u64)SIZE_MAX, off, planned, done, limit, rec_base, block_size, n_blocks, 1, lo, hi, run, stride, count, pieces, m, 0};
     }
     void take(const WalkTail & t) {
         off = t.off;
@@ -468,8 +550,15 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
 // other one walks with its period (frame.hpp), so that its windows hold only the chunks that meet a run, up to end = phi(w - 1) + 1; in
 // the gather a chunk [p, p + o) holds the output bytes [t_a, t_b) = [below(p), below(p + o)), below(x) the number of t < w with phi(t) < x,
 // which are contiguous in `out` and one segment (push_strided_segment); `committed` is t_b.
+// selects (bz3_hip_decompress_device_select[_many]; only with periods; valid as bz3_hip.h demands): per frame nullptr, or a table of two or more
+// pieces, with periods[3 i + 1] and periods[3 i + 2] its stride and count (every other request of that call arrives normalised, as the strided
+// or empty request it is).  The frame wants the first w = min(out_sizes[i], base_sizes[i], count L) of the bytes phi(t) of bz3_hip.h.  w <= l_0
+// is the contiguous range (offset + s_0, w) and takes the range path untouched.  Every other one walks with its table (frame.hpp), which is
+// uploaded once, beside the walk's arguments; `count` is cut to the periods w reaches; the gather is the strided one with this phi
+// (push_select_segment).
 void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
-                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr, const u64 * periods = nullptr) {
+                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr, const u64 * periods = nullptr,
+                       const PieceTable * const * selects = nullptr) {
     struct Frame {
         size_t buf_max = 0, committed = 0;
         u32 decoded = 0;        // chunks decoded and committed
@@ -478,9 +567,12 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         bool failed = false;    // a chunk of the current window failed
         u64 lo = 0, hi = 0;     // range: the decoded bytes wanted
         u64 run = 0, stride = 0, count = 0;  // count > 1: of [lo, hi) only `count` runs of `run` bytes, `stride` apart; buf_max = w
+        const PieceTable * sel = nullptr;    // of every period only the pieces of this table, at device address d_tab
+        u64 d_tab = 0;
         u64 below(u64 x) const {             // the number of t < buf_max with phi(t) < x
             if (x <= lo) return 0;
             const u64 d = x - lo, i = d / stride, r = d % stride;
+            if (sel) return std::min<u64>(i >= count ? count * sel->L : i * sel->L + sel->below(r), buf_max);
             return std::min<u64>(i >= count ? count * run : i * run + std::min(r, run), buf_max);
         }
     };
@@ -491,7 +583,8 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     std::vector<Frame> fr((size_t)n);
     std::vector<WalkPos> pos((size_t)n);
     std::vector<char> live((size_t)n, 0);
-    bool any = false, any_period = false;
+    bool any = false, any_period = false, any_select = false;
+    std::vector<u64> tables;  // the piece tables of the frames that walk with one, as they are uploaded
     for (s32 i = 0; i < n; i++) {
         rcs[i] = BZ3_OK;
         if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
@@ -499,7 +592,20 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
         if (range) {
             fr[i].lo = offsets ? offsets[i] : 0;
-            if (periods) {
+            if (selects && selects[i]) {
+                const PieceTable & t = *selects[i];
+                const u64 stride = periods[3 * i + 1], w = fr[i].buf_max = (size_t)std::min<u64>(fr[i].buf_max, periods[3 * i + 2] * t.L);
+                if (w && w <= t.l(0)) {
+                    fr[i].lo += t.s(0);
+                } else if (w) {
+                    fr[i].sel = &t;
+                    fr[i].count = (w - 1) / t.L + 1;
+                    fr[i].stride = fr[i].count > 1 ? stride : std::max(stride, t.last_end());  // (one period: its stride is never used, and may be 0)
+                    fr[i].d_tab = tables.size() * sizeof(u64);
+                    tables.insert(tables.end(), t.tab.begin(), t.tab.end());
+                    any_select = true;
+                }
+            } else if (periods) {
                 const u64 run = periods[3 * i], stride = periods[3 * i + 1], W = periods[3 * i + 2] * run;
                 const u64 w = fr[i].buf_max = (size_t)std::min<u64>(fr[i].buf_max, W), runs = w ? (w - 1) / run + 1 : 0;
                 if (runs > 1 && stride != run) {
@@ -508,7 +614,13 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 }
             }
             fr[i].hi = fr[i].lo + (u64)fr[i].buf_max < fr[i].lo ? UINT64_MAX : fr[i].lo + (u64)fr[i].buf_max;
-            if (fr[i].count) fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + (fr[i].buf_max - (fr[i].count - 1) * fr[i].run);  // phi(w - 1) + 1
+            if (fr[i].sel) {
+                const PieceTable & t = *fr[i].sel;
+                const u64 r = (fr[i].buf_max - 1) % t.L, j = piece_of(t.tab.data(), (u32)t.m, r);
+                fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + t.s(j) + (r - t.P(j)) + 1;  // phi(w - 1) + 1
+            } else if (fr[i].count) {
+                fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + (fr[i].buf_max - (fr[i].count - 1) * fr[i].run);  // phi(w - 1) + 1
+            }
             out_sizes[i] = 0;
         }
     }
@@ -567,7 +679,8 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 if (!live[i] || fr[i].pending != BZ3_OK || range_walk_over(i)) continue;
                 const u64 from = std::max(fr[i].lo, pos[i].planned), est = (fr[i].hi - from) / pos[i].block_size + 2;
                 const u32 lim = (u32)std::min<u64>({est, (u64)(pos[i].n_blocks - pos[i].done), (u64)(W - win.size()), (u64)(WALK_RECORDS - base)});
-                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base, fr[i].run, fr[i].stride, fr[i].count));
+                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base, fr[i].run, fr[i].stride, fr[i].count, fr[i].d_tab,
+                                                fr[i].sel ? (u32)fr[i].sel->m : 0));
                 who.push_back(i);
                 base += lim;
             }
@@ -597,8 +710,14 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     };
     u32 bs_max = 0;
     try {
-        if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
+        if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64))) throw std::runtime_error("no device");
         DeviceGuard g(dev);
+        if (any_select) {  // the piece tables: one upload per call
+            HIP_CHECK(hipMemcpyAsync(f.meta + f.lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, f.s));
+            HIP_CHECK(hipStreamSynchronize(f.s));
+            for (s32 i = 0; i < n; i++)
+                if (fr[i].sel) fr[i].d_tab += (u64)(f.meta + f.lay.pieces);
+        }
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
         for (s32 i = 0; i < n; i++) {
             if (range && fr[i].buf_max == 0) live[i] = 0;  // nothing wanted: the frame header alone was checked
@@ -651,17 +770,24 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                         x.failed = true;
                         continue;
                     }
-                    if (range && x.count) {  // the chunk's bytes c(u) are the output bytes [ta, tb)
+                    if (range && x.sel) {  // the chunk's bytes c(u) of planes.hpp, "Select merge", are the output bytes [ta, tb)
+                        const u64 p = c.rec.out_off, ta = x.below(p), tb = x.below(p + (u64)c.rec.orig);
+                        push_select_segment(f.segs, f.clips, f.periods, f.selects, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, x.lo - p, x.stride, *x.sel,
+                                            x.d_tab, ta / x.sel->L, ta % x.sel->L, tb - ta, (u64)(outs[c.frame] + ta), bases && bases[c.frame] ? (u64)(bases[c.frame] + ta) : 0);
+                        x.committed = (size_t)tb;
+                    } else if (range && x.count) {  // the chunk's bytes c(u) are the output bytes [ta, tb)
                         const u64 p = c.rec.out_off, ta = x.below(p), tb = x.below(p + (u64)c.rec.orig);
                         const u64 c0 = x.lo + (ta / x.run) * x.stride + ta % x.run - p;
                         push_strided_segment(f.segs, f.clips, f.periods, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, c0, x.run - ta % x.run, x.run,
                                              x.stride, tb - ta, (u64)(outs[c.frame] + ta), bases && bases[c.frame] ? (u64)(bases[c.frame] + ta) : 0);
+                        if (any_select) f.selects.insert(f.selects.end(), SELECT_PARAMS, 0);
                         x.committed = (size_t)tb;
                     } else if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
                         const u64 p = c.rec.out_off, a = x.lo > p ? x.lo - p : 0, b = std::min<u64>(x.hi - p, (u64)c.rec.orig), at = p + a - x.lo;
                         push_range_segment(f.segs, f.clips, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, a, b, (u64)(outs[c.frame] + at),
                                            bases && bases[c.frame] ? (u64)(bases[c.frame] + at) : 0);
-                        if (any_period) f.periods.insert(f.periods.end(), STRIDED_PARAMS, 0);
+                        if (any_period || any_select) f.periods.insert(f.periods.end(), STRIDED_PARAMS, 0);
+                        if (any_select) f.selects.insert(f.selects.end(), SELECT_PARAMS, 0);
                         x.committed = (size_t)(p + b - x.lo);
                     } else {
                         f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
@@ -959,6 +1085,61 @@ BZIP3_API int bz3_hip_decompress_device_strided(uint32_t elem_size, const void *
     return bz3_hip_decompress_device_strided_many(1, &elem_size, ins, &in_size, params, bases, &base_size, outs, out_size, &rc);
 }
 
+// params: per frame (offset, stride, count, m); pieces[i]: m pairs (s_j, l_j) in host memory.  The whole-call checks of the range call, then the
+// validity of every request and its normal form: no piece left is the empty request, one piece the strided request (offset + s_0, l_0, stride,
+// count), and a call without a frame of two or more pieces is that strided call.
+BZIP3_API int bz3_hip_decompress_device_select_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                    const uint64_t params[], const uint64_t * const pieces[], const void * const bases[], const size_t base_sizes[],
+                                                    void * const outs[], size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    std::vector<u64> offsets((size_t)n), periods(3 * (size_t)n, 0), wanted((size_t)n, 0);
+    std::vector<PieceTable> tables((size_t)n);
+    std::vector<const PieceTable *> selects((size_t)n, nullptr);
+    for (s32 i = 0; i < n; i++) {
+        const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
+        PieceTable & t = tables[(size_t)i];
+        offsets[(size_t)i] = offset;
+        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+        if (t.L == 0 || count == 0) continue;  // W = 0: the period (0, 0, 0)
+        const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
+        if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+        wanted[(size_t)i] = (u64)W;
+        periods[3 * (size_t)i + 1] = stride, periods[3 * (size_t)i + 2] = count;
+        if (t.m == 1) {
+            offsets[(size_t)i] = offset + t.s(0);
+            periods[3 * (size_t)i] = t.L;
+        } else {
+            selects[(size_t)i] = &t;
+        }
+    }
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
+        if (!bases[i] || !base_sizes[i]) continue;
+        const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], wanted[(size_t)i]}), x = (u64)outs[i], y = (u64)bases[i];
+        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    bool any = false;
+    for (const PieceTable * t : selects) any |= t != nullptr;
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true, offsets.data(),
+                      periods.data(), any ? selects.data() : nullptr);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_decompress_device_select(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t stride, uint64_t count, uint64_t m,
+                                               const uint64_t * pieces, const void * base, size_t base_size, void * out, size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    const uint64_t params[4] = {offset, stride, count, m};
+    const uint64_t * lists[1] = {pieces};
+    int rc = BZ3_OK;
+    return bz3_hip_decompress_device_select_many(1, &elem_size, ins, &in_size, params, lists, bases, &base_size, outs, out_size, &rc);
+}
+
 BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * base, size_t base_size, void * out,
                                               size_t * out_size) {
     if (!out_size) return BZ3_ERR_INIT;
@@ -1107,6 +1288,75 @@ BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, voi
         std::vector<u8> staging;
         sc.open(strided_table_bytes((size_t)n));
         copy_segments(v, staging, sc.mem, sc.s, &clips, &periods);
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+    } catch (...) {
+        rc = BZ3_ERR_INIT;
+    }
+    return rc;
+}
+
+// n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, rel, stride, q0, r0, nbytes, first_piece, m): of the merge of the `len`
+// bytes at src_off the nbytes bytes c(u) (planes.hpp, "Select merge") of the m pieces (s_j, l_j) from pieces[2 first_piece] on, to dst_off (plus the
+// bytes at base_off unless it is UINT64_MAX), one launch through the segments a select call's gather makes of them.  The pieces are taken as they
+// are, empty ones and neighbours that touch included.
+BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces) {
+    if (n < 0 || (n > 0 && !segs) || (n_pieces && !pieces)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    std::vector<PieceTable> tabs((size_t)n);
+    size_t words = 0;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)12 * i;
+        const u64 len = q[3], rel = q[5], stride = q[6], q0 = q[7], r0 = q[8], nbytes = q[9], first = q[10], m = q[11];
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || len >= ((u64)1 << 31) || nbytes > len) return BZ3_ERR_INIT;
+        if (first > n_pieces || m > n_pieces - first || m >= ((u64)1 << 31)) return BZ3_ERR_INIT;
+        PieceTable & t = tabs[(size_t)i];  // the list as it is: (s_j, P_j) for every piece, then P_m
+        u64 end = 0;
+        for (u64 j = 0; j < m; j++) {
+            const u64 sj = pieces[2 * (first + j)], lj = pieces[2 * (first + j) + 1];
+            if (sj + lj < sj || (j && sj < end) || t.L + lj < lj) return BZ3_ERR_INIT;
+            t.tab.push_back(sj);
+            t.tab.push_back(t.L);
+            t.L += lj;
+            end = sj + lj;
+        }
+        t.tab.push_back(0);
+        t.tab.push_back(t.L);
+        t.m = m;
+        words += t.tab.size();
+        any_base |= q[1] != UINT64_MAX;
+        if (!nbytes) continue;
+        if (t.L == 0 || r0 >= t.L || (nbytes > t.L - r0 && stride < end)) return BZ3_ERR_INIT;
+        for (const u64 u : {(u64)0, nbytes - 1}) {  // c(0) and c(nbytes - 1) lie in the chunk (c increases)
+            const u64 x = r0 + u, r = x % t.L, j = piece_of(t.tab.data(), (u32)m, r);
+            const unsigned __int128 period = (unsigned __int128)q0 + x / t.L;
+            if (stride && period > UINT64_MAX / stride) return BZ3_ERR_INIT;
+            const __int128 c = (__int128)(s64)rel + (__int128)(period * stride) + t.s(j) + (r - t.P(j));
+            if (c < 0 || c >= (__int128)len) return BZ3_ERR_INIT;
+        }
+    }
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    int rc = BZ3_OK;
+    try {
+        DeviceGuard g(dev);
+        const size_t tab_bytes = align256(select_table_bytes((size_t)n));
+        sc.open(tab_bytes + words * sizeof(u64) + 16);
+        std::vector<u64> all;
+        std::vector<CopySeg> v;
+        std::vector<u64> clips, periods, selects;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)12 * i;
+            const PieceTable & t = tabs[(size_t)i];
+            const u64 d_tab = (u64)(sc.mem + tab_bytes) + all.size() * sizeof(u64);
+            all.insert(all.end(), t.tab.begin(), t.tab.end());
+            if (q[9])
+                push_select_segment(v, clips, periods, selects, (u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, d_tab, q[7], q[8], q[9], (u64)dst + q[2],
+                                    q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+        }
+        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(sc.mem + tab_bytes, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, sc.s));
+        std::vector<u8> staging;
+        copy_segments(v, staging, sc.mem, sc.s, &clips, &periods, &selects);
         HIP_CHECK(hipStreamSynchronize(sc.s));
     } catch (...) {
         rc = BZ3_ERR_INIT;

@@ -134,6 +134,15 @@ __global__ void __launch_bounds__(COPY_THREADS) k_copy_segments(const CopySeg * 
 // starts before the chunk's end.  A chunk that lies in a gap between two runs is header-checked and skipped like one before the range.
 // One 64-bit division per chunk, on the one lane that follows the chain.  A launch in which no frame has a period is
 // k_frame_walk_many as it was; one with such a frame is k_frame_walk_strided, where a lane with count <= 1 executes the walk above.
+//
+// A range walk with a piece table (WalkArg::m > 0; bz3_hip_decompress_device_select, api_frames.hip) wants of each of `count` periods, `stride`
+// bytes apart from lo on, the m pieces [s_j, s_j + l_j) of the period, ascending, disjoint and none empty, the last period cut at hi.  The
+// table lies in device memory, m + 1 entries of two u64: (s_j, P_j) with P_j = l_0 + ... + l_{j-1}, and the closing entry (unused, P_m), so
+// that l_j = P_{j+1} - P_j.  A chunk is recorded iff it meets a piece: q is the period that holds the chunk's first byte (0 before lo), j
+// the first piece of that period that ends behind it (binary search), piece 0 of period q + 1 where there is none; the chunk meets it iff
+// that period exists and the piece starts before the chunk's end and below hi.  A chunk in a gap between two pieces, or between the last piece
+// of a period and the first of the next, is header-checked and skipped.  One 64-bit division and one binary search per chunk, on the one lane
+// that follows the chain.  A launch with such a frame is k_frame_walk_select, where the other lanes execute the walks above.
 struct WalkChunk {
     u64 in_off;   // offset of the chunk header in the frame
     u64 out_off;  // output bytes of the chunks before it (planned)
@@ -150,6 +159,8 @@ struct WalkArg {
     u32 range;                 // != 0: a range walk over the output bytes [lo, hi)
     u64 lo, hi;
     u64 run, stride, count;    // count > 1: only the chunks that meet one of `count` runs of `run` bytes, `stride` apart from lo on
+    u64 pieces;                // m > 0: the device address of the piece table; only the chunks that meet a piece of one of `count` periods
+    u32 m, pad;
 };
 struct WalkTail {
     u64 off, planned;  // resume state after the last well-formed chunk read
@@ -162,8 +173,20 @@ struct WalkTail {
 static_assert(sizeof(WalkChunk) % 16 == 0 && sizeof(WalkArg) % 8 == 0 && sizeof(WalkTail) % 8 == 0, "walk records are packed arrays");
 constexpr u32 WALK_THREADS = 64;
 
+// The first piece of a table of m that ends behind byte r of its period, or m.
+__host__ __device__ inline u32 first_piece_behind(const u64 * tab, u32 m, u64 r) {
+    u32 lo = 0, hi = m;  // invariant: the pieces before lo end at or before r, those from hi on behind it
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tab[2 * mid] + (tab[2 * mid + 3] - tab[2 * mid + 1]) > r) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 // PERIOD: some frame of the launch walks with a period (k_frame_walk_strided); without it the fields of the period are never looked at.
-template <bool PERIOD>
+// SELECT: some frame of the launch walks with a piece table (k_frame_walk_select); likewise.
+template <bool PERIOD, bool SELECT = false>
 __device__ __forceinline__ void frame_walk(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec, WalkTail * __restrict__ tails) {
     const u32 i = blockIdx.x * WALK_THREADS + threadIdx.x;
     if (i >= n) return;
@@ -189,7 +212,17 @@ __device__ __forceinline__ void frame_walk(const WalkArg * __restrict__ args, u3
         if (err != BZ3_OK) break;
         const u64 data = off + 8;
         bool wanted = !a.range || (orig > 0 && planned + (u64)orig > a.lo);
-        if (PERIOD && wanted && a.count > 1) {
+        if (SELECT && wanted && a.m > 0) {
+            const u64 * tab = (const u64 *)a.pieces;
+            u64 q = planned < a.lo ? 0 : (planned - a.lo) / a.stride;
+            u32 j = first_piece_behind(tab, a.m, planned < a.lo ? 0 : planned - a.lo - q * a.stride);
+            if (j == a.m) {
+                q++;
+                j = 0;
+            }
+            const u64 start = a.lo + q * a.stride + tab[2 * j];  // (q < count: it fits, bz3_hip.h)
+            wanted = q < a.count && start < planned + (u64)orig && start < a.hi;
+        } else if (PERIOD && wanted && a.count > 1) {
             const u64 i0 = planned < a.lo + a.run ? 0 : (planned - a.lo - a.run) / a.stride + 1;
             wanted = i0 < a.count && a.lo + i0 * a.stride < planned + (u64)orig;
         }
@@ -227,6 +260,12 @@ __global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_many(const WalkArg 
 __global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_strided(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
                                                                      WalkTail * __restrict__ tails) {
     frame_walk<true>(args, n, rec, tails);
+}
+
+// The same for a launch in which some frame walks with a piece table.
+__global__ void __launch_bounds__(WALK_THREADS) k_frame_walk_select(const WalkArg * __restrict__ args, u32 n, WalkChunk * __restrict__ rec,
+                                                                    WalkTail * __restrict__ tails) {
+    frame_walk<true, true>(args, n, rec, tails);
 }
 
 }  // namespace bz3

@@ -80,6 +80,25 @@
 // only the lane's own 16 k bytes, so what else phase 1 takes from the base are the 256th lane's bytes and the bytes below s0, which
 // belong to other tiles, may have been overwritten already and land in LDS outside [s0 - origin, s1 - origin), where phase 2 never
 // reads.
+//
+// Select merge (CopySeg::mode & PLANES_SELECT; bz3_hip_decompress_device_select, api_frames.hip).  An index request wants of a chunk the bytes
+// of a LIST of pieces per period: the periods start `stride` bytes apart, piece j of a period is its bytes [s_j, s_j + l_j), the pieces
+// ascend and are disjoint, P_j = l_0 + ... + l_{j-1}, L = P_m.  The table of the m + 1 pairs (s_j, P_j) -- the last one closes it with
+// P_m -- lies in device memory and is only ever read.  In the output the chunk's share is CONTIGUOUS, dst[0, nbytes): one segment.  With
+// x = r0 + u, destination byte u comes from chunk byte
+//     c(u) = rel + (q0 + x / L) stride + s_j + (x % L - P_j),     j the piece with P_j <= x % L < P_{j+1}
+// (rel = the request's offset less the chunk's, mod 2^64; q0, r0: the period and the place in it of destination byte 0) and chunk byte c
+// lives where merge_k puts it, as above.  The host has checked that c(0) and c(nbytes - 1) lie in [0, len); c increases, so every c(u) does.
+// select_tile tiles the DESTINATION exactly as strided_tile does and differs in phase 1 alone: a lane locates its first byte with one
+// division (32 bits where L < 2^31, else a comparison: x < L + 2^31 then) and one binary search over P, and from there steps through the
+// pieces linearly, skipping empty ones, with the chunk byte of the period's start in hand.  The 16-byte path is strided_tile's under
+// strided_tile's conditions with "piece" for "run"; every other lane moves its bytes one by one.  So, as there: every granule loaded from the
+// slot holds a byte of the chunk (16-byte path: c + 16 k <= m k, and plane granule q covers slot[q m + c / k, + 16)); every granule loaded
+// from the base holds a byte of base[0, nbytes) (16-byte path: u0 + 16 k <= nbytes, and load_elems16 takes the aligned granules around
+// exactly those bytes; byte path: bytes u < nbytes); nothing outside dst[0, nbytes) is written (phase 2 is store_from_lds over the tile's
+// share of [dst, dst + nbytes)).  In place (dst == base): the tile argument of the strided merge holds word for word, because the tiling, the
+// lanes' destination bytes and phase 2 are the same and only the SOURCE byte of a destination byte differs.  No scratch, and the LDS of
+// k_strided_segments.
 #pragma once
 #include "frame.hpp"
 
@@ -93,6 +112,8 @@ constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = e
 constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments alone)
 constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments alone)
 constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
+constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone)
+constexpr u32 SELECT_PARAMS = 7;                            // u64 per segment in its side table: rel, stride, q0, r0, nbytes, the piece table's address, m
 
 __host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // Workgroups of a split / merge segment: one per PLANES_TILE_ELEMS elements; a block shorter than an element still has its tail.
@@ -617,6 +638,171 @@ __global__ void __launch_bounds__(COPY_THREADS) k_strided_segments(const CopySeg
     const u8 * base = (const u8 *)sg.base;
     u8 * dst = (u8 *)sg.dst;
     if (sg.mode & PLANES_STRIDED) {
+        const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
+        const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
+        const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)
+        const u32 gap = nbytes > first ? (u32)(pp[3] - pp[2]) : 0;
+        const u32 len = (u32)sg.len;
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (sg.mode & PLANES_CLIP) {
+        const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (!sg.base) {
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
+        else copy_segment_tile(sg, tile);
+    } else if ((sg.mode & 0xff) > 1) {
+        planes_tile<true>(sg, tile, (u8 *)lds);
+    } else {
+        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
+        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+        if (sg.mode & PLANES_INVERSE) delta1_tile<true>(src, base, dst, sg.len, g_first, g_last);
+        else delta1_tile<false>(src, base, dst, sg.len, g_first, g_last);
+    }
+}
+
+// ---- select merge --------------------------------------------------------------------------------------------------------------------
+// The piece of a table of m (pairs (s_j, P_j), closed by P_m) that holds byte r < P_m of the period's wanted bytes: P_j <= r < P_{j+1}.
+__host__ __device__ inline u32 piece_of(const u64 * tab, u32 m, u64 r) {
+    u32 lo = 0, hi = m;  // invariant: P_lo <= r < P_hi
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tab[2 * mid + 1] <= r) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Tile `tile` of a select merge of the `len` < 2^31 bytes at `src`: destination bytes [0, nbytes) from the chunk bytes c(u) (the head of this
+// file; sp: the segment's SELECT_PARAMS), to dst; with D, plus base[0, nbytes) (which may be `dst`).  Workgroups: strided_tiles(nbytes, k).
+template <int K, bool D>
+__device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, const u64 * __restrict__ sp, u32 tile, u8 * lds) {
+    const u32 m = len / K, ua = tile * (PLANES_TILE_ELEMS * K), nbytes = (u32)sp[4];
+    const u32 u0 = ua + 16 * K * threadIdx.x;
+    if (u0 < nbytes) {
+        const u64 * __restrict__ tab = (const u64 *)sp[5];
+        const u32 np = (u32)sp[6], stride = (u32)sp[1];  // (chunk bytes are taken mod 2^32: every c(u) that is read lies below 2^31)
+        const u64 L = tab[2 * np + 1], x = sp[3] + u0;
+        u64 q, r;  // x = q L + r
+        if (L >> 31) {
+            q = x >= L ? 1 : 0;
+            r = x - (q ? L : 0);
+        } else {
+            q = (u32)x / (u32)L;
+            r = (u32)x - (u32)q * (u32)L;
+        }
+        u32 j = piece_of(tab, np, r);
+        u32 cb = (u32)(sp[0] + (sp[2] + q) * sp[1]);  // the chunk byte of the period's first byte
+        const u64 in = r - tab[2 * j + 1], rest = tab[2 * j + 3] - r;  // bytes of piece j before and from the lane's first byte
+        u32 c = cb + (u32)(tab[2 * j] + in);
+        u32 left = rest < 0x7fffffffu ? (u32)rest : 0x7fffffffu;  // (beyond the chunk's 2^31 bytes: no destination byte lies behind it)
+        if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
+            u32 w[4 * K];
+            if constexpr (K == 1) {
+                const uint4 v = load16_any((u64)src + c);
+                w[0] = v.x;
+                w[1] = v.y;
+                w[2] = v.z;
+                w[3] = v.w;
+            } else {
+                u32 p[K][4];
+#pragma unroll
+                for (int i = 0; i < K; i++) {
+                    const uint4 v = load16_any((u64)src + (u64)i * m + c / K);
+                    p[i][0] = v.x;
+                    p[i][1] = v.y;
+                    p[i][2] = v.z;
+                    p[i][3] = v.w;
+                }
+                interleave<K>(p, w);
+            }
+            if (D) {
+                u32 b[4 * K];
+                load_elems16<K>((u64)base + u0, b);
+#pragma unroll
+                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+        } else {
+            const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
+            for (u32 u = u0; u < u1; u++) {
+                const u8 v = src[c < m * K ? (c % K) * m + c / K : c];
+                lds[u - ua] = D ? (u8)(v + base[u]) : v;
+                c++;
+                if (--left == 0 && u + 1 < u1) {  // the next piece that is not empty (there is one: L > 0), in the next period behind the last
+                    u64 l;
+                    do {
+                        if (++j == np) {
+                            j = 0;
+                            cb += stride;
+                        }
+                        l = tab[2 * j + 3] - tab[2 * j + 1];
+                    } while (l == 0);
+                    c = cb + (u32)tab[2 * j];
+                    left = l < 0x7fffffffu ? (u32)l : 0x7fffffffu;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const u64 d0 = (u64)dst, dend = d0 + nbytes;
+    const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ua, dend);
+    const u64 s1 = ua + PLANES_TILE_ELEMS * K >= nbytes ? dend : align16_up_to(d0 + ua + PLANES_TILE_ELEMS * K, dend);
+    store_from_lds<K>(lds, d0 + ua, s0, s1);  // at most 255 K + 1 granules
+}
+
+// k_strided_segments for a launch in which some segment is a select merge: selects[7 i .. 7 i + 6] are segment i's SELECT_PARAMS (read for
+// segments with PLANES_SELECT alone); tile_start counts such a segment's workgroups with strided_tiles.  The other segments take what they
+// take in k_strided_segments.  (A kernel of its own, as the four before it: launches without a select segment keep the five kernels above
+// as they are.)
+__global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                  const u64 * __restrict__ clips, const u64 * __restrict__ periods, const u64 * __restrict__ selects) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 b = blockIdx.x;
+    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (tile_start[mid] <= b) lo = mid;
+        else hi = mid;
+    }
+    const CopySeg sg = segs[lo];
+    const u32 tile = b - tile_start[lo];
+    const u8 * src = (const u8 *)sg.src;
+    const u8 * base = (const u8 *)sg.base;
+    u8 * dst = (u8 *)sg.dst;
+    if (sg.mode & PLANES_SELECT) {
+        const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
+        const u32 len = (u32)sg.len;
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 1: select_tile<1, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 2: select_tile<2, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 4: select_tile<4, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 8: select_tile<8, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 1 | 16: select_tile<1, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 2 | 16: select_tile<2, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 4 | 16: select_tile<4, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 8 | 16: select_tile<8, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            default: break;
+        }
+    } else if (sg.mode & PLANES_STRIDED) {
         const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
         const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
         const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)

@@ -300,6 +300,62 @@ BZIP3_API int bz3_hip_decompress_device_strided_many(int32_t n, const uint32_t e
  * chunk byte c(nbytes - 1) is not below len, for len >= 2^31 and for what bz3_hip_debug_range refuses.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
 
+/* Index decode: an arbitrary ascending set of rows, experts or columns of what a frame decodes to -- `count` periods whose starts lie
+ * `stride` bytes apart from `offset` on, and of every period the same m pieces (s_j, l_j): piece j is the bytes [s_j, s_j + l_j) of its
+ * period -- at the cost of the chunks that hold a byte of a piece.  `pieces` is a HOST array of 2 m u64: s_0, l_0, s_1, l_1, ...  X, p_j,
+ * o_j and T are as in the range contract above (the j of p_j and o_j numbers chunks, the j of s_j, l_j and P_j pieces).
+ * P_j = l_0 + ... + l_{j-1}, L = P_m; W = count * L; w = min(*out_size, W), with a base min(*out_size, base_size, W); for t < w
+ *     phi(t) = offset + (t / L) * stride + s_j + (t % L - P_j),     j the piece with P_j <= t % L < P_{j+1},
+ * which is strictly increasing (see Validity); end = phi(w - 1) + 1.  The call is pread(2) of the bytes phi(0), phi(1), ... of X:
+ *   it writes out[t] = X[phi(t)] for t < r -- with a base (X[phi(t)] + base[t]) mod 256 --, r the number of t < w with phi(t) < T (a
+ *   prefix, because phi increases), and returns BZ3_OK with *out_size = r.  BZ3_ERR_DATA_TOO_BIG is never returned.
+ *   `base` holds the base's bytes OF THE INDEX SET, in output order: base[t] pairs with out[t].  `out` may be exactly `base`; any other
+ *   overlap of out[0, w) and base[0, w) is BZ3_ERR_INIT before any write.
+ *   Validity (a violation is BZ3_ERR_INIT for the whole call before any write, exactly as a bad elem_size is): s_j + l_j must not
+ *   overflow 64 bits; s_j + l_j <= s_{j+1}: the pieces ascend and are disjoint (l_j = 0 is allowed); s_{m-1} + l_{m-1} <= stride
+ *   wherever count > 1 and L > 0; count * L and offset + (count - 1) * stride + s_{m-1} + l_{m-1} must not overflow 64 bits; pieces == NULL
+ *   with m > 0.  m == 0, L == 0 or count == 0 is allowed and means W = 0 (nothing else of such a request is looked at): the frame header
+ *   alone is checked, as for w = 0 in the range call.
+ *   The frame header is always checked.  The header of chunk j is read and checked iff w > 0 and p_j < end, with the three checks of
+ *   the range call.  Chunk j is DECODED iff o_j > 0 and [p_j, p_j + o_j) holds phi(t) for some t < w; it is then decoded whole and ONCE,
+ *   however many pieces and periods it holds, with its CRC and every per-block check.  A chunk that lies before the first piece, or IN
+ *   ANY GAP -- between two pieces of a period, or between the last piece of one period and the first of the next -- is header-checked
+ *   and skipped: a corrupt payload there is not noticed.
+ *   The result is the first event in chunk order, a header error or a failed chunk: its code is returned, the output bytes t with
+ *   phi(t) below that chunk's p_j are committed (a prefix), *out_size is their count, nothing else of `out` is written.
+ *   Nothing outside out[0, r) is ever written; `in`, `pieces` and a base that is not `out` are never written.
+ *   Normal form and equivalence: empty pieces are dropped; pieces with s_j + l_j == s_{j+1} are joined; w cuts count and the last
+ *   period's pieces.  A request left with one piece is the strided request (offset + s_0, l_0, stride, count): it returns byte for byte
+ *   what bz3_hip_decompress_device_strided returns for *out_size = min(*out_size, W), with the same return code and *out_size, through
+ *   the same launches (and that call in turn takes the range call's for one run or stride == run).
+ * A frame with two or more pieces walks with its piece table in device memory (16 bytes per piece, uploaded once per call beside the
+ * walk's arguments; frame.hpp k_frame_walk_select: one division and one binary search per chunk header).  Within a decoded chunk the
+ * wanted bytes are gathered by one launch per window (planes.hpp k_select_segments), a chunk being one segment however many pieces and
+ * periods it holds.  Lanes whose 16 elements lie inside one piece move 16 elements at once; the others byte by byte.
+ * _many follows bz3_hip_decompress_device_range_many word for word: n independent frames on ONE GPU (the same frame may appear more than
+ * once), NULL elem_sizes, bases and bases[i] as there, the same whole-call checks, rcs[], independence of frames, windows across frames
+ * and headroom rule.  params holds four u64 per frame: offset, stride, count, m; pieces[i] is frame i's host array of 2 m_i u64.  NULL
+ * params, or NULL pieces or pieces[i] where m_i > 0, is BZ3_ERR_INIT.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_decompress_device_select(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t stride,
+                                               uint64_t count, uint64_t m, const uint64_t * pieces, const void * base, size_t base_size,
+                                               void * out, size_t * out_size);
+BZIP3_API int bz3_hip_decompress_device_select_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                    const uint64_t params[], const uint64_t * const pieces[], const void * const bases[],
+                                                    const size_t base_sizes[], void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: one launch of the gather of a select call: n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, rel,
+ * stride, q0, r0, nbytes, first_piece, m) relative to `src` / `base` / `dst`, and one host array `pieces` of 2 n_pieces u64 (s, l) of
+ * which a tuple takes the m pieces from first_piece on.  Of merge_k(the len bytes at src_off) the nbytes bytes c(0), c(1), ... are
+ * stored at dst_off, plus the nbytes bytes at base_off unless base_off is UINT64_MAX: with x = r0 + u,
+ *     c(u) = rel + (q0 + x / L) * stride + s_j + (x % L - P_j),     j the piece with P_j <= x % L < P_{j+1},
+ * rel a two's-complement u64 (the request's offset less the chunk's).  The pieces are NOT normalised: empty ones and neighbours that
+ * touch stay in the table, so a uniform list reaches the select kernel.  A tuple whose nbytes lie within one piece is one contiguous
+ * piece and becomes the clipped or whole segment of bz3_hip_debug_range.  `dst` may be `base` with dst_off == base_off.  BZ3_ERR_INIT for
+ * what bz3_hip_debug_strided refuses of the first five fields, for a piece list that is invalid (above; and where the tuple's bytes
+ * span two periods, s_{m-1} + l_{m-1} > stride), for r0 >= L, and for a tuple whose c(0) or c(nbytes - 1) lies outside [0, len).
+ * Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n,
+                                       const uint64_t * pieces, uint64_t n_pieces);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
