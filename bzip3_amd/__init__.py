@@ -536,6 +536,43 @@ def decompress_tensors(frames, outs=None, lib=None, planes=1, bases=None):
     return res
 
 
+def _decompress_partial(name, frames, request, outs, planes, bases, lib):
+    """The body of decompress_tensors_range, _strided and _select.  request(n) validates the caller's request for the n frames and returns
+    (the bytes asked of every frame, the C entry point's name, its parameter arrays between in_sizes and bases)."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    nbytes, entry, params = request(n)
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
+    dev = _same_device(frames, name)
+    L = lib or load()
+    if outs is None:
+        outs = _carve(sum(nbytes), nbytes, dev)
+    else:
+        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
+        if len(outs) != n:
+            raise ValueError(f"{name}: {n} frames and {len(outs)} outputs")
+        _same_device(frames + outs, name)
+    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
+        if o.numel() < w or (b is not None and b.numel() < w):
+            raise ValueError(f"{name}: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
+    torch.cuda.synchronize(dev)
+    out_sizes = (C.c_size_t * n)(*nbytes)
+    rcs = (C.c_int * n)()
+    rc = getattr(L, entry)(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), *params, _ptrs_or_null(bases),
+                           (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, nbytes)]), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(rc, entry, index=idx, codes=codes, outs=res)
+    return res
+
+
 def decompress_tensors_range(frames, offsets, nbytes, outs=None, planes=1, bases=None, lib=None):
     """Bytes [offsets[i], offsets[i] + nbytes[i]) of what frames[i] decodes to, for many frames in ONE call
     (bz3_hip_decompress_device_range_many): only the chunks that hold bytes of a range are decoded (plus a walk over the chunk headers
@@ -545,42 +582,15 @@ def decompress_tensors_range(frames, offsets, nbytes, outs=None, planes=1, bases
     base's bytes OF THE RANGE (at least nbytes[i] of them: bases[i][j] pairs with byte offsets[i] + j); outs[i] may be bases[i].  The
     same frame may appear more than once.  Raises Bz3Error with .index / .codes / .outs (per frame the range bytes committed before its
     error) as decompress_tensors does.  [] returns []."""
-    import torch
+    def request(n):
+        offs, sizes = [int(o) for o in offsets], [int(w) for w in nbytes]
+        if len(offs) != n or len(sizes) != n:
+            raise ValueError(f"decompress_tensors_range: {n} frames, {len(offs)} offsets and {len(sizes)} sizes")
+        if any(o < 0 for o in offs) or any(w < 0 for w in sizes):
+            raise ValueError("decompress_tensors_range: offsets and sizes must not be negative")
+        return sizes, "bz3_hip_decompress_device_range_many", [(C.c_uint64 * n)(*offs)]
 
-    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
-    n = len(frames)
-    offsets, nbytes = [int(o) for o in offsets], [int(w) for w in nbytes]
-    if len(offsets) != n or len(nbytes) != n:
-        raise ValueError(f"decompress_tensors_range: {n} frames, {len(offsets)} offsets and {len(nbytes)} sizes")
-    if any(o < 0 for o in offsets) or any(w < 0 for w in nbytes):
-        raise ValueError("decompress_tensors_range: offsets and sizes must not be negative")
-    if not frames:
-        return []
-    ks = _planes_arg(planes, n)
-    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
-    dev = _same_device(frames, "decompress_tensors_range")
-    L = lib or load()
-    if outs is None:
-        outs = _carve(sum(nbytes), nbytes, dev)
-    else:
-        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
-        if len(outs) != n:
-            raise ValueError(f"decompress_tensors_range: {n} frames and {len(outs)} outputs")
-        _same_device(frames + outs, "decompress_tensors_range")
-    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
-        if o.numel() < w or (b is not None and b.numel() < w):
-            raise ValueError(f"decompress_tensors_range: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
-    torch.cuda.synchronize(dev)
-    out_sizes = (C.c_size_t * n)(*nbytes)
-    rcs = (C.c_int * n)()
-    rc = L.bz3_hip_decompress_device_range_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), (C.c_uint64 * n)(*offsets),
-                                                _ptrs_or_null(bases), (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, nbytes)]), _ptrs(outs), out_sizes, rcs)
-    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
-        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(rc, "bz3_hip_decompress_device_range_many", index=idx, codes=codes, outs=res)
-    return res
+    return _decompress_partial("decompress_tensors_range", frames, request, outs, planes, bases, lib)
 
 
 def decompress_tensor_range(frame, offset, nbytes, out=None, planes=1, base=None, lib=None):
@@ -604,49 +614,19 @@ def decompress_tensors_strided(frames, offsets, runs, strides, counts, outs=None
     least as many as are asked for); outs[i] may be bases[i].  ValueError for a negative number, for strides[i] < runs[i] where
     counts[i] > 1 and runs[i] > 0, and for a set that does not fit 64 bits.  The same frame may appear more than once.  Raises Bz3Error
     with .index / .codes / .outs (per frame the bytes committed before its error) as decompress_tensors does.  [] returns []."""
-    import torch
+    def request(n):
+        cols = [[int(v) for v in col] for col in (offsets, runs, strides, counts)]
+        if any(len(col) != n for col in cols):
+            raise ValueError(f"decompress_tensors_strided: {n} frames and {[len(col) for col in cols]} offsets, runs, strides and counts")
+        params = list(zip(*cols))
+        for i, (o, r, s, c) in enumerate(params):
+            if min(o, r, s, c) < 0:
+                raise ValueError("decompress_tensors_strided: offsets, runs, strides and counts must not be negative")
+            if r and c and ((c > 1 and s < r) or c * r >= 1 << 64 or o + (c - 1) * s + r >= 1 << 64):
+                raise ValueError(f"decompress_tensors_strided: ({o}, {r}, {s}, {c}) of frame {i} is no strided range")
+        return [r * c for _, r, _, c in params], "bz3_hip_decompress_device_strided_many", [(C.c_uint64 * (4 * n))(*[v for p in params for v in p])]
 
-    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
-    n = len(frames)
-    cols = [[int(v) for v in col] for col in (offsets, runs, strides, counts)]
-    if any(len(col) != n for col in cols):
-        raise ValueError(f"decompress_tensors_strided: {n} frames and {[len(col) for col in cols]} offsets, runs, strides and counts")
-    params = list(zip(*cols))
-    for i, (o, r, s, c) in enumerate(params):
-        if min(o, r, s, c) < 0:
-            raise ValueError("decompress_tensors_strided: offsets, runs, strides and counts must not be negative")
-        if r and c and ((c > 1 and s < r) or c * r >= 1 << 64 or o + (c - 1) * s + r >= 1 << 64):
-            raise ValueError(f"decompress_tensors_strided: ({o}, {r}, {s}, {c}) of frame {i} is no strided range")
-    if not frames:
-        return []
-    ks = _planes_arg(planes, n)
-    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
-    dev = _same_device(frames, "decompress_tensors_strided")
-    L = lib or load()
-    nbytes = [r * c for _, r, _, c in params]
-    if outs is None:
-        outs = _carve(sum(nbytes), nbytes, dev)
-    else:
-        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
-        if len(outs) != n:
-            raise ValueError(f"decompress_tensors_strided: {n} frames and {len(outs)} outputs")
-        _same_device(frames + outs, "decompress_tensors_strided")
-    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
-        if o.numel() < w or (b is not None and b.numel() < w):
-            raise ValueError(f"decompress_tensors_strided: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
-    caps = nbytes
-    torch.cuda.synchronize(dev)
-    out_sizes = (C.c_size_t * n)(*caps)
-    rcs = (C.c_int * n)()
-    rc = L.bz3_hip_decompress_device_strided_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
-                                                  (C.c_uint64 * (4 * n))(*[v for p in params for v in p]), _ptrs_or_null(bases),
-                                                  (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, caps)]), _ptrs(outs), out_sizes, rcs)
-    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
-        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(rc, "bz3_hip_decompress_device_strided_many", index=idx, codes=codes, outs=res)
-    return res
+    return _decompress_partial("decompress_tensors_strided", frames, request, outs, planes, bases, lib)
 
 
 def decompress_tensor_strided(frame, offset, run, stride, count, out=None, planes=1, base=None, lib=None):
@@ -671,55 +651,28 @@ def decompress_tensors_select(frames, offsets, strides, counts, pieces, outs=Non
     ValueError for a negative number, for pieces that overlap or descend, for a last piece that ends behind strides[i] where
     counts[i] > 1, and for a set that does not fit 64 bits.  The same frame may appear more than once.  Raises Bz3Error with .index /
     .codes / .outs (per frame the bytes committed before its error) as decompress_tensors does.  [] returns []."""
-    import torch
+    def request(n):
+        cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
+        lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
+        if any(len(col) != n for col in cols) or len(lists) != n:
+            raise ValueError(f"decompress_tensors_select: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists")
+        params = list(zip(*cols))
+        nbytes = []
+        for i, ((o, s, c), pl) in enumerate(zip(params, lists)):
+            if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
+                raise ValueError("decompress_tensors_select: offsets, strides, counts and pieces must not be negative")
+            if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
+                raise ValueError(f"decompress_tensors_select: the pieces of frame {i} do not ascend")
+            L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
+            if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
+                raise ValueError(f"decompress_tensors_select: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
+            nbytes.append(c * L)
+        arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
+        ptrs = (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs])
+        ptrs.arrays = arrs  # alive as long as their pointers
+        return nbytes, "bz3_hip_decompress_device_select_many", [(C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]), ptrs]
 
-    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
-    n = len(frames)
-    cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
-    lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
-    if any(len(col) != n for col in cols) or len(lists) != n:
-        raise ValueError(f"decompress_tensors_select: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists")
-    params = list(zip(*cols))
-    nbytes = []
-    for i, ((o, s, c), pl) in enumerate(zip(params, lists)):
-        if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
-            raise ValueError("decompress_tensors_select: offsets, strides, counts and pieces must not be negative")
-        if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
-            raise ValueError(f"decompress_tensors_select: the pieces of frame {i} do not ascend")
-        L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
-        if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
-            raise ValueError(f"decompress_tensors_select: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
-        nbytes.append(c * L)
-    if not frames:
-        return []
-    ks = _planes_arg(planes, n)
-    bases = [_base_u8(b, f, f"bases[{i}]", same_size=False) for i, (b, f) in enumerate(zip(_bases_arg(bases, n), frames))]
-    dev = _same_device(frames, "decompress_tensors_select")
-    L = lib or load()
-    if outs is None:
-        outs = _carve(sum(nbytes), nbytes, dev)
-    else:
-        outs = [_device_u8(o, f"outs[{i}]") for i, o in enumerate(outs)]
-        if len(outs) != n:
-            raise ValueError(f"decompress_tensors_select: {n} frames and {len(outs)} outputs")
-        _same_device(frames + outs, "decompress_tensors_select")
-    for i, (o, b, w) in enumerate(zip(outs, bases, nbytes)):
-        if o.numel() < w or (b is not None and b.numel() < w):
-            raise ValueError(f"decompress_tensors_select: outs[{i}] / bases[{i}] hold fewer than the {w} bytes asked for")
-    torch.cuda.synchronize(dev)
-    out_sizes = (C.c_size_t * n)(*nbytes)
-    rcs = (C.c_int * n)()
-    arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
-    rc = L.bz3_hip_decompress_device_select_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
-                                                 (C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]),
-                                                 (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs]), _ptrs_or_null(bases),
-                                                 (C.c_size_t * n)(*[0 if b is None else w for b, w in zip(bases, nbytes)]), _ptrs(outs), out_sizes, rcs)
-    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
-        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(rc, "bz3_hip_decompress_device_select_many", index=idx, codes=codes, outs=res)
-    return res
+    return _decompress_partial("decompress_tensors_select", frames, request, outs, planes, bases, lib)
 
 
 def decompress_tensor_select(frame, offset, stride, count, pieces, out=None, planes=1, base=None, lib=None):
@@ -1003,9 +956,8 @@ def _row_bytes(p, what):
 
 def _unpack_rows_many(ps, rows, outs, lib, bases):
     """Rows rows[i] = (start, stop) of dimension 0 of every PackedTensor (None: the whole tensor), in ONE
-    bz3_hip_decompress_device_range_many call."""
-    import torch
-
+    bz3_hip_decompress_device_range_many call.  bases[i]: the same rows of the base.  (A tensor that comes back whole is read as the range
+    of its bytes: a frame that decodes to more is not noticed here.)"""
     shapes, spans = [], []
     for i, (p, r) in enumerate(zip(ps, rows)):
         if not isinstance(p, PackedTensor):
@@ -1020,30 +972,10 @@ def _unpack_rows_many(ps, rows, outs, lib, bases):
             raise ValueError(f"rows ({start}, {stop}) of a tensor of {p.shape[0]} rows")
         shapes.append((stop - start, *p.shape[1:]))
         spans.append((start * rb, (stop - start) * rb))
-    bases = _bases_arg(bases, len(ps))
-    braws = []
-    for i, (p, b, (_, w), shape) in enumerate(zip(ps, bases, spans, shapes)):
-        if p.delta and b is None:
-            raise ValueError(f"unpack: tensor {i} was packed against a base, which is needed to restore it")
-        if not p.delta:
-            b = None
-        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != shape:
-            raise ValueError(f"unpack: base {i} must hold the same rows of the base: {p.dtype} {shape}")
-        braws.append(_base_bytes(b, w, p.frame.device, f"base {i}"))
-    dev = _same_device([p.frame for p in ps], "unpack")
-    if outs is None:
-        raws = _carve(0, [w for _, w in spans], dev)  # every output at a multiple of 16 bytes, so that any dtype can view it
-    else:
-        raws = []
-        for p, o, shape in zip(ps, outs, shapes):
-            if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or tuple(o.shape) != shape or not o.is_contiguous():
-                raise TypeError("unpack: `out` must be a contiguous tensor of the packed dtype and of the rows' shape")
-            raws.append(_as_bytes(o, "out"))
-    got = decompress_tensors_range([p.frame for p in ps], [o for o, _ in spans], [w for _, w in spans], raws, planes=[p.planes for p in ps], bases=braws, lib=lib)
-    for i, (g, (_, w)) in enumerate(zip(got, spans)):
-        if g.numel() != w:
-            raise Bz3Error(BZ3_ERR_TRUNCATED_DATA, f"unpack: the frame of tensor {i} holds {g.numel()} of the {w} bytes of its rows;", g)
-    return list(outs) if outs is not None else [_from_bytes(r, p.dtype, shape) for r, p, shape in zip(raws, ps, shapes)]
+    frames, planes, sizes = [p.frame for p in ps], [p.planes for p in ps], [w for _, w in spans]
+    return _unpack_parts_many(ps, shapes, sizes, [], outs, lib, bases, "rows",
+                              lambda raws, braws: decompress_tensors_range(frames, [o for o, _ in spans], sizes, raws, planes=planes, bases=braws, lib=lib))
+
 
 
 def unpack_tensor_rows(p, start, stop, out=None, base=None, lib=None):
@@ -1106,7 +1038,7 @@ def _unpack_parts_many(ps, shapes, sizes, whole, outs, lib, bases, what, decode)
         raws = []
         for p, o, shape in zip(ps, outs, shapes):
             if not isinstance(o, torch.Tensor) or o.dtype != p.dtype or tuple(o.shape) != shape or not o.is_contiguous():
-                raise TypeError(f"unpack: `out` must be a contiguous tensor of the packed dtype and of the {what}'s shape")
+                raise TypeError(f"unpack: `out` must be a contiguous tensor of the packed dtype and of the {what}'{'' if what.endswith('s') else 's'} shape")
             raws.append(_as_bytes(o, "out"))
     got = decode(raws, braws)
     for i, (g, w) in enumerate(zip(got, sizes)):
@@ -1294,18 +1226,20 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
     inplace are as with `slices`.  A name in more than one of `rows`, `slices` and `index`: ValueError.  index=None runs what the function
     ran before it had the argument."""
     names = list(packed)
-    if index is not None:
+    if index is not None or slices is not None or rows is not None:
+        # one partial path: the narrowest call that the arguments given call for reads every tensor, whole ones included
+        arg, part = ("index", "a part of") if index is not None else ("slices", "a slice of") if slices is not None else ("rows", "rows for")
         if verify:
-            raise ValueError("unpack_state_dict: verify=True and index do not go together (the checksum covers the whole tensor)")
+            raise ValueError(f"unpack_state_dict: verify=True and {arg} do not go together (the checksum covers the whole tensor)")
         if inplace:
-            raise ValueError("unpack_state_dict: index and inplace=True do not go together")
-        want = {k: (0, int(r[0]), int(r[1])) for k, r in (rows or {}).items()}
+            raise ValueError(f"unpack_state_dict: {arg} and inplace=True do not go together")
+        want = {k: (0, int(r[0]), int(r[1])) for k, r in (rows or {}).items()}  # rows are slices of dimension 0
         for k, sl in (slices or {}).items():
             if k in want:
                 raise ValueError(f"unpack_state_dict: {k!r} is in both rows and slices")
             want[k] = tuple(sl)
         order = {}
-        for k, (dim, idx) in index.items():
+        for k, (dim, idx) in (index or {}).items():
             if k in want:
                 raise ValueError(f"unpack_state_dict: {k!r} is in index and in rows or slices")
             if k in packed:
@@ -1315,15 +1249,16 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
                 want[k] = (dim, idx)
         unknown = [k for k in want if k not in packed]
         if unknown:
-            raise ValueError(f"unpack_state_dict: a part of {unknown[0]!r}, which is not in the dict")
+            raise ValueError(f"unpack_state_dict: {part} {unknown[0]!r}, which is not in the dict")
         if not names:
             return {}
         import torch
 
         ps = [packed[k] for k in names]
         sels = [want.get(k) for k in names]
-        for k, p, sel in zip(names, ps, sels):  # (every request is validated before anything is read)
-            _index_of(p, sel, repr(k))
+        for k, p, sel in zip(names, ps, sels):  # every request is validated before anything is read (rows alone: by _unpack_rows_many, in its own words)
+            if arg != "rows":
+                _index_of(p, sel, repr(k))
             if order.get(k) is not None and p.delta:
                 raise ValueError(f"unpack_state_dict: {k!r} was packed against a base and takes a strictly increasing index")
         bases, whole = [], []
@@ -1334,75 +1269,23 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
             # the whole base is at hand here, for the tensors read in part too: check it as unpack_tensor does, before anything is decoded
             whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}") if check_base and fits and p.base_crc is not None else None)
             if fits and sel is not None and len(sel) == 3:
-                b = b.narrow(int(sel[0]) % len(p.shape), int(sel[1]), int(sel[2]) - int(sel[1]))
+                if arg != "rows" or (len(p.shape) and 0 <= sel[1] <= sel[2] <= p.shape[0]):
+                    b = b.narrow(int(sel[0]) % len(p.shape), int(sel[1]), int(sel[2]) - int(sel[1]))
             elif fits and sel is not None:
                 b = b.index_select(int(sel[0]) % len(p.shape), torch.tensor(sel[1], dtype=torch.int64, device=b.device))
             bases.append(b)
         _check_bases(ps, whole, [repr(k) for k in names], L)
-        got = dict(zip(names, _unpack_index_many(ps, sels, None, lib, bases)))
+        if arg == "index":
+            parts = _unpack_index_many(ps, sels, None, lib, bases)
+        elif arg == "slices":
+            parts = _unpack_slices_many(ps, sels, None, lib, bases)
+        else:
+            parts = _unpack_rows_many(ps, [None if sel is None else sel[1:] for sel in sels], None, lib, bases)
+        got = dict(zip(names, parts))
         for k, where in order.items():
             if where is not None:
                 got[k] = torch.index_select(got[k], int(index[k][0]) % len(packed[k].shape), torch.tensor(where, dtype=torch.int64, device=got[k].device))
         return got
-    if slices is not None:
-        if verify:
-            raise ValueError("unpack_state_dict: verify=True and slices do not go together (the checksum covers the whole tensor)")
-        if inplace:
-            raise ValueError("unpack_state_dict: slices and inplace=True do not go together")
-        want = {k: (0, int(r[0]), int(r[1])) for k, r in (rows or {}).items()}
-        for k, sl in slices.items():
-            if k in want:
-                raise ValueError(f"unpack_state_dict: {k!r} is in both rows and slices")
-            want[k] = sl
-        unknown = [k for k in want if k not in packed]
-        if unknown:
-            raise ValueError(f"unpack_state_dict: a slice of {unknown[0]!r}, which is not in the dict")
-        if not names:
-            return {}
-        import torch
-
-        ps = [packed[k] for k in names]
-        sls = [want.get(k) for k in names]
-        shapes = [_slice_of(p, sl, repr(k))[0] for k, p, sl in zip(names, ps, sls)]  # (every slice is validated before anything is read)
-        bases, whole = [], []
-        L = lib or load()
-        for k, p, sl in zip(names, ps, sls):
-            b = base.get(k) if base is not None and p.delta else None
-            fits = isinstance(b, torch.Tensor) and b.dtype == p.dtype and tuple(b.shape) == tuple(p.shape)
-            # the whole base is at hand here, for the sliced tensors too: check it as unpack_tensor does, before anything is decoded
-            whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}") if check_base and fits and p.base_crc is not None else None)
-            if fits and sl is not None:
-                dim = int(sl[0]) % len(p.shape)
-                b = b.narrow(dim, int(sl[1]), int(sl[2]) - int(sl[1]))
-            bases.append(b)
-        _check_bases(ps, whole, [repr(k) for k in names], L)
-        return dict(zip(names, _unpack_slices_many(ps, sls, None, lib, bases)))
-    if rows is not None:
-        if verify:
-            raise ValueError("unpack_state_dict: verify=True and rows do not go together (the checksum covers the whole tensor)")
-        if inplace:
-            raise ValueError("unpack_state_dict: rows and inplace=True do not go together")
-        unknown = [k for k in rows if k not in packed]
-        if unknown:
-            raise ValueError(f"unpack_state_dict: rows for {unknown[0]!r}, which is not in the dict")
-        if not names:
-            return {}
-        ps = [packed[k] for k in names]
-        rws = [rows.get(k) for k in names]
-        bases, whole = [], []
-        L = lib or load()
-        for k, p, r in zip(names, ps, rws):
-            b = base.get(k) if base is not None and p.delta else None
-            # the whole base is at hand here, for the tensors read by rows too: check it as unpack_tensor does, before anything is decoded
-            if check_base and b is not None and p.base_crc is not None and getattr(b, "dtype", None) == p.dtype and tuple(b.shape) == tuple(p.shape):
-                whole.append(_base_bytes(b, p.nbytes, p.frame.device, f"base {k!r}"))
-            else:
-                whole.append(None)
-            if b is not None and r is not None and len(p.shape) and tuple(b.shape) == tuple(p.shape) and 0 <= int(r[0]) <= int(r[1]) <= p.shape[0]:
-                b = b[int(r[0]) : int(r[1])]
-            bases.append(b)
-        _check_bases(ps, whole, [repr(k) for k in names], L)
-        return dict(zip(names, _unpack_rows_many(ps, rws, None, lib, bases)))
     if not names:
         return {}
     ps = [packed[k] for k in names]

@@ -1,5 +1,9 @@
-// api_frames.hip -- the device-resident frame API of include/bz3_hip.h (plain, byte planes, delta, range, decoded sizes), its debug entry
-// points and the batched CRC.  The only unit that includes frame.hpp and planes.hpp: their kernels are ordinary definitions.
+// api_frames.hip -- the device-resident frame API of include/bz3_hip.h (plain, byte planes, delta, decoded sizes, and the partial decode calls:
+// range, strided, select), its debug entry points and the batched CRC.  The only unit that includes frame.hpp and planes.hpp: their kernels are
+// ordinary definitions.  The partial decode calls share one request form (Request), one list of gather segments with their side tables
+// (GatherList) and one body (decompress_frames); what differs between them is how an entry point reads its parameters.
+#include <functional>
+
 #include "api_internal.hpp"
 #include "frame.hpp"
 #include "planes.hpp"
@@ -36,101 +40,17 @@ int device_of(const void * p) {
 #endif
 }
 
-// Device tables of one k_copy_segments launch: the segments, then the nseg + 1 tile starts.
-constexpr size_t copy_table_bytes(size_t nseg) { return ((nseg * sizeof(CopySeg) + 15) & ~(size_t)15) + (nseg + 1) * sizeof(u32); }
+constexpr size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-// The same for a launch that may hold clipped merges (planes.hpp k_range_segments): behind the tables above, 16-byte aligned, the
-// [a, b) of every segment (two u64 each).
-constexpr size_t range_table_bytes(size_t nseg) { return ((copy_table_bytes(nseg) + 15) & ~(size_t)15) + nseg * 2 * sizeof(u64); }
-
-// The same for a launch that may hold strided merges (planes.hpp k_strided_segments): behind the clips, the STRIDED_PARAMS u64 of every segment.
-constexpr size_t strided_table_bytes(size_t nseg) { return range_table_bytes(nseg) + nseg * STRIDED_PARAMS * sizeof(u64); }
-
-// The same for a launch that may hold select merges (planes.hpp k_select_segments): behind the periods, the SELECT_PARAMS u64 of every segment.
-constexpr size_t select_table_bytes(size_t nseg) { return strided_table_bytes(nseg) + nseg * SELECT_PARAMS * sizeof(u64); }
-
-// Copies `segs` (absolute device addresses) in one launch on stream s; d_tab holds copy_table_bytes(segs.size()) bytes.
-// The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
-// clips (or nullptr): two u64 per segment, the [a, b) of the segments with PLANES_CLIP; d_tab then holds range_table_bytes(segs.size())
-// bytes, and a launch with such a segment goes to k_range_segments.
-// periods (or nullptr; only beside clips): STRIDED_PARAMS u64 per segment, read for the segments with PLANES_STRIDED; d_tab then holds
-// strided_table_bytes(segs.size()) bytes, and a launch with such a segment goes to k_strided_segments.
-// selects (or nullptr; only beside periods): SELECT_PARAMS u64 per segment, read for the segments with PLANES_SELECT; d_tab then holds
-// select_table_bytes(segs.size()) bytes, and a launch with such a segment goes to k_select_segments.
-void copy_segments(const std::vector<CopySeg> & segs, std::vector<u8> & staging, u8 * d_tab, hipStream_t s, const std::vector<u64> * clips = nullptr,
-                   const std::vector<u64> * periods = nullptr, const std::vector<u64> * selects = nullptr) {
-    const size_t n = segs.size(), seg_bytes = (n * sizeof(CopySeg) + 15) & ~(size_t)15;
-    if (clips && clips->size() != 2 * n) throw std::length_error("one clip per segment");
-    if (periods && (!clips || periods->size() != STRIDED_PARAMS * n)) throw std::length_error("one period per segment");
-    if (selects && (!periods || selects->size() != SELECT_PARAMS * n)) throw std::length_error("one piece list per segment");
-    staging.assign(selects ? select_table_bytes(n) : periods ? strided_table_bytes(n) : clips ? range_table_bytes(n) : copy_table_bytes(n), 0);
-    if (n) memcpy(staging.data(), segs.data(), n * sizeof(CopySeg));
-    u32 * starts = (u32 *)(staging.data() + seg_bytes);
-    u64 tiles = 0;
-    bool planes = false, delta = false, clip = false, strided = false, select = false;  // a segment with an element size: k_move_segments; one with a base: k_delta_segments (planes.hpp)
-    for (size_t i = 0; i < n; i++) {
-        starts[i] = (u32)tiles;
-        if (segs[i].mode & PLANES_SELECT) {
-            if (!selects) throw std::length_error("a select segment without its piece list");
-            tiles += strided_tiles((*selects)[SELECT_PARAMS * i + 4], segs[i].mode & 0xff);
-            select = true;
-        } else if (segs[i].mode & PLANES_STRIDED) {
-            if (!periods) throw std::length_error("a strided segment without its period");
-            tiles += strided_tiles((*periods)[STRIDED_PARAMS * i + 4], segs[i].mode & 0xff);
-            strided = true;
-        } else if (segs[i].mode & PLANES_CLIP) {
-            if (!clips) throw std::length_error("a clipped segment without its clip");
-            tiles += clip_tiles(segs[i].len, segs[i].mode & 0xff, (*clips)[2 * i], (*clips)[2 * i + 1]);
-            clip = true;
-        } else {
-            tiles += segment_tiles(segs[i]);
-        }
-        planes |= (segs[i].mode & 0xff) > 1;
-        delta |= segs[i].base != 0;
-    }
-    if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
-    starts[n] = (u32)tiles;
-    if (!tiles) return;
-    const size_t clip_off = range_table_bytes(n) - n * 2 * sizeof(u64);
-    if (clip) memcpy(staging.data() + clip_off, clips->data(), n * 2 * sizeof(u64));
-    if (strided) memcpy(staging.data() + range_table_bytes(n), periods->data(), n * STRIDED_PARAMS * sizeof(u64));
-    if (select) memcpy(staging.data() + strided_table_bytes(n), selects->data(), n * SELECT_PARAMS * sizeof(u64));
-    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), select ? select_table_bytes(n) : strided ? strided_table_bytes(n) : clip ? range_table_bytes(n) : copy_table_bytes(n),
-                             hipMemcpyHostToDevice, s));
-    if (select)
-        launch(k_select_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off),
-               (const u64 *)(d_tab + range_table_bytes(n)), (const u64 *)(d_tab + strided_table_bytes(n)));
-    else if (strided)
-        launch(k_strided_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off),
-               (const u64 *)(d_tab + range_table_bytes(n)));
-    else if (clip)
-        launch(k_range_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, (const u64 *)(d_tab + clip_off));
-    else
-        launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n);
-}
-
-// The gather segment of chunk bytes [a, b) of a decoded chunk of s bytes in `slot`, element size k, to dst (and base, or 0), which
-// address the clip's first byte: a whole chunk and every k = 1 clip are ordinary segments, the rest clipped merges (planes.hpp).
-void push_range_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, u64 slot, u64 s, u64 k, u64 a, u64 b, u64 dst, u64 base) {
-    const bool plain = k <= 1 || a == b || (a == 0 && b == s);
-    if (plain) segs.push_back({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
-    else segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base});
-    clips.push_back(plain ? 0 : a);
-    clips.push_back(plain ? 0 : b);
-}
-
-// The same for a chunk of which a strided range wants the nbytes bytes c(u) (planes.hpp, "Strided merge"; first in [1, run], stride >= run):
-// one contiguous piece (nbytes <= first) is the clipped or whole segment above, anything else a strided merge.  `periods` holds STRIDED_PARAMS u64 per segment.
-void push_strided_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, std::vector<u64> & periods, u64 slot, u64 s, u64 k, u64 c0, u64 first, u64 run, u64 stride,
-                          u64 nbytes, u64 dst, u64 base) {
-    const bool strided = nbytes > first;
-    if (!strided) {
-        push_range_segment(segs, clips, slot, s, k, c0, c0 + nbytes, dst, base);
-    } else {
-        segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_STRIDED, base});
-        clips.insert(clips.end(), {0, 0});
-    }
-    periods.insert(periods.end(), {strided ? c0 : 0, strided ? first : 0, strided ? run : 0, strided ? stride : 0, strided ? nbytes : 0});
+// Device tables of one segment launch whose highest segment kind is `level` (planes.hpp SegLevel): the segments, then the nseg + 1 tile starts;
+// from SEG_CLIP on, 16-byte aligned behind them, the [a, b) of every segment (two u64 each); from SEG_STRIDED on the STRIDED_PARAMS u64 of
+// every segment behind the clips; with SEG_SELECT the SELECT_PARAMS u64 of every segment behind the periods.
+constexpr size_t table_bytes(size_t nseg, int level) {
+    size_t b = align16(nseg * sizeof(CopySeg)) + (nseg + 1) * sizeof(u32);
+    if (level >= SEG_CLIP) b = align16(b) + nseg * 2 * sizeof(u64);
+    if (level >= SEG_STRIDED) b += nseg * STRIDED_PARAMS * sizeof(u64);
+    if (level >= SEG_SELECT) b += nseg * SELECT_PARAMS * sizeof(u64);
+    return b;
 }
 
 // The last chunk byte a strided merge reads, c(nbytes - 1) for nbytes > 0, or UINT64_MAX where it does not fit 64 bits.
@@ -141,8 +61,8 @@ u64 strided_last_byte(u64 c0, u64 first, u64 run, u64 stride, u64 nbytes) {
     return c > UINT64_MAX ? UINT64_MAX : (u64)c;
 }
 
-// A request's piece list as its walk and its gather want it (frame.hpp, planes.hpp): the pieces that are not empty, neighbours joined, as
-// m + 1 pairs (s_j, P_j), the last one closing the table with P_m = L.
+// A request's piece list as its walk and its gather want it (frame.hpp, planes.hpp): m + 1 pairs (s_j, P_j), the last one closing the table
+// with P_m = L.  A request's table holds the pieces that are not empty, neighbours joined; a debug call's the list as it was given.
 struct PieceTable {
     std::vector<u64> tab;
     u64 m = 0, L = 0;
@@ -151,8 +71,8 @@ struct PieceTable {
     u64 P(u64 j) const { return tab[2 * j + 1]; }
     u64 l(u64 j) const { return P(j + 1) - P(j); }
     u64 last_end() const { return m ? s(m - 1) + l(m - 1) : 0; }
-    // `pieces`: m_in pairs (s_j, l_j).  False for a list that bz3_hip.h calls invalid.
-    bool take(const u64 * pieces, u64 m_in) {
+    // `pieces`: m_in pairs (s_j, l_j).  False for a list that bz3_hip.h calls invalid.  join == false: every piece is kept as it is.
+    bool take(const u64 * pieces, u64 m_in, bool join = true) {
         tab.clear();
         m = L = given_end = 0;
         if (m_in && !pieces) return false;
@@ -160,9 +80,9 @@ struct PieceTable {
         for (u64 j = 0; j < m_in; j++) {
             const u64 sj = pieces[2 * j], lj = pieces[2 * j + 1];
             if (sj + lj < sj || (j && sj < end)) return false;
-            if (lj && m && sj == kept_end) {
+            if (join && lj && m && sj == kept_end) {
                 L += lj;  // joins the piece before it
-            } else if (lj) {
+            } else if (lj || !join) {
                 tab.push_back(sj);
                 tab.push_back(L);
                 L += lj;
@@ -182,24 +102,102 @@ struct PieceTable {
         const u32 j = first_piece_behind(tab.data(), (u32)m, r);
         return j == m ? L : P(j) + (r > s(j) ? r - s(j) : 0);
     }
+    // The byte of a period that is its wanted byte r < L.
+    u64 byte(u64 r) const {
+        const u64 j = piece_of(tab.data(), (u32)m, r);
+        return s(j) + (r - P(j));
+    }
 };
 
-// The gather segment of a decoded chunk of s bytes in `slot` of which a select request wants the nbytes > 0 bytes c(u) (planes.hpp, "Select merge":
-// rel, stride, q0, r0 < L, the table t at device address d_tab): a share within one piece is the clipped or whole segment of a range call, anything
-// else a select merge.  `selects` holds SELECT_PARAMS u64 per segment, `periods` STRIDED_PARAMS.
-void push_select_segment(std::vector<CopySeg> & segs, std::vector<u64> & clips, std::vector<u64> & periods, std::vector<u64> & selects, u64 slot, u64 s, u64 k, u64 rel,
-                         u64 stride, const PieceTable & t, u64 d_tab, u64 q0, u64 r0, u64 nbytes, u64 dst, u64 base) {
-    const u64 j = piece_of(t.tab.data(), (u32)t.m, r0);
-    const bool select = nbytes > t.P(j + 1) - r0;
-    if (!select) {
-        const u64 c0 = rel + q0 * stride + t.s(j) + (r0 - t.P(j));
-        push_range_segment(segs, clips, slot, s, k, c0, c0 + nbytes, dst, base);
-    } else {
-        segs.push_back({slot, dst, s, k | PLANES_INVERSE | PLANES_SELECT, base});
-        clips.insert(clips.end(), {0, 0});
+// The segments of one launch.  A segment of a partial merge (planes.hpp: clipped, strided, select) carries the row of its kind's side table with
+// it, so a segment and its parameters cannot fall out of step; copy_segments lays the tables out.  `level` is the highest kind among the
+// segments: it alone decides which tables are uploaded and which kernel runs.
+struct GatherList {
+    struct Entry {
+        CopySeg seg;
+        u64 row[SELECT_PARAMS];  // of the side table that seg.mode names: [a, b), STRIDED_PARAMS or SELECT_PARAMS
+    };
+    std::vector<Entry> v;
+    int level = SEG_DELTA;
+    size_t size() const { return v.size(); }
+    void clear() {
+        v.clear();
+        level = SEG_DELTA;
     }
-    periods.insert(periods.end(), STRIDED_PARAMS, 0);
-    selects.insert(selects.end(), {select ? rel : 0, select ? stride : 0, select ? q0 : 0, select ? r0 : 0, select ? nbytes : 0, select ? d_tab : 0, select ? t.m : 0});
+    // A segment as it is: a copy, a split, a merge, with or without a base.
+    void plain(const CopySeg & sg) { v.push_back({sg, {}}); }
+    // The chunk bytes [a, b) of a decoded chunk of s bytes in `slot`, element size k, to dst (and base, or 0), which address the clip's first
+    // byte: a whole chunk and every k = 1 clip are ordinary segments, the rest clipped merges.
+    void range(u64 slot, u64 s, u64 k, u64 a, u64 b, u64 dst, u64 base) {
+        if (k <= 1 || a == b || (a == 0 && b == s)) return plain({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
+        v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base}, {a, b}});
+        level = std::max<int>(level, SEG_CLIP);
+    }
+    // The same for a chunk of which a strided range wants the nbytes bytes c(u) (planes.hpp, "Strided merge"; first in [1, run], stride >= run):
+    // a share within one run (nbytes <= first) is the clipped or whole segment above, anything else a strided merge.
+    void strided(u64 slot, u64 s, u64 k, u64 c0, u64 first, u64 run, u64 stride, u64 nbytes, u64 dst, u64 base) {
+        if (nbytes <= first) return range(slot, s, k, c0, c0 + nbytes, dst, base);
+        v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_STRIDED, base}, {c0, first, run, stride, nbytes}});
+        level = std::max<int>(level, SEG_STRIDED);
+    }
+    // The same for a chunk of which a select request wants the nbytes > 0 bytes c(u) (planes.hpp, "Select merge": rel, stride, q0, r0 < L, the
+    // table t at device address d_tab): a share within one piece is the clipped or whole segment above, anything else a select merge.
+    void select(u64 slot, u64 s, u64 k, u64 rel, u64 stride, const PieceTable & t, u64 d_tab, u64 q0, u64 r0, u64 nbytes, u64 dst, u64 base) {
+        const u64 j = piece_of(t.tab.data(), (u32)t.m, r0);
+        if (nbytes <= t.P(j + 1) - r0) {
+            const u64 c0 = rel + q0 * stride + t.s(j) + (r0 - t.P(j));
+            return range(slot, s, k, c0, c0 + nbytes, dst, base);
+        }
+        v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_SELECT, base}, {rel, stride, q0, r0, nbytes, d_tab, t.m}});
+        level = SEG_SELECT;
+    }
+};
+
+// Copies the segments of g (absolute device addresses) in one launch on stream s; d_tab holds table_bytes(g.size(), g.level) bytes.  The kernel
+// is the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
+// k_copy_segments (planes.hpp).  The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
+void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
+    const size_t n = g.size(), bytes = table_bytes(n, g.level), seg_bytes = align16(n * sizeof(CopySeg));
+    const size_t clip_off = table_bytes(n, SEG_CLIP) - n * 2 * sizeof(u64), period_off = table_bytes(n, SEG_CLIP), select_off = table_bytes(n, SEG_STRIDED);
+    staging.assign(bytes, 0);
+    u32 * starts = (u32 *)(staging.data() + seg_bytes);
+    u64 tiles = 0;
+    bool planes = false, delta = false;
+    for (size_t i = 0; i < n; i++) {
+        const CopySeg & sg = g.v[i].seg;
+        const u64 * row = g.v[i].row;
+        const u64 k = sg.mode & 0xff;
+        memcpy(staging.data() + i * sizeof(CopySeg), &sg, sizeof(CopySeg));
+        starts[i] = (u32)tiles;
+        if (sg.mode & PLANES_SELECT) {  // (a segment of a kind raised g.level to it: its table lies inside `bytes`)
+            memcpy(staging.data() + select_off + i * SELECT_PARAMS * sizeof(u64), row, SELECT_PARAMS * sizeof(u64));
+            tiles += strided_tiles(row[4], k);
+        } else if (sg.mode & PLANES_STRIDED) {
+            memcpy(staging.data() + period_off + i * STRIDED_PARAMS * sizeof(u64), row, STRIDED_PARAMS * sizeof(u64));
+            tiles += strided_tiles(row[4], k);
+        } else if (sg.mode & PLANES_CLIP) {
+            memcpy(staging.data() + clip_off + i * 2 * sizeof(u64), row, 2 * sizeof(u64));
+            tiles += clip_tiles(sg.len, k, row[0], row[1]);
+        } else {
+            tiles += segment_tiles(sg);
+        }
+        planes |= k > 1;
+        delta |= sg.base != 0;
+    }
+    if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
+    starts[n] = (u32)tiles;
+    if (!tiles) return;
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), bytes, hipMemcpyHostToDevice, s));
+    const dim3 grid((u32)tiles), block(COPY_THREADS);
+    const CopySeg * d_segs = (const CopySeg *)d_tab;
+    const u32 * d_starts = (const u32 *)(d_tab + seg_bytes);
+    const u64 * d_clips = (const u64 *)(d_tab + clip_off);
+    const u64 * d_periods = (const u64 *)(d_tab + period_off);
+    const u64 * d_selects = (const u64 *)(d_tab + select_off);
+    if (g.level == SEG_SELECT) launch(k_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods, d_selects);
+    else if (g.level == SEG_STRIDED) launch(k_strided_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods);
+    else if (g.level == SEG_CLIP) launch(k_range_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
+    else launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, grid, block, 0, s, d_segs, d_starts, (u32)n);
 }
 
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
@@ -218,7 +216,7 @@ struct MetaLayout {
     MetaLayout() = default;
     explicit MetaLayout(size_t frames, size_t piece_bytes = 0) : n(frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
-        args = tab + align256(piece_bytes ? select_table_bytes(2 * FRAME_WINDOW_MAX + n) : strided_table_bytes(2 * FRAME_WINDOW_MAX + n));
+        args = tab + align256(table_bytes(2 * FRAME_WINDOW_MAX + n, piece_bytes ? SEG_SELECT : SEG_STRIDED));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
         pieces = tails + align256(n * sizeof(WalkTail));
@@ -244,10 +242,7 @@ struct DeviceFrames {
     u8 * slab = nullptr;
     size_t stride = 0;
     std::vector<bz3_state *> states;
-    std::vector<CopySeg> segs;
-    std::vector<u64> clips;  // empty, or the [a, b) of every segment of `segs` (a range call's gather)
-    std::vector<u64> periods;  // empty, or the STRIDED_PARAMS of every segment of `segs` (a strided call's gather)
-    std::vector<u64> selects;  // empty, or the SELECT_PARAMS of every segment of `segs` (a select call's gather)
+    GatherList gather;  // the segments of the next launch
     std::vector<u8> staging;
     ~DeviceFrames() {
         if (device < 0) return;
@@ -307,14 +302,11 @@ struct DeviceFrames {
         return true;
     }
     u8 * slot(size_t k) const { return slab + k * stride; }
-    void copy() {  // the segments collected in `segs`, one launch, complete on return
-        if (segs.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
-        copy_segments(segs, staging, meta + lay.tab, s, clips.empty() ? nullptr : &clips, periods.empty() ? nullptr : &periods, selects.empty() ? nullptr : &selects);
+    void copy() {  // the segments collected in `gather`, one launch, complete on return
+        if (gather.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
+        copy_segments(gather, staging, meta + lay.tab, s);
         HIP_CHECK(hipStreamSynchronize(s));
-        segs.clear();
-        clips.clear();
-        periods.clear();
-        selects.clear();
+        gather.clear();
     }
     void stage_headers(const std::vector<u8> & h) {
         if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
@@ -470,7 +462,7 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
                     slots[cnt] = f.slot(cnt);
                     f.states[cnt]->block_size = (s32)x.bs;  // every check of the block is made against its own frame's block size
                     f.states[cnt]->last_error = BZ3_OK;
-                    f.segs.push_back({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0,
+                    f.gather.plain({(u64)(ins[i] + (size_t)x.next * x.bs), (u64)f.slot(cnt), (u64)size, elem_sizes ? (u64)elem_sizes[i] : 0,
                                       bases && bases[i] ? (u64)(bases[i] + (size_t)x.next * x.bs) : 0});
                 }
             }
@@ -487,7 +479,7 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
                 hdr.resize(h + 13);
                 wr_le32(hdr.data() + h + 5, x.bs);
                 wr_le32(hdr.data() + h + 9, x.nb);
-                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)outs[i], 13});
+                f.gather.plain({(u64)(f.meta + f.lay.hdr + h), (u64)outs[i], 13});
                 x.pos = 13;
                 x.started = true;
             }
@@ -510,8 +502,8 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
                 hdr.resize(h + 8);
                 wr_le32(hdr.data() + h, (u32)osz);
                 wr_le32(hdr.data() + h + 4, (u32)orig[k]);
-                f.segs.push_back({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
-                f.segs.push_back({(u64)f.slot(k), (u64)(outs[i] + x.pos + 8), (u64)osz});
+                f.gather.plain({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
+                f.gather.plain({(u64)f.slot(k), (u64)(outs[i] + x.pos + 8), (u64)osz});
                 x.pos += (size_t)osz + 8;
             }
             f.stage_headers(hdr);
@@ -531,6 +523,82 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
     }
 }
 
+// What a partial decode call wants of one frame: the first w bytes of the bytes phi(t) of bz3_hip.h, in its normal form.  The three calls name
+// them differently and each reduces to the form below it wherever it can, so that a request the lower call could have made takes that call's path:
+//   range    phi(t) = lo + t                                                        count == 0
+//   strided  phi(t) = lo + (t / run) stride + t % run                               count > 1 runs, stride != run
+//   select   phi(t) = lo + (t / L) stride + s_j + (t % L - P_j), piece j of `sel`   count >= 1 periods, two or more pieces
+// cut() fixes w at the smallest of *out_size, the base's size and what the request names, and then normalises: a strided request of one run (after
+// the cut) or with stride == run is the range (lo, w); a select request with w <= l_0 is the range (lo + s_0, w), any other one has `count` cut
+// to the periods w reaches.  (An entry point has already turned a piece list that joins to one piece into its strided request, and one without
+// a byte into the empty one.)
+struct Request {
+    u64 lo = 0, wanted = UINT64_MAX;     // phi(0); the bytes the request names
+    u64 run = 0, stride = 0, count = 0;  // count periods `stride` apart, of each its first `run` bytes ...
+    const PieceTable * sel = nullptr;    // ... or the L bytes of the pieces of this table, which the device has at d_tab
+    u64 d_tab = 0;
+    u64 w = 0, hi = 0;                   // after cut(): the bytes wanted, and end() = phi(w - 1) + 1: no chunk from there on is needed
+    static Request range(u64 offset) {
+        Request r;
+        r.lo = offset;
+        return r;
+    }
+    static Request strided(u64 offset, u64 run, u64 stride, u64 count) {  // (count run fits 64 bits: the caller's check)
+        Request r = range(offset);
+        r.wanted = count * run, r.run = run, r.stride = stride, r.count = count;
+        return r;
+    }
+    static Request select(u64 offset, u64 stride, u64 count, const PieceTable & t) {  // (count L fits 64 bits)
+        if (t.L == 0 || count == 0) return strided(offset, 0, 0, 0);
+        if (t.m == 1) return strided(offset + t.s(0), t.L, stride, count);
+        Request r = strided(offset, t.L, stride, count);
+        r.sel = &t;
+        return r;
+    }
+    void cut(u64 cap) {
+        w = std::min(cap, wanted);
+        const u64 periods = w && count ? (w - 1) / run + 1 : 0;  // (w > 0 with count > 0: run > 0)
+        if (sel && w > sel->l(0)) {
+            count = periods;
+            if (count == 1) stride = std::max(stride, sel->last_end());  // (one period: its stride is never used, and may be 0)
+        } else if (!sel && periods > 1 && stride != run) {
+            count = periods;
+        } else {
+            if (sel && w) lo += sel->s(0);
+            sel = nullptr;
+            run = stride = count = 0;
+        }
+        hi = end();
+    }
+    u64 end() const {
+        if (!count) return lo + w < lo ? UINT64_MAX : lo + w;
+        const u64 r = (w - 1) - (count - 1) * run;  // the last byte's place among its period's wanted bytes
+        return lo + (count - 1) * stride + (sel ? sel->byte(r) : r) + 1;
+    }
+    // The number of t < w with phi(t) < x.
+    u64 below(u64 x) const {
+        if (x <= lo) return 0;
+        const u64 d = x - lo;
+        if (!count) return std::min(d, w);
+        const u64 i = d / stride, r = d % stride;
+        return std::min(i >= count ? count * run : i * run + (sel ? sel->below(r) : std::min(r, run)), w);
+    }
+    // The walk of the next `limit` chunks that hold a byte of the request (frame.hpp).
+    WalkArg walk_arg(const WalkPos & pos, const u8 * in, size_t in_size, u32 limit, u32 rec_base) const {
+        return pos.range_arg(in, in_size, lo, hi, limit, rec_base, sel ? 0 : run, stride, count, d_tab, sel ? (u32)sel->m : 0);
+    }
+    // The gather segment of the decoded chunk in `slot` that holds the frame's bytes [p, p + orig): its wanted bytes are the output bytes
+    // [ta, tb) = [below(p), below(p + orig)), contiguous in `out` (and in the base, or nullptr) and one segment, whatever the number of runs or
+    // pieces in the chunk; in the chunk they are the bytes c(u) of planes.hpp.  Returns tb, what the frame has committed with this chunk.
+    u64 gather(GatherList & g, u64 slot, u64 p, u64 orig, u64 k, u8 * out, const u8 * base) const {
+        const u64 ta = below(p), tb = below(p + orig), dst = (u64)(out + ta), b = base ? (u64)(base + ta) : 0;
+        if (sel) g.select(slot, orig, k, lo - p, stride, *sel, d_tab, ta / run, ta % run, tb - ta, dst, b);
+        else if (count) g.strided(slot, orig, k, lo + (ta / run) * stride + ta % run - p, run - ta % run, run, stride, tb - ta, dst, b);
+        else g.range(slot, orig, k, lo + ta - p, lo + tb - p, dst, b);
+        return tb;
+    }
+};
+
 // ---- decompress: n frames whose buffers passed the pointer checks, on device dev ------------------------------------------
 // One walk reads every frame header.  Then per window: the walk of the next chunks of the frames in order, up to the
 // window's size in all (one launch, one read-back), scatter, run_decode (one CM launch), gather.  Every frame keeps its
@@ -539,51 +607,31 @@ void compress_frames(int dev, u32 block_size_arg, s32 n, const u32 * elem_sizes,
 // bases (or nullptr): per frame nullptr, or base_sizes[i] bytes that are added to the decoded bytes at the same offsets; such a frame's capacity
 // is the smaller of out_sizes[i] and base_sizes[i], so that the walk refuses a chunk that runs past the base as one that runs past `out`.
 // outs[i] may be bases[i] (planes.hpp, "In place").
-// range (bz3_hip_decompress_device_range[_many]): frame i wants the w = min(out_sizes[i], base_sizes[i]) decoded bytes from offsets[i] on
-// (offsets == nullptr: 0) and nothing is too big.  Its walks are range walks (frame.hpp): chunks that end before the range are
-// header-checked and skipped on the device, headers at or beyond its end are never read, so the windows hold only the chunks that
-// share a byte with their frame's range; the first and the last of them are gathered clipped (push_range_segment), and `committed`
-// counts range bytes.  A frame's walk is over at its last chunk, at a header error or at the end of its range.
-// periods (bz3_hip_decompress_device_strided[_many]; only with range; valid as bz3_hip.h demands): per frame (run, stride, count), the frame
-// wants the first w = min(out_sizes[i], base_sizes[i], count run) of the bytes phi(t) = offsets[i] + (t / run) stride + t % run.  A request
-// of one run (after the cut at w) or with stride == run is the contiguous range (offset, w) and takes the range path untouched.  Every
-// other one walks with its period (frame.hpp), so that its windows hold only the chunks that meet a run, up to end = phi(w - 1) + 1; in
-// the gather a chunk [p, p + o) holds the output bytes [t_a, t_b) = [below(p), below(p + o)), below(x) the number of t < w with phi(t) < x,
-// which are contiguous in `out` and one segment (push_strided_segment); `committed` is t_b.
-// selects (bz3_hip_decompress_device_select[_many]; only with periods; valid as bz3_hip.h demands): per frame nullptr, or a table of two or more
-// pieces, with periods[3 i + 1] and periods[3 i + 2] its stride and count (every other request of that call arrives normalised, as the strided
-// or empty request it is).  The frame wants the first w = min(out_sizes[i], base_sizes[i], count L) of the bytes phi(t) of bz3_hip.h.  w <= l_0
-// is the contiguous range (offset + s_0, w) and takes the range path untouched.  Every other one walks with its table (frame.hpp), which is
-// uploaded once, beside the walk's arguments; `count` is cut to the periods w reaches; the gather is the strided one with this phi
-// (push_select_segment).
+// reqs (or nullptr: whole frames, capacity-checked; bz3_hip_decompress_device_{range,strided,select}[_many]): frame i wants the bytes of reqs[i],
+// cut at min(out_sizes[i], base_sizes[i]), and nothing is too big.  Its walks are range walks (frame.hpp): chunks that end before the request's
+// first byte, or that lie in a gap between two runs or pieces, are header-checked and skipped on the device, headers at or beyond its end() are
+// never read, so the windows hold only the chunks that share a byte with their frame's request.  A request in range form walks without a period
+// and is gathered clipped at its two ends, one with a period or a piece table walks with it; the tables of a call are uploaded once, beside the
+// walk's arguments.  Every chunk is one gather segment (Request::gather) and `committed` counts the request's bytes.  A frame's walk is over at
+// its last chunk, at a header error or at the end of its request.
 void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u8 * const * bases, const size_t * base_sizes,
-                       u8 * const * outs, size_t * out_sizes, int * rcs, bool range = false, const u64 * offsets = nullptr, const u64 * periods = nullptr,
-                       const PieceTable * const * selects = nullptr) {
-    struct Frame {
-        size_t buf_max = 0, committed = 0;
+                       u8 * const * outs, size_t * out_sizes, int * rcs, const Request * reqs = nullptr) {
+    struct Frame : Request {
+        size_t buf_max = 0, committed = 0;  // the capacity (a request: its w)
         u32 decoded = 0;        // chunks decoded and committed
         u32 walked = 0;         // chunks the walks recorded, less those given back (whole frames: pos.done)
         int pending = BZ3_OK;   // the header error the walk stopped at
         bool failed = false;    // a chunk of the current window failed
-        u64 lo = 0, hi = 0;     // range: the decoded bytes wanted
-        u64 run = 0, stride = 0, count = 0;  // count > 1: of [lo, hi) only `count` runs of `run` bytes, `stride` apart; buf_max = w
-        const PieceTable * sel = nullptr;    // of every period only the pieces of this table, at device address d_tab
-        u64 d_tab = 0;
-        u64 below(u64 x) const {             // the number of t < buf_max with phi(t) < x
-            if (x <= lo) return 0;
-            const u64 d = x - lo, i = d / stride, r = d % stride;
-            if (sel) return std::min<u64>(i >= count ? count * sel->L : i * sel->L + sel->below(r), buf_max);
-            return std::min<u64>(i >= count ? count * run : i * run + std::min(r, run), buf_max);
-        }
     };
     struct Chunk {
         s32 frame;
         WalkChunk rec;
     };
+    const bool range = reqs != nullptr;
     std::vector<Frame> fr((size_t)n);
     std::vector<WalkPos> pos((size_t)n);
     std::vector<char> live((size_t)n, 0);
-    bool any = false, any_period = false, any_select = false;
+    bool any = false;
     std::vector<u64> tables;  // the piece tables of the frames that walk with one, as they are uploaded
     for (s32 i = 0; i < n; i++) {
         rcs[i] = BZ3_OK;
@@ -591,35 +639,12 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
         else live[i] = any = 1;
         fr[i].buf_max = bases && bases[i] ? std::min(out_sizes[i], base_sizes[i]) : out_sizes[i];
         if (range) {
-            fr[i].lo = offsets ? offsets[i] : 0;
-            if (selects && selects[i]) {
-                const PieceTable & t = *selects[i];
-                const u64 stride = periods[3 * i + 1], w = fr[i].buf_max = (size_t)std::min<u64>(fr[i].buf_max, periods[3 * i + 2] * t.L);
-                if (w && w <= t.l(0)) {
-                    fr[i].lo += t.s(0);
-                } else if (w) {
-                    fr[i].sel = &t;
-                    fr[i].count = (w - 1) / t.L + 1;
-                    fr[i].stride = fr[i].count > 1 ? stride : std::max(stride, t.last_end());  // (one period: its stride is never used, and may be 0)
-                    fr[i].d_tab = tables.size() * sizeof(u64);
-                    tables.insert(tables.end(), t.tab.begin(), t.tab.end());
-                    any_select = true;
-                }
-            } else if (periods) {
-                const u64 run = periods[3 * i], stride = periods[3 * i + 1], W = periods[3 * i + 2] * run;
-                const u64 w = fr[i].buf_max = (size_t)std::min<u64>(fr[i].buf_max, W), runs = w ? (w - 1) / run + 1 : 0;
-                if (runs > 1 && stride != run) {
-                    fr[i].run = run, fr[i].stride = stride, fr[i].count = runs;
-                    any_period = true;
-                }
-            }
-            fr[i].hi = fr[i].lo + (u64)fr[i].buf_max < fr[i].lo ? UINT64_MAX : fr[i].lo + (u64)fr[i].buf_max;
+            static_cast<Request &>(fr[i]) = reqs[i];
+            fr[i].cut(fr[i].buf_max);
+            fr[i].buf_max = (size_t)fr[i].w;
             if (fr[i].sel) {
-                const PieceTable & t = *fr[i].sel;
-                const u64 r = (fr[i].buf_max - 1) % t.L, j = piece_of(t.tab.data(), (u32)t.m, r);
-                fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + t.s(j) + (r - t.P(j)) + 1;  // phi(w - 1) + 1
-            } else if (fr[i].count) {
-                fr[i].hi = fr[i].lo + (fr[i].count - 1) * fr[i].stride + (fr[i].buf_max - (fr[i].count - 1) * fr[i].run);  // phi(w - 1) + 1
+                fr[i].d_tab = tables.size() * sizeof(u64);
+                tables.insert(tables.end(), fr[i].sel->tab.begin(), fr[i].sel->tab.end());
             }
             out_sizes[i] = 0;
         }
@@ -679,8 +704,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 if (!live[i] || fr[i].pending != BZ3_OK || range_walk_over(i)) continue;
                 const u64 from = std::max(fr[i].lo, pos[i].planned), est = (fr[i].hi - from) / pos[i].block_size + 2;
                 const u32 lim = (u32)std::min<u64>({est, (u64)(pos[i].n_blocks - pos[i].done), (u64)(W - win.size()), (u64)(WALK_RECORDS - base)});
-                args.push_back(pos[i].range_arg(ins[i], in_sizes[i], fr[i].lo, fr[i].hi, lim, base, fr[i].run, fr[i].stride, fr[i].count, fr[i].d_tab,
-                                                fr[i].sel ? (u32)fr[i].sel->m : 0));
+                args.push_back(fr[i].walk_arg(pos[i], ins[i], in_sizes[i], lim, base));
                 who.push_back(i);
                 base += lim;
             }
@@ -712,7 +736,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     try {
         if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64))) throw std::runtime_error("no device");
         DeviceGuard g(dev);
-        if (any_select) {  // the piece tables: one upload per call
+        if (!tables.empty()) {  // the piece tables: one upload per call
             HIP_CHECK(hipMemcpyAsync(f.meta + f.lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, f.s));
             HIP_CHECK(hipStreamSynchronize(f.s));
             for (s32 i = 0; i < n; i++)
@@ -756,7 +780,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                 f.states[k]->block_size = (s32)pos[c.frame].block_size;  // every check of the block is made against its own frame's block size
                 f.states[k]->last_error = BZ3_OK;
                 memcpy(hdrs.data() + 17 * (size_t)k, c.rec.hdr, 17);
-                f.segs.push_back({(u64)(ins[c.frame] + c.rec.in_off + 8), (u64)f.slot(k), (u64)c.rec.size});
+                f.gather.plain({(u64)(ins[c.frame] + c.rec.in_off + 8), (u64)f.slot(k), (u64)c.rec.size});
             }
             if (t) {
                 f.copy();
@@ -770,28 +794,12 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
                         x.failed = true;
                         continue;
                     }
-                    if (range && x.sel) {  // the chunk's bytes c(u) of planes.hpp, "Select merge", are the output bytes [ta, tb)
-                        const u64 p = c.rec.out_off, ta = x.below(p), tb = x.below(p + (u64)c.rec.orig);
-                        push_select_segment(f.segs, f.clips, f.periods, f.selects, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, x.lo - p, x.stride, *x.sel,
-                                            x.d_tab, ta / x.sel->L, ta % x.sel->L, tb - ta, (u64)(outs[c.frame] + ta), bases && bases[c.frame] ? (u64)(bases[c.frame] + ta) : 0);
-                        x.committed = (size_t)tb;
-                    } else if (range && x.count) {  // the chunk's bytes c(u) are the output bytes [ta, tb)
-                        const u64 p = c.rec.out_off, ta = x.below(p), tb = x.below(p + (u64)c.rec.orig);
-                        const u64 c0 = x.lo + (ta / x.run) * x.stride + ta % x.run - p;
-                        push_strided_segment(f.segs, f.clips, f.periods, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, c0, x.run - ta % x.run, x.run,
-                                             x.stride, tb - ta, (u64)(outs[c.frame] + ta), bases && bases[c.frame] ? (u64)(bases[c.frame] + ta) : 0);
-                        if (any_select) f.selects.insert(f.selects.end(), SELECT_PARAMS, 0);
-                        x.committed = (size_t)tb;
-                    } else if (range) {  // the chunk's bytes [a, b) are the range's from `at` on
-                        const u64 p = c.rec.out_off, a = x.lo > p ? x.lo - p : 0, b = std::min<u64>(x.hi - p, (u64)c.rec.orig), at = p + a - x.lo;
-                        push_range_segment(f.segs, f.clips, (u64)f.slot(k), (u64)c.rec.orig, elem_sizes ? (u64)elem_sizes[c.frame] : 1, a, b, (u64)(outs[c.frame] + at),
-                                           bases && bases[c.frame] ? (u64)(bases[c.frame] + at) : 0);
-                        if (any_period || any_select) f.periods.insert(f.periods.end(), STRIDED_PARAMS, 0);
-                        if (any_select) f.selects.insert(f.selects.end(), SELECT_PARAMS, 0);
-                        x.committed = (size_t)(p + b - x.lo);
+                    const u64 es = elem_sizes ? (u64)elem_sizes[c.frame] : 1;
+                    const u8 * base = bases ? bases[c.frame] : nullptr;
+                    if (range) {
+                        x.committed = (size_t)x.gather(f.gather, (u64)f.slot(k), c.rec.out_off, (u64)c.rec.orig, es, outs[c.frame], base);
                     } else {
-                        f.segs.push_back({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, (elem_sizes ? (u64)elem_sizes[c.frame] : 1) | PLANES_INVERSE,
-                                          bases && bases[c.frame] ? (u64)(bases[c.frame] + c.rec.out_off) : 0});
+                        f.gather.plain({(u64)f.slot(k), (u64)(outs[c.frame] + c.rec.out_off), (u64)c.rec.orig, es | PLANES_INVERSE, base ? (u64)(base + c.rec.out_off) : 0});
                         x.committed = c.rec.out_off + (size_t)c.rec.orig;
                     }
                     x.decoded++;
@@ -925,6 +933,30 @@ bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
     return true;
 }
 
+
+// The three partial decode calls: the whole-call checks they share, frame i's request from make(i, request) (false: an invalid one, which fails
+// the whole call before any write), then decompress_frames.  A base is device memory of the same GPU, and `out` is the base itself or does not
+// overlap it; the overlap is judged on the w = min(out_sizes[i], base_sizes[i], what the request names) bytes the call can touch of each: two
+// runs of w bytes overlap iff they start less than w apart.
+int decompress_requests(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], bool params_ok, const void * const bases[],
+                        const size_t base_sizes[], void * const outs[], size_t out_sizes[], int rcs[],
+                        const std::function<bool(s32, Request &)> & make) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params_ok || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    std::vector<Request> reqs((size_t)n);
+    for (s32 i = 0; i < n; i++)
+        if (!make(i, reqs[(size_t)i])) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    for (s32 i = 0; bases && i < n; i++) {
+        if (!bases[i] || !base_sizes[i]) continue;
+        const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], reqs[(size_t)i].wanted}), x = (u64)outs[i], y = (u64)bases[i];
+        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, reqs.data());
+    return first_error(n, rcs);
+}
 }  // namespace
 
 BZIP3_API int bz3_hip_compress_device_delta(uint32_t block_size, uint32_t elem_size, const void * in, const void * base, void * out, size_t in_size,
@@ -1029,49 +1061,25 @@ BZIP3_API int bz3_hip_decompress_device_delta_many(int32_t n, const uint32_t ele
 BZIP3_API int bz3_hip_decompress_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
                                                    const uint64_t offsets[], const void * const bases[], const size_t base_sizes[], void * const outs[],
                                                    size_t out_sizes[], int rcs[]) {
-    if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
-        if (!bases[i] || !base_sizes[i]) continue;
-        // the call touches w = min(*out_size, base_size) bytes of each at the most: two runs of w bytes overlap iff they start less than w apart
-        const u64 w = out_sizes[i] < base_sizes[i] ? out_sizes[i] : base_sizes[i], x = (u64)outs[i], y = (u64)bases[i];
-        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    }
-    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true,
-                      (const u64 *)offsets);
-    return first_error(n, rcs);
+    return decompress_requests(n, elem_sizes, ins, in_sizes, true, bases, base_sizes, outs, out_sizes, rcs, [&](s32 i, Request & r) {
+        r = Request::range(offsets ? offsets[i] : 0);
+        return true;
+    });
 }
 
-// params: per frame (offset, run, stride, count).  The whole-call checks of the range call, then the validity of every period; the overlap of
-// `out` and a base is judged on the w = min(out_sizes[i], base_sizes[i], count run) bytes the call can touch of each.
+// params: per frame (offset, run, stride, count), valid as bz3_hip.h demands.
 BZIP3_API int bz3_hip_decompress_device_strided_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
                                                      const uint64_t params[], const void * const bases[], const size_t base_sizes[], void * const outs[],
                                                      size_t out_sizes[], int rcs[]) {
-    if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    std::vector<u64> offsets((size_t)n), periods(3 * (size_t)n);
-    for (s32 i = 0; i < n; i++) {
+    return decompress_requests(n, elem_sizes, ins, in_sizes, params != nullptr, bases, base_sizes, outs, out_sizes, rcs, [&](s32 i, Request & r) {
         const u64 offset = params[4 * i], run = params[4 * i + 1], stride = params[4 * i + 2], count = params[4 * i + 3];
-        offsets[(size_t)i] = offset;
-        periods[3 * (size_t)i] = run, periods[3 * (size_t)i + 1] = stride, periods[3 * (size_t)i + 2] = count;
-        if (run == 0 || count == 0) continue;  // W = 0
-        const unsigned __int128 W = (unsigned __int128)count * run, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + run;
-        if ((count > 1 && stride < run) || W > UINT64_MAX || last > UINT64_MAX) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    }
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
-        if (!bases[i] || !base_sizes[i]) continue;
-        const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], periods[3 * (size_t)i] * periods[3 * (size_t)i + 2]}), x = (u64)outs[i], y = (u64)bases[i];
-        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    }
-    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true, offsets.data(),
-                      periods.data());
-    return first_error(n, rcs);
+        if (run && count) {  // (else W = 0)
+            const unsigned __int128 W = (unsigned __int128)count * run, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + run;
+            if ((count > 1 && stride < run) || W > UINT64_MAX || last > UINT64_MAX) return false;
+        }
+        r = Request::strided(offset, run, stride, count);
+        return true;
+    });
 }
 
 BZIP3_API int bz3_hip_decompress_device_strided(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t run, uint64_t stride, uint64_t count,
@@ -1085,47 +1093,25 @@ BZIP3_API int bz3_hip_decompress_device_strided(uint32_t elem_size, const void *
     return bz3_hip_decompress_device_strided_many(1, &elem_size, ins, &in_size, params, bases, &base_size, outs, out_size, &rc);
 }
 
-// params: per frame (offset, stride, count, m); pieces[i]: m pairs (s_j, l_j) in host memory.  The whole-call checks of the range call, then the
-// validity of every request and its normal form: no piece left is the empty request, one piece the strided request (offset + s_0, l_0, stride,
-// count), and a call without a frame of two or more pieces is that strided call.
+// params: per frame (offset, stride, count, m); pieces[i]: m pairs (s_j, l_j) in host memory, valid as bz3_hip.h demands.  Request::select gives a
+// request its normal form: no piece left is the empty request, one piece the strided request (offset + s_0, l_0, stride, count), so a call
+// without a frame of two or more pieces is that strided call.
 BZIP3_API int bz3_hip_decompress_device_select_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
                                                     const uint64_t params[], const uint64_t * const pieces[], const void * const bases[], const size_t base_sizes[],
                                                     void * const outs[], size_t out_sizes[], int rcs[]) {
-    if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    std::vector<u64> offsets((size_t)n), periods(3 * (size_t)n, 0), wanted((size_t)n, 0);
-    std::vector<PieceTable> tables((size_t)n);
-    std::vector<const PieceTable *> selects((size_t)n, nullptr);
-    for (s32 i = 0; i < n; i++) {
+    std::vector<PieceTable> tables;  // (sized once the whole-call checks have passed)
+    return decompress_requests(n, elem_sizes, ins, in_sizes, params != nullptr, bases, base_sizes, outs, out_sizes, rcs, [&](s32 i, Request & r) {
         const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
+        tables.resize((size_t)n);
         PieceTable & t = tables[(size_t)i];
-        offsets[(size_t)i] = offset;
-        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-        if (t.L == 0 || count == 0) continue;  // W = 0: the period (0, 0, 0)
-        const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
-        if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-        wanted[(size_t)i] = (u64)W;
-        periods[3 * (size_t)i + 1] = stride, periods[3 * (size_t)i + 2] = count;
-        if (t.m == 1) {
-            offsets[(size_t)i] = offset + t.s(0);
-            periods[3 * (size_t)i] = t.L;
-        } else {
-            selects[(size_t)i] = &t;
+        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return false;
+        if (t.L && count) {  // (else W = 0)
+            const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
+            if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX) return false;
         }
-    }
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    for (s32 i = 0; bases && i < n; i++) {  // a base: device memory of the same GPU; `out` is the base itself or does not overlap it
-        if (!bases[i] || !base_sizes[i]) continue;
-        const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], wanted[(size_t)i]}), x = (u64)outs[i], y = (u64)bases[i];
-        if (device_of(bases[i]) != dev || (x != y && (x > y ? x - y : y - x) < w)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    }
-    bool any = false;
-    for (const PieceTable * t : selects) any |= t != nullptr;
-    decompress_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, (const u8 * const *)bases, base_sizes, (u8 * const *)outs, out_sizes, rcs, true, offsets.data(),
-                      periods.data(), any ? selects.data() : nullptr);
-    return first_error(n, rcs);
+        r = Request::select(offset, stride, count, t);
+        return true;
+    });
 }
 
 BZIP3_API int bz3_hip_decompress_device_select(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t stride, uint64_t count, uint64_t m,
@@ -1189,6 +1175,29 @@ struct ScratchStream {
     }
 };
 
+// The frame of a debug launch: dst, src and (with need_base) base are device memory of one GPU; then a stream and an allocation for the tables of
+// n segments up to `level` and `extra` bytes behind them, the segments from fill(g, the device address of the extra bytes, the stream), one
+// launch.  BZ3_ERR_INIT for everything that goes wrong.
+int32_t debug_launch(const void * src, const void * base, bool need_base, void * dst, size_t n, int level, size_t extra,
+                     const std::function<void(GatherList &, u8 *, hipStream_t)> & fill) {
+    const int dev = device_of(dst);
+    if (dev < 0 || device_of(src) != dev || (need_base && device_of(base) != dev)) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    try {
+        DeviceGuard g(dev);
+        const size_t tab_bytes = align256(table_bytes(n, level));
+        sc.open(tab_bytes + extra);
+        GatherList list;
+        fill(list, sc.mem + tab_bytes, sc.s);
+        std::vector<u8> staging;
+        copy_segments(list, staging, sc.mem, sc.s);
+        HIP_CHECK(hipStreamSynchronize(sc.s));
+    } catch (...) {
+        return BZ3_ERR_INIT;
+    }
+    return BZ3_OK;
+}
+
 // n segments of `width` u64 each relative to src / base / dst, one launch: (src_off, dst_off, len[, elem_size | inverse << 8]), or with
 // width 5 (src_off, base_off, dst_off, len, elem_size | inverse << 8), base_off = UINT64_MAX for a segment without a base.
 int32_t debug_move_segments(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, int width) {
@@ -1197,27 +1206,17 @@ int32_t debug_move_segments(const void * src, const void * base, void * dst, con
         const u64 mode = segs[width * i + width - 1];
         if (!planes_elem_size_ok(mode & 0xff) || (mode >> 9)) return BZ3_ERR_INIT;
     }
-    const int dev = device_of(dst);
-    if (dev < 0 || device_of(src) != dev || (width == 5 && device_of(base) != dev)) return BZ3_ERR_INIT;
-    ScratchStream sc;
-    int rc = BZ3_OK;
-    try {
-        DeviceGuard g(dev);
-        std::vector<CopySeg> v((size_t)n);
+    return debug_launch(src, base, width == 5, dst, (size_t)n, SEG_DELTA, 0, [&](GatherList & g, u8 *, hipStream_t) {
         for (s32 i = 0; i < n; i++) {
             const uint64_t * q = segs + (size_t)width * i;
-            if (width == 5) v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[2], q[3], q[4], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]};
-            else v[(size_t)i] = {(u64)src + q[0], (u64)dst + q[1], q[2], width == 4 ? q[3] : 0, 0};
+            if (width == 5) g.plain({(u64)src + q[0], (u64)dst + q[2], q[3], q[4], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]});
+            else g.plain({(u64)src + q[0], (u64)dst + q[1], q[2], width == 4 ? q[3] : 0, 0});
         }
-        std::vector<u8> staging;
-        sc.open(copy_table_bytes((size_t)n));
-        copy_segments(v, staging, sc.mem, sc.s);
-        HIP_CHECK(hipStreamSynchronize(sc.s));
-    } catch (...) {
-        rc = BZ3_ERR_INIT;
-    }
-    return rc;
+    });
 }
+
+// The base address of a debug tuple's segment: base_off == UINT64_MAX is no base.
+u64 debug_base(const void * base, u64 base_off) { return base_off == UINT64_MAX ? 0 : (u64)base + base_off; }
 }  // namespace
 
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 3); }
@@ -1238,26 +1237,12 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
         if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
         any_base |= q[1] != UINT64_MAX;
     }
-    const int dev = device_of(dst);
-    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
-    ScratchStream sc;
-    int rc = BZ3_OK;
-    try {
-        DeviceGuard g(dev);
-        std::vector<CopySeg> v;
-        std::vector<u64> clips;
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
         for (s32 i = 0; i < n; i++) {
             const uint64_t * q = segs + (size_t)7 * i;
-            push_range_segment(v, clips, (u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+            g.range((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], debug_base(base, q[1]));
         }
-        std::vector<u8> staging;
-        sc.open(range_table_bytes((size_t)n));
-        copy_segments(v, staging, sc.mem, sc.s, &clips);
-        HIP_CHECK(hipStreamSynchronize(sc.s));
-    } catch (...) {
-        rc = BZ3_ERR_INIT;
-    }
-    return rc;
+    });
 }
 
 // n tuples of 10 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, c0, first, run, stride, nbytes): of the merge of the `len` bytes at
@@ -1272,27 +1257,12 @@ BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, voi
         if (q[9] && (q[7] == 0 || q[6] == 0 || q[6] > q[7] || q[8] < q[7] || strided_last_byte(q[5], q[6], q[7], q[8], q[9]) >= q[3])) return BZ3_ERR_INIT;
         any_base |= q[1] != UINT64_MAX;
     }
-    const int dev = device_of(dst);
-    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
-    ScratchStream sc;
-    int rc = BZ3_OK;
-    try {
-        DeviceGuard g(dev);
-        std::vector<CopySeg> v;
-        std::vector<u64> clips, periods;
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_STRIDED, 0, [&](GatherList & g, u8 *, hipStream_t) {
         for (s32 i = 0; i < n; i++) {
             const uint64_t * q = segs + (size_t)10 * i;
-            push_strided_segment(v, clips, periods, (u64)src + q[0], q[3], q[4] & 0xff, q[9] ? q[5] : 0, q[6], q[7], q[8], q[9], (u64)dst + q[2],
-                                 q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+            g.strided((u64)src + q[0], q[3], q[4] & 0xff, q[9] ? q[5] : 0, q[6], q[7], q[8], q[9], (u64)dst + q[2], debug_base(base, q[1]));
         }
-        std::vector<u8> staging;
-        sc.open(strided_table_bytes((size_t)n));
-        copy_segments(v, staging, sc.mem, sc.s, &clips, &periods);
-        HIP_CHECK(hipStreamSynchronize(sc.s));
-    } catch (...) {
-        rc = BZ3_ERR_INIT;
-    }
-    return rc;
+    });
 }
 
 // n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, rel, stride, q0, r0, nbytes, first_piece, m): of the merge of the `len`
@@ -1303,65 +1273,36 @@ BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void
     if (n < 0 || (n > 0 && !segs) || (n_pieces && !pieces)) return BZ3_ERR_INIT;
     bool any_base = false;
     std::vector<PieceTable> tabs((size_t)n);
-    size_t words = 0;
+    std::vector<u64> all;  // the tables one after the other, as they are uploaded
     for (s32 i = 0; i < n; i++) {
         const uint64_t * q = segs + (size_t)12 * i;
         const u64 len = q[3], rel = q[5], stride = q[6], q0 = q[7], r0 = q[8], nbytes = q[9], first = q[10], m = q[11];
         if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || len >= ((u64)1 << 31) || nbytes > len) return BZ3_ERR_INIT;
         if (first > n_pieces || m > n_pieces - first || m >= ((u64)1 << 31)) return BZ3_ERR_INIT;
-        PieceTable & t = tabs[(size_t)i];  // the list as it is: (s_j, P_j) for every piece, then P_m
-        u64 end = 0;
-        for (u64 j = 0; j < m; j++) {
-            const u64 sj = pieces[2 * (first + j)], lj = pieces[2 * (first + j) + 1];
-            if (sj + lj < sj || (j && sj < end) || t.L + lj < lj) return BZ3_ERR_INIT;
-            t.tab.push_back(sj);
-            t.tab.push_back(t.L);
-            t.L += lj;
-            end = sj + lj;
-        }
-        t.tab.push_back(0);
-        t.tab.push_back(t.L);
-        t.m = m;
-        words += t.tab.size();
+        PieceTable & t = tabs[(size_t)i];
+        if (!t.take(m ? pieces + 2 * first : nullptr, m, false)) return BZ3_ERR_INIT;
+        all.insert(all.end(), t.tab.begin(), t.tab.end());
         any_base |= q[1] != UINT64_MAX;
         if (!nbytes) continue;
-        if (t.L == 0 || r0 >= t.L || (nbytes > t.L - r0 && stride < end)) return BZ3_ERR_INIT;
+        if (t.L == 0 || r0 >= t.L || (nbytes > t.L - r0 && stride < t.given_end)) return BZ3_ERR_INIT;
         for (const u64 u : {(u64)0, nbytes - 1}) {  // c(0) and c(nbytes - 1) lie in the chunk (c increases)
-            const u64 x = r0 + u, r = x % t.L, j = piece_of(t.tab.data(), (u32)m, r);
+            const u64 x = r0 + u;
             const unsigned __int128 period = (unsigned __int128)q0 + x / t.L;
             if (stride && period > UINT64_MAX / stride) return BZ3_ERR_INIT;
-            const __int128 c = (__int128)(s64)rel + (__int128)(period * stride) + t.s(j) + (r - t.P(j));
+            const __int128 c = (__int128)(s64)rel + (__int128)(period * stride) + t.byte(x % t.L);
             if (c < 0 || c >= (__int128)len) return BZ3_ERR_INIT;
         }
     }
-    const int dev = device_of(dst);
-    if (dev < 0 || device_of(src) != dev || (any_base && device_of(base) != dev)) return BZ3_ERR_INIT;
-    ScratchStream sc;
-    int rc = BZ3_OK;
-    try {
-        DeviceGuard g(dev);
-        const size_t tab_bytes = align256(select_table_bytes((size_t)n));
-        sc.open(tab_bytes + words * sizeof(u64) + 16);
-        std::vector<u64> all;
-        std::vector<CopySeg> v;
-        std::vector<u64> clips, periods, selects;
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
+        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+        size_t at = 0;
         for (s32 i = 0; i < n; i++) {
             const uint64_t * q = segs + (size_t)12 * i;
             const PieceTable & t = tabs[(size_t)i];
-            const u64 d_tab = (u64)(sc.mem + tab_bytes) + all.size() * sizeof(u64);
-            all.insert(all.end(), t.tab.begin(), t.tab.end());
-            if (q[9])
-                push_select_segment(v, clips, periods, selects, (u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, d_tab, q[7], q[8], q[9], (u64)dst + q[2],
-                                    q[1] == UINT64_MAX ? 0 : (u64)base + q[1]);
+            if (q[9]) g.select((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, (u64)d_tabs + at * sizeof(u64), q[7], q[8], q[9], (u64)dst + q[2], debug_base(base, q[1]));
+            at += t.tab.size();
         }
-        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(sc.mem + tab_bytes, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, sc.s));
-        std::vector<u8> staging;
-        copy_segments(v, staging, sc.mem, sc.s, &clips, &periods, &selects);
-        HIP_CHECK(hipStreamSynchronize(sc.s));
-    } catch (...) {
-        rc = BZ3_ERR_INIT;
-    }
-    return rc;
+    });
 }
 
 // The CRC-32C of bz3's block headers (crc32sum, src/libbz3.c: state init, no inversion) of n buffers in device memory of one GPU, at any

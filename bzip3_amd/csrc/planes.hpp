@@ -109,8 +109,8 @@ constexpr u32 PLANES_LOAD_ELEMS = COPY_THREADS * 16;        // elements a workgr
 constexpr u32 PLANE_STRIDE = PLANES_LOAD_ELEMS + 16;        // LDS bytes per plane (split): phase 2 reads up to 20 bytes from offset < 4080
 constexpr u32 PLANES_LDS_BYTES = 8 * PLANE_STRIDE;          // >= 8 * PLANES_LOAD_ELEMS + 16, the merge layout
 constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = elem_size | PLANES_INVERSE for merge
-constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments alone)
-constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments alone)
+constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments and the kernels above it)
+constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments and k_select_segments)
 constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
 constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone)
 constexpr u32 SELECT_PARAMS = 7;                            // u64 per segment in its side table: rel, stride, q0, r0, nbytes, the piece table's address, m
@@ -369,21 +369,26 @@ __device__ __forceinline__ void planes_tile(const CopySeg & sg, u64 tile, u8 * l
     }
 }
 
-// k_copy_segments for a launch in which some segment has an element size: segments without one take copy_tile as before, the
-// others split_tile / merge_tile.  tile_start counts a segment's workgroups with segment_tiles.  (A kernel of its own so that launches
-// of plain copies keep k_copy_segments, which holds no LDS.)
-__global__ void __launch_bounds__(COPY_THREADS) k_move_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
-    const u32 b = blockIdx.x;
+// The segment that holds workgroup b of a launch: tile_start[lo] <= b < tile_start[lo + 1].
+__device__ __forceinline__ u32 segment_of_tile(const u32 * __restrict__ tile_start, u32 nseg, u32 b) {
     u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
     while (hi - lo > 1) {
         const u32 mid = (lo + hi) >> 1;
         if (tile_start[mid] <= b) lo = mid;
         else hi = mid;
     }
+    return lo;
+}
+
+// k_copy_segments for a launch in which some segment has an element size: segments without one take copy_tile as before, the
+// others split_tile / merge_tile.  tile_start counts a segment's workgroups with segment_tiles.  (A kernel of its own so that launches
+// of plain copies keep k_copy_segments, which holds no LDS.)
+__global__ void __launch_bounds__(COPY_THREADS) k_move_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
     const CopySeg sg = segs[lo];
-    if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, b - tile_start[lo], (u8 *)lds);
-    else copy_segment_tile(sg, b - tile_start[lo]);
+    if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, blockIdx.x - tile_start[lo], (u8 *)lds);
+    else copy_segment_tile(sg, blockIdx.x - tile_start[lo]);
 }
 
 // ---- delta segments ---------------------------------------------------------------------------------------------------------------
@@ -417,32 +422,6 @@ __device__ __forceinline__ void delta1_tile(const u8 * src, const u8 * base, u8 
             const u64 b0 = a > d0 ? a : d0, b1 = a + 16 < d1 ? a + 16 : d1;
             for (u64 b = b0; b < b1; b++) *(u8 *)b = INV ? (u8)(*(const u8 *)(b + ds) + *(const u8 *)(b + db)) : (u8)(*(const u8 *)(b + ds) - *(const u8 *)(b + db));
         }
-    }
-}
-
-// k_move_segments for a launch in which some segment has a base: those segments take the delta tiles, the others what they take in
-// k_move_segments.  (A kernel of its own, as k_move_segments is: launches without a base keep the code and the registers they had.)
-__global__ void __launch_bounds__(COPY_THREADS) k_delta_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
-    const u32 b = blockIdx.x;
-    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const CopySeg sg = segs[lo];
-    const u32 tile = b - tile_start[lo];
-    if (!sg.base) {
-        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
-        else copy_segment_tile(sg, tile);
-    } else if ((sg.mode & 0xff) > 1) {
-        planes_tile<true>(sg, tile, (u8 *)lds);
-    } else {
-        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
-        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
-        if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
-        else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
     }
 }
 
@@ -505,48 +484,6 @@ __device__ __forceinline__ void clip_merge_tile(const u8 * src, const u8 * base,
     if (rel == 0 && threadIdx.x < len - m * K) {
         const u64 t = m * K + threadIdx.x;
         if (t >= ca && t < cb) dst[t - ca] = D ? (u8)(src[t] + base[t - ca]) : src[t];
-    }
-}
-
-// k_delta_segments for a launch in which some segment is a clipped merge: clips[2 i], clips[2 i + 1] are segment i's [a, b) (read for
-// segments with PLANES_CLIP alone); tile_start counts such a segment's workgroups with clip_tiles.  The other segments take what they
-// take in k_delta_segments.  (A kernel of its own, once more: launches without a clip keep the three kernels above as they are.)
-__global__ void __launch_bounds__(COPY_THREADS) k_range_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
-                                                                 const u64 * __restrict__ clips) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
-    const u32 b = blockIdx.x;
-    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const CopySeg sg = segs[lo];
-    const u32 tile = b - tile_start[lo];
-    if (sg.mode & PLANES_CLIP) {
-        const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
-        const u8 * src = (const u8 *)sg.src;
-        const u8 * base = (const u8 *)sg.base;
-        u8 * dst = (u8 *)sg.dst;
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            default: break;
-        }
-    } else if (!sg.base) {
-        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
-        else copy_segment_tile(sg, tile);
-    } else if ((sg.mode & 0xff) > 1) {
-        planes_tile<true>(sg, tile, (u8 *)lds);
-    } else {
-        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
-        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
-        if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
-        else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
     }
 }
 
@@ -616,66 +553,6 @@ __device__ __forceinline__ void strided_tile(const u8 * src, const u8 * base, u8
     const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ua, dend);
     const u64 s1 = ua + PLANES_TILE_ELEMS * K >= nbytes ? dend : align16_up_to(d0 + ua + PLANES_TILE_ELEMS * K, dend);
     store_from_lds<K>(lds, d0 + ua, s0, s1);  // at most 255 K + 1 granules
-}
-
-// k_range_segments for a launch in which some segment is a strided merge: periods[5 i .. 5 i + 4] are segment i's c0, first, run, stride
-// and nbytes (read for segments with PLANES_STRIDED alone); tile_start counts such a segment's workgroups with strided_tiles.  The other
-// segments take what they take in k_range_segments.  (A kernel of its own, as the three before it: launches without a strided segment
-// keep the four kernels above as they are.)
-__global__ void __launch_bounds__(COPY_THREADS) k_strided_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
-                                                                   const u64 * __restrict__ clips, const u64 * __restrict__ periods) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
-    const u32 b = blockIdx.x;
-    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const CopySeg sg = segs[lo];
-    const u32 tile = b - tile_start[lo];
-    const u8 * src = (const u8 *)sg.src;
-    const u8 * base = (const u8 *)sg.base;
-    u8 * dst = (u8 *)sg.dst;
-    if (sg.mode & PLANES_STRIDED) {
-        const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
-        const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
-        const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)
-        const u32 gap = nbytes > first ? (u32)(pp[3] - pp[2]) : 0;
-        const u32 len = (u32)sg.len;
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            default: break;
-        }
-    } else if (sg.mode & PLANES_CLIP) {
-        const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            default: break;
-        }
-    } else if (!sg.base) {
-        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
-        else copy_segment_tile(sg, tile);
-    } else if ((sg.mode & 0xff) > 1) {
-        planes_tile<true>(sg, tile, (u8 *)lds);
-    } else {
-        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
-        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
-        if (sg.mode & PLANES_INVERSE) delta1_tile<true>(src, base, dst, sg.len, g_first, g_last);
-        else delta1_tile<false>(src, base, dst, sg.len, g_first, g_last);
-    }
 }
 
 // ---- select merge --------------------------------------------------------------------------------------------------------------------
@@ -769,72 +646,72 @@ __device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 
     store_from_lds<K>(lds, d0 + ua, s0, s1);  // at most 255 K + 1 granules
 }
 
-// k_strided_segments for a launch in which some segment is a select merge: selects[7 i .. 7 i + 6] are segment i's SELECT_PARAMS (read for
-// segments with PLANES_SELECT alone); tile_start counts such a segment's workgroups with strided_tiles.  The other segments take what they
-// take in k_strided_segments.  (A kernel of its own, as the four before it: launches without a select segment keep the five kernels above
-// as they are.)
-__global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
-                                                                  const u64 * __restrict__ clips, const u64 * __restrict__ periods, const u64 * __restrict__ selects) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
-    const u32 b = blockIdx.x;
-    u32 lo = 0, hi = nseg;  // invariant: tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
+// ---- the segment kernels -------------------------------------------------------------------------------------------------------------
+// The kinds of segment a launch may hold, in the order they were added: every kind's kernel handles the kinds below it as well.
+enum SegLevel : int { SEG_DELTA = 0, SEG_CLIP = 1, SEG_STRIDED = 2, SEG_SELECT = 3 };
+
+// One workgroup of a launch whose highest segment kind is LEVEL: the tile of its segment, by the segment's mode.  clips[2 i], clips[2 i + 1]
+// are segment i's [a, b) (read for segments with PLANES_CLIP alone, LEVEL >= SEG_CLIP), periods[5 i .. 5 i + 4] its c0, first, run, stride and
+// nbytes (PLANES_STRIDED, LEVEL >= SEG_STRIDED), selects[7 i .. 7 i + 6] its SELECT_PARAMS (PLANES_SELECT, LEVEL == SEG_SELECT); tile_start counts
+// a segment's workgroups with strided_tiles, strided_tiles, clip_tiles and segment_tiles in that order.  A branch above LEVEL is not compiled,
+// so a kernel holds the code of its own kinds alone.  (The switch value is written out in every branch: computed once above them it costs
+// four to six SGPRs.)
+template <int LEVEL>
+__device__ __forceinline__ void segments_tile(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg, const u64 * __restrict__ clips,
+                                              const u64 * __restrict__ periods, const u64 * __restrict__ selects, u8 * lds) {
+    const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
     const CopySeg sg = segs[lo];
-    const u32 tile = b - tile_start[lo];
+    const u32 tile = blockIdx.x - tile_start[lo];
     const u8 * src = (const u8 *)sg.src;
     const u8 * base = (const u8 *)sg.base;
     u8 * dst = (u8 *)sg.dst;
-    if (sg.mode & PLANES_SELECT) {
+    if (LEVEL >= SEG_SELECT && (sg.mode & PLANES_SELECT)) {
         const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
         const u32 len = (u32)sg.len;
         switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: select_tile<1, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 2: select_tile<2, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 4: select_tile<4, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 8: select_tile<8, false>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 1 | 16: select_tile<1, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 2 | 16: select_tile<2, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 4 | 16: select_tile<4, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
-            case 8 | 16: select_tile<8, true>(src, base, dst, len, sp, tile, (u8 *)lds); break;
+            case 1: select_tile<1, false>(src, base, dst, len, sp, tile, lds); break;
+            case 2: select_tile<2, false>(src, base, dst, len, sp, tile, lds); break;
+            case 4: select_tile<4, false>(src, base, dst, len, sp, tile, lds); break;
+            case 8: select_tile<8, false>(src, base, dst, len, sp, tile, lds); break;
+            case 1 | 16: select_tile<1, true>(src, base, dst, len, sp, tile, lds); break;
+            case 2 | 16: select_tile<2, true>(src, base, dst, len, sp, tile, lds); break;
+            case 4 | 16: select_tile<4, true>(src, base, dst, len, sp, tile, lds); break;
+            case 8 | 16: select_tile<8, true>(src, base, dst, len, sp, tile, lds); break;
             default: break;
         }
-    } else if (sg.mode & PLANES_STRIDED) {
+    } else if (LEVEL >= SEG_STRIDED && (sg.mode & PLANES_STRIDED)) {
         const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
         const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
         const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)
         const u32 gap = nbytes > first ? (u32)(pp[3] - pp[2]) : 0;
         const u32 len = (u32)sg.len;
         switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
-            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, (u8 *)lds); break;
+            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
+            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
             default: break;
         }
-    } else if (sg.mode & PLANES_CLIP) {
+    } else if (LEVEL >= SEG_CLIP && (sg.mode & PLANES_CLIP)) {
         const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
         switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+            case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+            case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+            case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+            case 2 | 16: clip_merge_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+            case 4 | 16: clip_merge_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+            case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
             default: break;
         }
     } else if (!sg.base) {
-        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, (u8 *)lds);
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, lds);
         else copy_segment_tile(sg, tile);
     } else if ((sg.mode & 0xff) > 1) {
-        planes_tile<true>(sg, tile, (u8 *)lds);
+        planes_tile<true>(sg, tile, lds);
     } else {
         const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
         const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
@@ -842,5 +719,32 @@ __global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg 
         else delta1_tile<false>(src, base, dst, sg.len, g_first, g_last);
     }
 }
+
+// The four kernels of launches in which some segment has a base, is a clipped, a strided or a select merge.  Kernels of their own, as
+// k_move_segments is, so that a launch without the higher kinds keeps the code and the registers of the kernel below: the wrappers declare
+// the LDS and pass the tables they have.
+__global__ void __launch_bounds__(COPY_THREADS) k_delta_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    segments_tile<SEG_DELTA>(segs, tile_start, nseg, nullptr, nullptr, nullptr, (u8 *)lds);
+}
+
+__global__ void __launch_bounds__(COPY_THREADS) k_range_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                 const u64 * __restrict__ clips) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    segments_tile<SEG_CLIP>(segs, tile_start, nseg, clips, nullptr, nullptr, (u8 *)lds);
+}
+
+__global__ void __launch_bounds__(COPY_THREADS) k_strided_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                   const u64 * __restrict__ clips, const u64 * __restrict__ periods) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    segments_tile<SEG_STRIDED>(segs, tile_start, nseg, clips, periods, nullptr, (u8 *)lds);
+}
+
+__global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                  const u64 * __restrict__ clips, const u64 * __restrict__ periods, const u64 * __restrict__ selects) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    segments_tile<SEG_SELECT>(segs, tile_start, nseg, clips, periods, selects, (u8 *)lds);
+}
+
 
 }  // namespace bz3

@@ -581,3 +581,33 @@ def test_many_whole_call_errors(emu):
     assert call(n=-1)[0] == INIT
     assert emu.bz3_hip_decompress_device_select_many(0, None, None, None, None, None, None, None, None, None, None) == 0
     assert emu.bz3_hip_decompress_device_select_many(2, None, None, None, None, None, None, None, None, None, None) == INIT
+
+
+@pytest.mark.parametrize("window", [2, 8])
+def test_one_call_holds_every_request_form(emu, window, monkeypatch):
+    """Five frames of element size 4 in one _many call, two of them with a base: a one-run range, the whole tensor, a two-run strided request,
+    a two-piece select request and a select request with w <= l_0.  Every frame is a full block of 65 KiB + 3 and a short one, and every
+    request but the whole tensor lies in the short chunk.  Windows of two chunks gather (clipped, whole), (whole, strided) and (select,
+    clipped) in one launch each; a window of eight gathers all six chunks, so that ONE launch holds whole, clipped, strided and select
+    segments side by side, each with the parameters of its own kind.  Every output is the numpy slice full[phi(t)] of the reference decode."""
+    monkeypatch.setenv("BZ3_HIP_FRAME_WINDOW", str(window))
+    ref = require_ref().lib
+    bs = BS + 3
+    plain, based = (Case(ref, bs, 4, wb, stream_for(bs, blocks=1, last=6001), seed=310 + wb) for wb in (0, 1))
+    assert plain.sizes == [bs, 6001]
+    # (case, (offset, stride, count), pieces, *out_size)
+    plan = [(based, (bs + 10, 0, 1), [(0, 777)], 10 ** 6),  # one run inside chunk 1
+            (plain, (0, 0, 1), [(0, plain.T)], 10 ** 6),  # the whole tensor: both chunks, whole
+            (plain, (bs + 5, 1000, 2), [(3, 401)], 10 ** 6),  # two runs
+            (based, (bs + 100, 2000, 2), [(0, 300), (650, 130)], 10 ** 6),  # two pieces
+            (plain, (bs + 9, 900, 3), [(4, 500), (600, 100)], 333)]  # w <= l_0: the range (offset + 4, 333)
+    params, lists, caps = [p for _, p, _, _ in plan], [l for *_, l, _ in plan], [cap for *_, cap in plan]
+    bases = [index_base(c, *p, l, cap) for c, p, l, cap in plan]
+    rc, got = many_call(emu, [4] * len(plan), [c.frame for c, *_ in plan], params, lists, caps, bases, [False] * len(plan))
+    assert rc == 0
+    for i, (c, p, l, cap) in enumerate(plan):
+        want = want_select(c, *p, l, cap)
+        assert len(want) == min(cap, p[2] * total(l)) > 0, i
+        assert got[i][:2] == (0, len(want)), (i, got[i][:2])
+        assert got[i][2][: len(want)] == want, ("bytes differ", i)
+        assert got[i][2][len(want) :] == got[i][3][len(want) :], ("wrote beyond the request", i)

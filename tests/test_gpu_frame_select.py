@@ -361,3 +361,79 @@ def test_unpack_state_dict_index(gpu_lib, monkeypatch):
     with pytest.raises(ValueError):
         bzip3_amd.unpack_state_dict(packed, base=wrong, index=index)
     bzip3_amd.unpack_state_dict(packed, base=wrong, index=index, check_base=False)  # (other bytes, no error: the caller vouches)
+
+
+# ---- every request form in one call ---------------------------------------------------------------------------------------------
+def test_one_call_holds_every_request_form_on_the_gpu(gpu_lib, monkeypatch):
+    """test_frame_select_emu.test_one_call_holds_every_request_form on the device: five frames of element size 4 (a block of 65 KiB and a short
+    one), two of them with a base, in one bz3_hip_decompress_device_select_many call: a one-run range, the whole tensor, a two-run strided request, a
+    two-piece select request and a select request cut to w <= l_0, at windows of two chunks and of eight (all six chunks in one launch).
+    The oracle is unpack_tensor's result indexed with torch."""
+    import torch
+
+    bs, numel = 65 << 10, (65 << 10) // 4 + 1500
+    x, y, base = (_make("float32", numel, seed) for seed in (51, 52, 53))
+    px, py = bzip3_amd.pack_tensor(x, bs, planes=4), bzip3_amd.pack_tensor(y, bs, planes=4, base=base)
+    assert px.block_size == py.block_size == bs and py.delta
+    full = [bzip3_amd.unpack_tensor(px).view(torch.uint8).flatten(), bzip3_amd.unpack_tensor(py, base=base).view(torch.uint8).flatten()]
+    assert _raw(full[0]) == _raw(x) and _raw(full[1]) == _raw(y)
+    base_raw = base.view(torch.uint8).flatten()
+    T = 4 * numel
+    # (tensor, (offset, stride, count), pieces, the bytes asked for)
+    plan = [(1, (bs + 10, 0, 1), [(0, 777)], 777), (0, (0, 0, 1), [(0, T)], T), (0, (bs + 5, 1000, 2), [(3, 401)], 802), (1, (bs + 100, 2000, 2), [(0, 300), (650, 130)], 860),
+            (0, (bs + 9, 900, 3), [(4, 500), (600, 100)], 333)]
+
+    def phi(offset, stride, count, pieces, w):
+        per = torch.cat([torch.arange(a, a + l) for a, l in pieces])
+        return (torch.arange(count).unsqueeze(1) * stride + per.unsqueeze(0) + offset).flatten()[:w].to(x.device)
+
+    idx = [phi(*p, l, w) for _, p, l, w in plan]
+    n = len(plan)
+    frames = [(px, py)[t].frame for t, *_ in plan]
+    base_ts = [base_raw[i] if t else None for (t, *_), i in zip(plan, idx)]
+    vp = lambda ts: (C.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])  # noqa: E731
+    arrs = [_pieces_arg(l) for _, _, l, _ in plan]
+    for window in ("2", "8"):
+        monkeypatch.setenv("BZ3_HIP_FRAME_WINDOW", window)
+        outs = [torch.full((w + 8,), 0xA5, dtype=torch.uint8, device=x.device) for *_, w in plan]
+        out_sizes, rcs = (C.c_size_t * n)(*[w for *_, w in plan]), (C.c_int * n)(*([77] * n))  # (the last frame's *out_size cuts its request to w <= l_0)
+        torch.cuda.synchronize()
+        rc = gpu_lib.bz3_hip_decompress_device_select_many(n, (C.c_uint32 * n)(*([4] * n)), vp(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                                           (C.c_uint64 * (4 * n))(*[v for _, p, l, _ in plan for v in (*p, len(l))]),
+                                                           (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs]), vp(base_ts),
+                                                           (C.c_size_t * n)(*[0 if b is None else b.numel() for b in base_ts]), vp(outs), out_sizes, rcs)
+        assert rc == 0 and list(rcs) == [0] * n
+        for i, ((t, p, l, w), o) in enumerate(zip(plan, outs)):
+            assert out_sizes[i] == w and torch.equal(o[:w], full[t][idx[i]]), (window, i)
+            assert bool((o[w:] == 0xA5).all()), ("wrote beyond the request", window, i)
+
+
+def test_unpack_state_dict_takes_the_narrowest_call(gpu_lib, monkeypatch):
+    """rows= alone goes through bz3_hip_decompress_device_range_many, slices= + rows= through _strided_many, index= + slices= + rows= through
+    _select_many, one call each, on a dict of an (8, 1024) tensor packed against a base, a (4, 64, 256) tensor and a 0-d one; the error of a
+    truncated frame read by rows names the range call."""
+    import torch
+
+    sd = {"a": _make("float32", 8 * 1024, 61, (8, 1024)), "b": _make("float32", 4 * 64 * 256, 62, (4, 64, 256)), "step": _make("int32", 1, 63, ())}
+    base = {"a": _make("float32", 8 * 1024, 64, (8, 1024))}
+    packed = bzip3_amd.pack_state_dict(sd, 65 << 10, base=base)
+    assert packed["a"].delta and not packed["b"].delta
+    calls = []
+    for name in ("range", "strided", "select"):
+        entry = f"bz3_hip_decompress_device_{name}_many"
+        monkeypatch.setattr(gpu_lib, entry, (lambda real, name: lambda *a: calls.append(name) or real(*a))(getattr(gpu_lib, entry), name))
+    sel = lambda t, dim, idx: t.index_select(dim, torch.tensor(idx, dtype=torch.int64, device=t.device))  # noqa: E731
+    for kw, via, want in (({"rows": {"a": (2, 5)}}, "range", {"a": sd["a"][2:5], "b": sd["b"], "step": sd["step"]}),
+                          ({"slices": {"b": (1, 10, 20)}, "rows": {"a": (2, 5)}}, "strided", {"a": sd["a"][2:5], "b": sd["b"][:, 10:20], "step": sd["step"]}),
+                          ({"index": {"b": (2, [1, 5, 6, 200])}, "slices": {}, "rows": {"a": (0, 8)}}, "select", {"a": sd["a"], "b": sel(sd["b"], 2, [1, 5, 6, 200]), "step": sd["step"]}),
+                          ({"index": {"a": (1, [0, 7, 1023])}, "slices": {"b": (0, 1, 3)}, "rows": {}}, "select", {"a": sel(sd["a"], 1, [0, 7, 1023]), "b": sd["b"][1:3], "step": sd["step"]})):
+        del calls[:]
+        got = bzip3_amd.unpack_state_dict(packed, base=base, lib=gpu_lib, **kw)
+        assert calls == [via], (kw, calls)
+        assert list(got) == list(sd)
+        for k, w in want.items():
+            assert got[k].dtype == w.dtype and got[k].shape == w.shape and got[k].is_contiguous() and torch.equal(got[k], w), (via, k)
+    p = packed["b"]
+    short = dict(packed, b=bzip3_amd.PackedTensor(p.frame[: p.frame.numel() // 2], p.dtype, p.shape, p.planes, p.block_size, p.nbytes))
+    with pytest.raises(bzip3_amd.Bz3Error, match="bz3_hip_decompress_device_range_many"):
+        bzip3_amd.unpack_state_dict(short, base=base, rows={"b": (2, 4)}, lib=gpu_lib)
