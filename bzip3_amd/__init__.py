@@ -103,6 +103,10 @@ def _declare(L, strict=True):
         "bz3_hip_decompress_device_select_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)),
                                                             C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_select": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), C.c_uint64]),
+        "bz3_hip_update_device_range": (C.c_int, [u32, vp, sz, C.c_uint64, vp, sz, vp, vp, C.POINTER(sz)]),
+        "bz3_hip_update_device_range_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp),
+                                                       C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_patch": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -603,6 +607,65 @@ def decompress_tensor_range(frame, offset, nbytes, out=None, planes=1, base=None
         raise Bz3Error(e.code, "bz3_hip_decompress_device_range", e.outs[0]) from None
 
 
+def update_tensors_range(frames, offsets, datas, planes=1, bases=None, lib=None, block_sizes=None):
+    """New frames in which the bytes [offsets[i], offsets[i] + datas[i].numel()) of what frames[i] decodes to are replaced by datas[i], for many
+    frames in ONE call (bz3_hip_update_device_range_many) and one synchronisation: only the chunks that hold bytes of a range are coded again, of
+    those only the (at most two per frame) that the range cuts are decoded first, and every other chunk is copied as it is, undecoded (DESIGN.md,
+    "Range update").  Result i is byte for byte the frame compress_tensor gives for the updated bytes.  frames and datas: contiguous uint8
+    tensors on one GPU; a range must lie inside what its frame decodes to (an update never grows a tensor; Bz3Error with BZ3_ERR_DATA_TOO_BIG),
+    and an empty datas[i] gives a copy of the frame.  `planes` as in decompress_tensors.  `bases[i]`: None, or for a frame made against a base the
+    base's bytes OF THE RANGE, as many as datas[i].  `block_sizes`: the block sizes of the frames where the caller knows them
+    (PackedTensor.block_size); without them the 13 header bytes of all frames are read from the device once, which is a second synchronisation.
+    They only size the outputs, which are views of one allocation of frames[i].numel() + (datas[i].numel() // block size + 2) *
+    bz3_bound(block size) bytes each (.clone() one to drop the rest).  The inputs are never written.  Raises Bz3Error with .index / .codes / .outs
+    as compress_tensors does; a frame that fails has no output.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    offs = [int(o) for o in offsets]
+    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
+    if len(offs) != n or len(datas) != n:
+        raise ValueError(f"update_tensors_range: {n} frames, {len(offs)} offsets and {len(datas)} data tensors")
+    if any(o < 0 for o in offs):
+        raise ValueError("update_tensors_range: offsets must not be negative")
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
+    dev = _same_device(frames + datas, "update_tensors_range")
+    L = lib or load()
+    if block_sizes is None:
+        heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
+        block_sizes = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
+    bss = [min(max(int(b), _KiB65), _MiB511) for b in block_sizes]  # (a header that lies: the call refuses it, or finds the output too small)
+    if len(bss) != n:
+        raise ValueError(f"update_tensors_range: {n} frames and {len(bss)} block sizes")
+    caps = [f.numel() + (d.numel() // bs + 2) * L.bz3_bound(bs) for f, d, bs in zip(frames, datas, bss)]
+    outs = _carve(sum(caps), caps, dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    torch.cuda.synchronize(dev)
+    rc = L.bz3_hip_update_device_range_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), (C.c_uint64 * n)(*offs), _ptrs(datas),
+                                            (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(codes[idx], "bz3_hip_update_device_range_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def update_tensor_range(frame, offset, data, planes=1, base=None, lib=None, block_size=None):
+    """The frame in which the bytes [offset, offset + data.numel()) of what `frame` decodes to are replaced by `data`
+    (bz3_hip_update_device_range): update_tensors_range for one frame."""
+    try:
+        return update_tensors_range([frame], [offset], [data], planes=planes, bases=None if base is None else [base], lib=lib,
+                                    block_sizes=None if block_size is None else [block_size])[0]
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_update_device_range") from None
+
+
 def decompress_tensors_strided(frames, offsets, runs, strides, counts, outs=None, planes=1, bases=None, lib=None):
     """A strided byte set of what every frame decodes to, for many frames in ONE call (bz3_hip_decompress_device_strided_many): of frame i
     the counts[i] runs of runs[i] bytes whose starts lie strides[i] bytes apart from offsets[i] on, one after the other -- a slice along
@@ -989,6 +1052,48 @@ def unpack_tensor_rows(p, start, stop, out=None, base=None, lib=None):
     return _unpack_rows_many([p], [(start, stop)], None if out is None else [out], lib, [base])[0]
 
 
+def _update_rows_many(ps, rows, bases, lib):
+    """rows[i] = (start, values): the PackedTensors with rows [start, start + len(values)) of dimension 0 replaced, through ONE
+    bz3_hip_update_device_range_many call.  bases[i]: the same rows of the base.  Every argument is checked before any GPU work."""
+    import torch
+
+    offs, raws, braws = [], [], []
+    for i, (p, (start, values), b) in enumerate(zip(ps, rows, _bases_arg(bases, len(ps)))):
+        rb = _row_bytes(p, f"tensor {i}")
+        start = int(start)
+        if not isinstance(values, torch.Tensor) or values.device.type != "cuda":
+            raise TypeError(f"update: the rows of tensor {i} must be a torch tensor on a GPU")
+        if values.dtype != p.dtype or values.dim() != len(p.shape) or tuple(values.shape[1:]) != tuple(p.shape[1:]):
+            raise TypeError(f"update: the rows of tensor {i} must be {p.dtype} of shape (rows, {', '.join(map(str, p.shape[1:]))})")
+        if not 0 <= start <= start + values.shape[0] <= p.shape[0]:
+            raise ValueError(f"update: rows ({start}, {start + values.shape[0]}) of a tensor of {p.shape[0]} rows")
+        if p.delta and b is None:
+            raise ValueError(f"update: tensor {i} was packed against a base, whose rows are needed to code the new ones")
+        if not p.delta:
+            b = None
+        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != tuple(values.shape):
+            raise ValueError(f"update: base {i} must hold the same rows of the base: {p.dtype} {tuple(values.shape)}")
+        raw = _as_bytes(values, f"rows {i}")
+        offs.append(start * rb)
+        raws.append(raw)
+        braws.append(_base_bytes(b, raw.numel(), p.frame.device, f"base {i}"))
+    frames = update_tensors_range([p.frame for p in ps], offs, raws, planes=[p.planes for p in ps], bases=braws, lib=lib, block_sizes=[p.block_size for p in ps])
+    return [PackedTensor(f, p.dtype, p.shape, p.planes, p.block_size, p.nbytes, p.delta, p.base_crc, None) for f, p in zip(frames, ps)]
+
+
+def update_tensor_rows(p, start, values, base=None, lib=None):
+    """A new PackedTensor that holds p's tensor with rows [start, start + len(values)) of dimension 0 replaced by `values`, on the frame's GPU,
+    without the tensor ever being materialised: only the chunks of the frame that hold bytes of those rows are coded again
+    (bz3_hip_update_device_range), the others are copied.  Its frame is byte for byte the one pack_tensor gives for the updated tensor at
+    p.block_size and p.planes.  `values`: a GPU tensor of p's dtype and trailing shape (TypeError otherwise); the rows must lie inside
+    p.shape[0] (ValueError; a 0-d tensor has no rows): an update never grows a tensor.  All of that is checked before any GPU work.  A tensor
+    packed against a base needs `base`: THE SAME ROWS of the base, of values' shape (ValueError without them); as with unpack_tensor_rows,
+    base_crc covers the whole base and cannot vouch for a slice of it.  planes, block_size, dtype, shape, nbytes, delta and base_crc are
+    carried over; `crc` of the result is None, because the checksum of the whole tensor cannot be had without the bytes of the chunks that were
+    only copied (verify=True skips such a tensor; pack it anew, or unpack and checksum it, where a checksum is wanted).  `p` is unchanged."""
+    return _update_rows_many([p], [(start, values)], [base], lib)[0]
+
+
 def _slice_of(p, sl, what):
     """(shape, (offset, run, stride, count)) of the slice sl = (dim, start, stop) of a PackedTensor; None is the whole tensor."""
     if not isinstance(p, PackedTensor):
@@ -1305,6 +1410,21 @@ def unpack_state_dict(packed, lib=None, base=None, inplace=False, check_base=Tru
         else:
             outs.append(b)
     return dict(zip(names, _unpack_many(ps, outs, lib, bases, check_base, verify, names)))
+
+
+def update_state_dict_rows(packed, rows, base=None, lib=None):
+    """update_tensor_rows for several tensors of a packed state dict in ONE bz3_hip_update_device_range_many call: `rows` is
+    {name: (start, values)}, and the result a new dict in which those names have new PackedTensors (crc None) and every other name the
+    PackedTensor of `packed` itself.  `base`: {name: the same rows of that tensor's base}, needed for the named tensors that were packed
+    against one.  A name that is not in `packed`: ValueError.  Everything is checked before any GPU work; `packed` is unchanged."""
+    unknown = [k for k in rows if k not in packed]
+    if unknown:
+        raise ValueError(f"update_state_dict_rows: rows for {unknown[0]!r}, which is not in the dict")
+    names = list(rows)
+    out = dict(packed)
+    if names:
+        out.update(zip(names, _update_rows_many([packed[k] for k in names], [rows[k] for k in names], [None if base is None else base.get(k) for k in names], lib)))
+    return out
 
 
 # ---- chains of checkpoints ----------------------------------------------------------------------------------------------------

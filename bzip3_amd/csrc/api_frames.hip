@@ -119,10 +119,12 @@ struct GatherList {
     };
     std::vector<Entry> v;
     int level = SEG_DELTA;
+    bool patched = false;  // the list holds a clipped split: the launch is k_patch_segments, and holds no partial merge
     size_t size() const { return v.size(); }
     void clear() {
         v.clear();
         level = SEG_DELTA;
+        patched = false;
     }
     // A segment as it is: a copy, a split, a merge, with or without a base.
     void plain(const CopySeg & sg) { v.push_back({sg, {}}); }
@@ -132,6 +134,15 @@ struct GatherList {
         if (k <= 1 || a == b || (a == 0 && b == s)) return plain({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
         v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base}, {a, b}});
         level = std::max<int>(level, SEG_CLIP);
+    }
+    // The write mirror of range(): the chunk bytes [a, b) of the chunk of s bytes that `slot` holds in split form get the new values src[0, b - a)
+    // (less base[0, b - a), or 0), which address the clip's first byte.  A whole chunk and every k = 1 clip are ordinary segments, the rest clipped
+    // splits (planes.hpp, "Clipped split").
+    void patch(u64 src, u64 base, u64 slot, u64 s, u64 k, u64 a, u64 b) {
+        if (k <= 1 || a == b || (a == 0 && b == s)) return plain({src, slot + (k <= 1 ? a : 0), b - a, k, base});
+        v.push_back({{src, slot, s, k | PLANES_CLIP, base}, {a, b}});
+        level = std::max<int>(level, SEG_CLIP);
+        patched = true;
     }
     // The same for a chunk of which a strided range wants the nbytes bytes c(u) (planes.hpp, "Strided merge"; first in [1, run], stride >= run):
     // a share within one run (nbytes <= first) is the clipped or whole segment above, anything else a strided merge.
@@ -154,7 +165,7 @@ struct GatherList {
 };
 
 // Copies the segments of g (absolute device addresses) in one launch on stream s; d_tab holds table_bytes(g.size(), g.level) bytes.  The kernel
-// is the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
+// is k_patch_segments for a list with a clipped split, else the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
 // k_copy_segments (planes.hpp).  The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
 void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
     const size_t n = g.size(), bytes = table_bytes(n, g.level), seg_bytes = align16(n * sizeof(CopySeg));
@@ -184,6 +195,7 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
         planes |= k > 1;
         delta |= sg.base != 0;
     }
+    if (g.patched && g.level != SEG_CLIP) throw std::logic_error("clipped splits and partial merges in one launch");
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
@@ -194,7 +206,8 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
     const u64 * d_clips = (const u64 *)(d_tab + clip_off);
     const u64 * d_periods = (const u64 *)(d_tab + period_off);
     const u64 * d_selects = (const u64 *)(d_tab + select_off);
-    if (g.level == SEG_SELECT) launch(k_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods, d_selects);
+    if (g.patched) launch(k_patch_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
+    else if (g.level == SEG_SELECT) launch(k_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods, d_selects);
     else if (g.level == SEG_STRIDED) launch(k_strided_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods);
     else if (g.level == SEG_CLIP) launch(k_range_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
     else launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, grid, block, 0, s, d_segs, d_starts, (u32)n);
@@ -210,13 +223,14 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // 8-byte chunk header per block of a window at most), the copy tables of a window (two segments per block, one per frame
 // header; with room for their clips and periods), the walk's arguments, records and tails.  A call that walks with piece tables
 // (piece_bytes > 0 of them, uploaded once per call) has them behind the tails and room for the piece-list parameters in its copy tables;
-// every other call has the layout and the size it had.
+// every other call has the layout and the size it had.  An update (update_frames) packs up to two runs of verbatim bytes per frame beside the two
+// segments of every block, the frame header travelling in the first run: `runs` = 2 segments per frame instead of 1.
 struct MetaLayout {
-    size_t n = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, pieces = 0, bytes = 0;
+    size_t n = 0, segs = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, pieces = 0, bytes = 0;
     MetaLayout() = default;
-    explicit MetaLayout(size_t frames, size_t piece_bytes = 0) : n(frames) {
+    explicit MetaLayout(size_t frames, size_t piece_bytes = 0, size_t runs = 1) : n(frames), segs(2 * FRAME_WINDOW_MAX + runs * frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
-        args = tab + align256(table_bytes(2 * FRAME_WINDOW_MAX + n, piece_bytes ? SEG_SELECT : SEG_STRIDED));
+        args = tab + align256(table_bytes(segs, piece_bytes ? SEG_SELECT : SEG_STRIDED));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
         pieces = tails + align256(n * sizeof(WalkTail));
@@ -253,10 +267,10 @@ struct DeviceFrames {
         if (meta) (void)hipFree(meta);
         if (own_stream && s) (void)hipStreamDestroy(s);
     }
-    bool open(int dev, size_t n, size_t piece_bytes = 0) {  // the device, a stream and the small buffer
+    bool open(int dev, size_t n, size_t piece_bytes = 0, size_t runs = 1) {  // the device, a stream and the small buffer
         if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
         device = dev;
-        lay = MetaLayout(n, piece_bytes);
+        lay = MetaLayout(n, piece_bytes, runs);
         HIP_CHECK(hipSetDevice(dev));
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         own_stream = true;
@@ -303,7 +317,7 @@ struct DeviceFrames {
     }
     u8 * slot(size_t k) const { return slab + k * stride; }
     void copy() {  // the segments collected in `gather`, one launch, complete on return
-        if (gather.size() > 2 * FRAME_WINDOW_MAX + lay.n) throw std::length_error("copy table overflow");
+        if (gather.size() > lay.segs) throw std::length_error("copy table overflow");
         copy_segments(gather, staging, meta + lay.tab, s);
         HIP_CHECK(hipStreamSynchronize(s));
         gather.clear();
@@ -888,6 +902,236 @@ void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t *
     }
 }
 
+// ---- update: n frames whose buffers passed the pointer checks, on device dev ------------------------------------------------------
+// Frame i's decoded bytes [offsets[i], offsets[i] + ws[i]) get the values datas[i][0, ws[i]) (less bases[i][0, ws[i]) where there is a base) and
+// the new frame goes to outs[i] (bz3_hip.h, "Range update").  Only the chunks that share a byte with the range (the touched ones) are coded again;
+// of those only the ones the range cuts are decoded first, the others are rebuilt from the new bytes alone; everything else of the frame is copied.
+//   1. One walk reads every frame header, then plain walks read every chunk header of every frame (rounds of WALK_RECORDS chunks over all
+//      frames).  They give T, the frame's end, `need`, and the records of the touched chunks, which are all that is kept.
+//   2. The touched chunks of all frames form one list in frame order and go through windows of as many slots as the call has states (sized from
+//      the list, never from n_blocks).  Before anything is written to an `out`, every cut chunk of the call is decoded whole.  Where the list
+//      fits one window (the usual row update) those decodes already sit in their chunks' slots; a longer list decodes its cut chunks once to
+//      check them, a window at a time, and again in the window that codes them (at most two chunks per frame).
+//   3. Per window: (the cut chunks' coded bytes into their slots, run_decode on that subset: the slot then holds the chunk in split form;) ONE
+//      patch launch -- a whole-block split from `data` for a covered chunk, a clipped split for a cut one --; run_encode on the window's slots;
+//      one pack launch: the new chunk headers from the staged buffer, the coded slots, and the verbatim runs.  The bytes of a frame before its
+//      first touched chunk (the frame header among them) are contiguous in `in` and in `out`, and so are those behind its last one: two plain
+//      segments per frame.  (A frame may hold empty chunks between touched ones; each such gap is a run of its own, and the launch is split
+//      where its table is full.)
+// A frame that fails in 1 or 2 has its code, size 0 and an untouched `out`; one that fails in 3 (not expected) its code and size 0.
+void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u64 * offsets, const u8 * const * datas,
+                   const size_t * ws, const u8 * const * bases, u8 * const * outs, size_t * out_sizes, int * rcs) {
+    struct Frame {
+        u64 lo = 0, hi = 0;     // the range; hi < lo: offset + w does not fit 64 bits
+        u64 need = 13, end = 0;  // the capacity the frame needs; the offset behind its last chunk
+        size_t cap = 0, pos = 0;
+        u64 in_next = 0;         // the frame's bytes before it are in `out`
+        u32 count = 0, packed = 0;  // its touched chunks, and those of them that are packed
+    };
+    struct Touched {
+        s32 frame;
+        WalkChunk rec;
+        u64 a, b;  // the chunk's bytes [a, b) are replaced
+        bool cut() const { return a != 0 || b != (u64)rec.orig; }
+    };
+    std::vector<Frame> fr((size_t)n);
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    std::vector<Touched> touch;
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        fr[i].cap = out_sizes[i];
+        out_sizes[i] = 0;
+        fr[i].lo = offsets ? offsets[i] : 0;
+        fr[i].hi = fr[i].lo + (u64)ws[i];
+        if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
+        else live[i] = any = 1;
+    }
+    if (!any) return;
+    auto fail = [&](s32 i, int rc) {
+        rcs[i] = rc;
+        out_sizes[i] = 0;
+        live[i] = 0;
+    };
+    DeviceFrames f;
+    u32 bs_max = 0;
+    try {
+        if (!f.open(dev, (size_t)n, 0, 2)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
+        std::vector<WalkArg> args;
+        std::vector<s32> who;
+        std::vector<WalkChunk> rec;
+        std::vector<WalkTail> tails;
+        for (;;) {  // every chunk header of every live frame
+            args.clear();
+            who.clear();
+            u32 budget = (u32)WALK_RECORDS, base = 0;
+            for (s32 i = 0; i < n && budget; i++) {
+                if (!live[i] || pos[i].done == pos[i].n_blocks) continue;
+                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+                args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, lim, base));
+                who.push_back(i);
+                base += lim;
+                budget -= lim;
+            }
+            if (args.empty()) break;
+            f.walk(args, rec, tails);
+            for (size_t q = 0; q < who.size(); q++) {
+                const s32 i = who[q];
+                Frame & x = fr[i];
+                for (u32 r = 0; r < tails[q].count; r++) {
+                    const WalkChunk & c = rec[args[q].rec_base + r];
+                    const u64 p = c.out_off, o = (u64)c.orig;
+                    const bool touched = x.lo < x.hi && o > 0 && p < x.hi && p + o > x.lo;
+                    x.need += 8 + (touched ? (u64)bz3_bound((size_t)o) : (u64)c.size);
+                    if (!touched) continue;
+                    touch.push_back({i, c, std::max(x.lo, p) - p, std::min(x.hi, p + o) - p});
+                    x.count++;
+                }
+                pos[i].take(tails[q]);
+                if (tails[q].err != BZ3_OK) fail(i, tails[q].err);
+            }
+        }
+        for (s32 i = 0; i < n; i++) {
+            if (!live[i]) continue;
+            fr[i].end = pos[i].off;
+            if (fr[i].hi < fr[i].lo || fr[i].hi > pos[i].planned || fr[i].cap < fr[i].need) fail(i, BZ3_ERR_DATA_TOO_BIG);
+        }
+        touch.erase(std::remove_if(touch.begin(), touch.end(), [&](const Touched & t) { return !live[t.frame]; }), touch.end());
+        for (const Touched & t : touch) bs_max = std::max(bs_max, pos[t.frame].block_size);
+        if (bs_max && !f.init(bs_max, std::min(touch.size(), FRAME_WINDOW_MAX))) throw std::runtime_error("no states");
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) fail(i, BZ3_ERR_INIT);
+        return;
+    }
+    try {
+        DeviceGuard g(dev);
+        const size_t total = touch.size(), W = std::max<size_t>(f.states.size(), 1);
+        const bool one_window = total <= W;
+        std::vector<bz3_state *> sts;
+        std::vector<void *> slots;
+        std::vector<s32> sizes, orig, which;
+        std::vector<size_t> caps;
+        std::vector<u8> hdrs, hdr;
+        // Decodes the chunks jobs[j] = (index into touch, slot) in place in their slots: one copy launch and one run_decode.  A chunk that fails
+        // ends its frame.
+        auto decode = [&](const std::vector<std::pair<size_t, size_t>> & jobs) {
+            if (jobs.empty()) return;
+            sts.clear(), slots.clear(), sizes.clear(), orig.clear(), caps.clear(), hdrs.clear();
+            for (const auto & [t, k] : jobs) {
+                const Touched & c = touch[t];
+                f.states[k]->block_size = (s32)pos[c.frame].block_size;  // every check of the block is made against its own frame's block size
+                f.states[k]->last_error = BZ3_OK;
+                sts.push_back(f.states[k]);
+                slots.push_back(f.slot(k));
+                sizes.push_back(c.rec.size);
+                orig.push_back(c.rec.orig);
+                caps.push_back(bz3_bound(pos[c.frame].block_size));
+                hdrs.insert(hdrs.end(), c.rec.hdr, c.rec.hdr + 17);
+                f.gather.plain({(u64)(ins[c.frame] + c.rec.in_off + 8), (u64)f.slot(k), (u64)c.rec.size});
+                if (f.gather.size() == f.lay.segs) f.copy();
+            }
+            f.copy();
+            run_decode(sts.data(), slots.data(), caps.data(), sizes.data(), orig.data(), hdrs.data(), (s32)jobs.size(), false);
+            for (size_t j = 0; j < jobs.size(); j++)
+                if (live[touch[jobs[j].first].frame] && bz3_last_error(sts[j]) != BZ3_OK) fail(touch[jobs[j].first].frame, sts[j]->last_error);
+        };
+        std::vector<std::pair<size_t, size_t>> jobs;
+        for (size_t t = 0; t < total; t++) {  // every cut chunk of the call, before any write to an `out`
+            if (touch[t].cut()) jobs.push_back({t, one_window ? t : jobs.size()});
+            if (jobs.size() == W || t + 1 == total) {
+                decode(jobs);
+                jobs.clear();
+            }
+        }
+        auto flush = [&]() {  // the pack launch (a part of it, where its table is full)
+            f.stage_headers(hdr);
+            f.copy();
+            hdr.clear();
+        };
+        auto run = [&](s32 i, u64 from, u64 to) {  // the frame's bytes [from, to) verbatim, behind what `out` holds
+            if (to > from) {
+                if (f.gather.size() + 3 > f.lay.segs) flush();
+                f.gather.plain({(u64)(ins[i] + from), (u64)(outs[i] + fr[i].pos), to - from});
+            }
+            fr[i].pos += (size_t)(to - from);
+            fr[i].in_next = to;
+        };
+        for (s32 i = 0; i < n; i++)  // a frame without a touched chunk is one run
+            if (live[i] && fr[i].count == 0) {
+                run(i, 0, fr[i].end);
+                out_sizes[i] = fr[i].pos;
+            }
+        for (size_t w0 = 0; w0 < total; w0 += W) {
+            const size_t cnt = std::min(W, total - w0);
+            if (!one_window) {
+                jobs.clear();
+                for (size_t k = 0; k < cnt; k++)
+                    if (touch[w0 + k].cut() && live[touch[w0 + k].frame]) jobs.push_back({w0 + k, k});
+                if (!f.gather.v.empty()) flush();  // (the runs collected so far: the decode's scatter is a launch of its own)
+                decode(jobs);
+            }
+            // patch: the new bytes into the slots, split
+            if (!f.gather.v.empty()) flush();
+            sts.clear(), slots.clear(), sizes.clear(), which.clear();
+            for (size_t k = 0; k < cnt; k++) {
+                const Touched & c = touch[w0 + k];
+                const s32 i = c.frame;
+                if (!live[i]) continue;
+                const u64 rel = c.rec.out_off + c.a - fr[i].lo, es = elem_sizes ? (u64)elem_sizes[i] : 1;  // the clip's first byte in data and base
+                f.gather.patch((u64)(datas[i] + rel), bases && bases[i] ? (u64)(bases[i] + rel) : 0, (u64)f.slot(k), (u64)c.rec.orig, es, c.a, c.b);
+                f.states[k]->block_size = (s32)pos[i].block_size;
+                f.states[k]->last_error = BZ3_OK;
+                sts.push_back(f.states[k]);
+                slots.push_back(f.slot(k));
+                sizes.push_back(c.rec.orig);
+                which.push_back((s32)k);
+            }
+            if (sts.empty()) continue;
+            f.copy();
+            run_encode(sts.data(), slots.data(), sizes.data(), (s32)sts.size(), false);
+            // pack
+            for (size_t j = 0; j < which.size(); j++) {
+                const Touched & c = touch[w0 + (size_t)which[j]];
+                const s32 i = c.frame;
+                Frame & x = fr[i];
+                if (!live[i]) continue;  // an earlier block of its frame failed in this window
+                const s32 osz = sizes[j];
+                if (bz3_last_error(sts[j]) != BZ3_OK || osz < 0 || (size_t)osz > bz3_bound((size_t)c.rec.orig)) {
+                    fail(i, bz3_last_error(sts[j]) != BZ3_OK ? sts[j]->last_error : BZ3_ERR_DATA_TOO_BIG);
+                    continue;
+                }
+                run(i, x.in_next, c.rec.in_off);  // the frame header and the chunks before its first touched one, or the empty chunks in a gap
+                if (f.gather.size() + 3 > f.lay.segs || hdr.size() + 8 > f.lay.tab - f.lay.hdr) flush();
+                const size_t h = hdr.size();
+                hdr.resize(h + 8);
+                wr_le32(hdr.data() + h, (u32)osz);
+                wr_le32(hdr.data() + h + 4, (u32)c.rec.orig);
+                f.gather.plain({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
+                f.gather.plain({(u64)slots[j], (u64)(outs[i] + x.pos + 8), (u64)osz});
+                x.pos += (size_t)osz + 8;
+                x.in_next = c.rec.in_off + 8 + (u64)c.rec.size;
+                if (++x.packed == x.count) {
+                    run(i, x.in_next, x.end);
+                    out_sizes[i] = x.pos;
+                }
+            }
+            flush();
+        }
+        if (!f.gather.v.empty()) flush();
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        for (s32 i = 0; i < n; i++)
+            if (live[i] && (fr[i].packed < fr[i].count || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i] && (fr[i].packed < fr[i].count || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+    }
+}
+
 // ---- the entry points' argument checks ------------------------------------------------------------------------------------
 // The GPU of a call: every non-empty buffer (a[i] with a_sizes[i] > 0, likewise b) must be device memory of the GPU the first
 // one lives on.  -1: no buffer is non-empty; -2: one is not.
@@ -1136,6 +1380,38 @@ BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * i
     return bz3_hip_decompress_device_range_many(1, &elem_size, ins, &in_size, &offset, bases, &base_size, outs, out_size, &rc);
 }
 
+// Range update (bz3_hip.h).  Whole-call checks as in the range calls; then, before any write, the overlaps of a frame's out[0, cap) with its input,
+// its data and its base.
+BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], const uint64_t offsets[],
+                                               const void * const datas[], const size_t ws[], const void * const bases[], void * const outs[], size_t out_sizes[],
+                                               int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !ins || !in_sizes || !datas || !ws || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev < 0) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (every frame is empty and has no room: nothing to walk, nowhere to write)
+    for (s32 i = 0; i < n; i++) {
+        const void * base = bases ? bases[i] : nullptr;
+        if (ws[i] && (device_of(datas[i]) != dev || (base && device_of(base) != dev))) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+        if (ranges_overlap(outs[i], out_sizes[i], ins[i], in_sizes[i]) || ranges_overlap(outs[i], out_sizes[i], datas[i], ws[i]) ||
+            (base && ranges_overlap(outs[i], out_sizes[i], base, ws[i])))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    update_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, offsets, (const u8 * const *)datas, ws, (const u8 * const *)bases, (u8 * const *)outs, out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_update_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * data, size_t w, const void * base, void * out,
+                                          size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * datas[1] = {data};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    int rc = BZ3_OK;
+    return bz3_hip_update_device_range_many(1, &elem_size, ins, &in_size, &offset, datas, &w, bases, outs, out_size, &rc);
+}
+
 BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
                                                     size_t out_sizes[], int rcs[]) {
     return bz3_hip_decompress_device_delta_many(n, elem_sizes, ins, in_sizes, nullptr, nullptr, outs, out_sizes, rcs);
@@ -1241,6 +1517,25 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
         for (s32 i = 0; i < n; i++) {
             const uint64_t * q = segs + (size_t)7 * i;
             g.range((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], debug_base(base, q[1]));
+        }
+    });
+}
+
+// n septuples (src_off, base_off, dst_off, len, elem_size, a, b): the slot of `len` bytes at dst_off holds a chunk in split form, of which the bytes
+// [a, b) get the values at src_off (less the bytes at base_off unless it is UINT64_MAX), one launch through the segments an update call's patch
+// makes of them.
+BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)7 * i;
+        if (!planes_elem_size_ok(q[4]) || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
+        any_base |= q[1] != UINT64_MAX;
+    }
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)7 * i;
+            g.patch((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6]);
         }
     });
 }

@@ -56,6 +56,25 @@
 // of the base belongs to other tiles and lands in LDS outside [s0 - origin, s1 - origin); a tail byte is read and written by one
 // thread.  dst and base share the clip's coordinates, so dst == base pairs every byte with itself.
 //
+// Clipped split (CopySeg::mode & PLANES_CLIP without PLANES_INVERSE; bz3_hip_update_device_range, api_frames.hip).  The write mirror of the
+// clipped merge: dst is a slot that holds split_k of a decoded chunk of s bytes (m = s / k, the tail in place), and of the chunk only the
+// bytes [a, b) get new values, src[0, b - a) (less base[0, b - a) where there is a base): src and base address the clip's first byte.  The
+// segment stores dst[q m + e] = src[e k + q - a] for every (e, q) with a <= e k + q < b, the tail bytes c in [max(a, m k), b) to dst[c], and
+// NO OTHER BYTE OF THE SLOT: the rest is the old chunk, which the encode that follows reads.  clip_split_tile is split_tile with these changes:
+//   * only the tiles that hold an element byte of [a, b) are launched (clip_first_tile, clip_tiles), the first of them stores the clip's
+//     part of the tail;
+//   * a lane whose 16 elements lie inside [a, b) loads, subtracts and transposes them as before; a lane whose elements straddle a or b moves
+//     the bytes inside the clip one by one (at most two lanes of a segment), a lane outside it loads nothing.  The interleaved side is the
+//     caller's here, so this holds with or without a base: every granule loaded from src or base holds a byte of src[0, b - a) or
+//     base[0, b - a), and nothing around the caller's row buffer is relied on;
+//   * plane q holds the clip's elements [ceil((a - q) / k), ceil((min(b, m k) - q) / k)), ranges that differ by at most one element between the
+//     planes.  A tile's store range in plane q is its usual one, cut at the 16-byte boundaries of dst + q m, then clamped to that element
+//     range; the first tile launched starts at the clamp whatever its own first granule is (the tile before it, which would own those bytes,
+//     is not launched; they are elements of this tile).  Full granules inside the range are 16-byte stores and the partial ones at the clamp
+//     byte stores, never a read-modify-write of a granule: the neighbouring bytes are the old chunk's, or another tile's.
+// k = 1 is a plain copy, or the delta1_tile copy with a base, at dst + a, and a == 0 && b == s the ordinary split segment (GatherList::patch,
+// api_frames.hip).  No scratch; the LDS of the other segment kernels.
+//
 // Strided merge (CopySeg::mode & PLANES_STRIDED; bz3_hip_decompress_device_strided, api_frames.hip).  A strided range wants of a chunk a
 // periodic set of its bytes: chunk byte c0, the `first` bytes from it on (the rest of the run c0 lies in), then runs of `run` bytes
 // whose starts lie `stride` bytes apart, nbytes in all.  In the output they are CONTIGUOUS, dst[0, nbytes), so the chunk is one segment
@@ -109,7 +128,7 @@ constexpr u32 PLANES_LOAD_ELEMS = COPY_THREADS * 16;        // elements a workgr
 constexpr u32 PLANE_STRIDE = PLANES_LOAD_ELEMS + 16;        // LDS bytes per plane (split): phase 2 reads up to 20 bytes from offset < 4080
 constexpr u32 PLANES_LDS_BYTES = 8 * PLANE_STRIDE;          // >= 8 * PLANES_LOAD_ELEMS + 16, the merge layout
 constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = elem_size | PLANES_INVERSE for merge
-constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments and the kernels above it)
+constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments and the kernels above it); without PLANES_INVERSE a split that replaces only them (k_patch_segments)
 constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments and k_select_segments)
 constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
 constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone)
@@ -487,6 +506,55 @@ __device__ __forceinline__ void clip_merge_tile(const u8 * src, const u8 * base,
     }
 }
 
+// ---- clipped split ------------------------------------------------------------------------------------------------------------------
+// Tile clip_first_tile + rel of a split INTO the `len` bytes at `dst`, which hold split_k of a chunk: of the chunk's bytes only [ca, cb) are
+// replaced, by src[0, cb - ca); with D, less base[0, cb - ca).  See the head of this file.
+template <int K, bool D>
+__device__ __forceinline__ void clip_split_tile(const u8 * src, const u8 * base, u8 * dst, u64 len, u64 ca, u64 cb, u64 rel, u8 * lds) {
+    const u64 m = len / K, ea = (clip_first_tile(len, K, ca) + rel) * PLANES_TILE_ELEMS;
+    const u64 e = ea + 16 * (u64)threadIdx.x;
+    const u64 bm = cb < m * K ? cb : m * K;
+    const u64 l0 = e * K, l1 = (e + 16) * K;  // the chunk bytes of the lane's elements
+    if (l0 < bm && l1 > ca) {
+        if (l0 >= ca && l1 <= bm) {  // (l1 <= bm <= m K: the lane's 16 elements are whole elements of the chunk)
+            u32 w[4 * K], p[K][4];
+            load_elems16<K>((u64)src + (l0 - ca), w);
+            if (D) {
+                u32 b[4 * K];
+                load_elems16<K>((u64)base + (l0 - ca), b);
+#pragma unroll
+                for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
+            }
+            deinterleave<K>(w, p);
+#pragma unroll
+            for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
+        } else {
+            for (u64 i = e; i < m && i < e + 16; i++)
+                for (int q = 0; q < K; q++) {
+                    const u64 c = i * K + q;
+                    if (c >= ca && c < cb) lds[q * PLANE_STRIDE + (i - ea)] = D ? (u8)(src[c - ca] - base[c - ca]) : src[c - ca];
+                }
+        }
+    }
+    __syncthreads();
+    if (bm > ca) {
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            // plane q holds the clip's elements [e0, e1): those e with ca <= e K + q < bm
+            const u64 e0 = ca > (u64)q ? (ca - q + K - 1) / K : 0, e1 = bm > (u64)q ? (bm - q + K - 1) / K : 0;
+            const u64 p0 = (u64)dst + q * m, pend = p0 + m;
+            const u64 s0 = rel == 0 ? p0 + e0 : align16_up_to(p0 + ea, pend);  // (the first tile launched starts the clip, wherever its own granules start)
+            const u64 t1 = align16_up_to(p0 + ea + PLANES_TILE_ELEMS, pend);
+            const u64 s1 = t1 < p0 + e1 ? t1 : p0 + e1;
+            if (s0 < s1) store_from_lds<1>(lds + q * PLANE_STRIDE, p0 + ea, s0, s1);
+        }
+    }
+    if (rel == 0 && threadIdx.x < len - m * K) {
+        const u64 t = m * K + threadIdx.x;
+        if (t >= ca && t < cb) dst[t] = D ? (u8)(src[t - ca] - base[t - ca]) : src[t - ca];
+    }
+}
+
 // ---- strided merge ------------------------------------------------------------------------------------------------------------------
 // Workgroups of a strided merge of nbytes destination bytes: one per PLANES_TILE_ELEMS k of them.
 __host__ __device__ inline u64 strided_tiles(u64 nbytes, u64 k) { return (nbytes + k * PLANES_TILE_ELEMS - 1) / (k * PLANES_TILE_ELEMS); }
@@ -650,6 +718,21 @@ __device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 
 // The kinds of segment a launch may hold, in the order they were added: every kind's kernel handles the kinds below it as well.
 enum SegLevel : int { SEG_DELTA = 0, SEG_CLIP = 1, SEG_STRIDED = 2, SEG_SELECT = 3 };
 
+// One tile of a segment that is moved whole: a copy, a split or a merge, with or without a base.
+__device__ __forceinline__ void whole_segment_tile(const CopySeg & sg, u32 tile, u8 * lds) {
+    if (!sg.base) {
+        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, lds);
+        else copy_segment_tile(sg, tile);
+    } else if ((sg.mode & 0xff) > 1) {
+        planes_tile<true>(sg, tile, lds);
+    } else {
+        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
+        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+        if (sg.mode & PLANES_INVERSE) delta1_tile<true>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+        else delta1_tile<false>((const u8 *)sg.src, (const u8 *)sg.base, (u8 *)sg.dst, sg.len, g_first, g_last);
+    }
+}
+
 // One workgroup of a launch whose highest segment kind is LEVEL: the tile of its segment, by the segment's mode.  clips[2 i], clips[2 i + 1]
 // are segment i's [a, b) (read for segments with PLANES_CLIP alone, LEVEL >= SEG_CLIP), periods[5 i .. 5 i + 4] its c0, first, run, stride and
 // nbytes (PLANES_STRIDED, LEVEL >= SEG_STRIDED), selects[7 i .. 7 i + 6] its SELECT_PARAMS (PLANES_SELECT, LEVEL == SEG_SELECT); tile_start counts
@@ -707,16 +790,8 @@ __device__ __forceinline__ void segments_tile(const CopySeg * __restrict__ segs,
             case 8 | 16: clip_merge_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
             default: break;
         }
-    } else if (!sg.base) {
-        if ((sg.mode & 0xff) > 1) planes_tile<false>(sg, tile, lds);
-        else copy_segment_tile(sg, tile);
-    } else if ((sg.mode & 0xff) > 1) {
-        planes_tile<true>(sg, tile, lds);
     } else {
-        const u64 g_first = (sg.dst >> 4) + (u64)tile * COPY_TILE_GRANULES, g_end = (sg.dst + sg.len + 15) >> 4;
-        const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
-        if (sg.mode & PLANES_INVERSE) delta1_tile<true>(src, base, dst, sg.len, g_first, g_last);
-        else delta1_tile<false>(src, base, dst, sg.len, g_first, g_last);
+        whole_segment_tile(sg, tile, lds);
     }
 }
 
@@ -744,6 +819,31 @@ __global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg 
                                                                   const u64 * __restrict__ clips, const u64 * __restrict__ periods, const u64 * __restrict__ selects) {
     __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
     segments_tile<SEG_SELECT>(segs, tile_start, nseg, clips, periods, selects, (u8 *)lds);
+}
+
+// The kernel of an update's patch launch (bz3_hip_update_device_range, api_frames.hip): clipped splits, whose [a, b) are clips[2 i], clips[2 i + 1],
+// beside segments that are moved whole.  It holds no merge that is clipped, strided or selected, and the kernels above hold no clipped split: a
+// launch has segments of one family (copy_segments sees to it).
+__global__ void __launch_bounds__(COPY_THREADS) k_patch_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                 const u64 * __restrict__ clips) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
+    const CopySeg sg = segs[lo];
+    const u32 tile = blockIdx.x - tile_start[lo];
+    if (!(sg.mode & PLANES_CLIP)) return whole_segment_tile(sg, tile, (u8 *)lds);
+    const u8 * src = (const u8 *)sg.src;
+    const u8 * base = (const u8 *)sg.base;
+    u8 * dst = (u8 *)sg.dst;
+    const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
+    switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+        case 2: clip_split_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 4: clip_split_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 8: clip_split_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 2 | 16: clip_split_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 4 | 16: clip_split_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 8 | 16: clip_split_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        default: break;
+    }
 }
 
 

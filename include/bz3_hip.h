@@ -356,6 +356,46 @@ BZIP3_API int bz3_hip_decompress_device_select_many(int32_t n, const uint32_t el
 BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n,
                                        const uint64_t * pieces, uint64_t n_pieces);
 
+/* Range update: the write mirror of range decode.  The bytes [offset, offset + w) of what a frame decodes to are replaced, and of the frame only
+ * the chunks that hold them are coded again.  f, k, X, p_j, o_j and T are as in the range-decode contract above, c_j is chunk j's coded size from
+ * its chunk header.  Chunk j is TOUCHED iff w > 0 and [p_j, p_j + o_j) shares a byte with [offset, offset + w); a touched chunk is CUT if the
+ * range does not hold all of [p_j, p_j + o_j), and COVERED otherwise.  Empty chunks (o_j == 0) are never touched.
+ *   Result.  On BZ3_OK, out[0, *out_size) is a frame f' with f's 13 header bytes and f's number of chunks.  An untouched chunk is chunk j of f,
+ *   copied verbatim (8 header bytes and c_j coded bytes): its payload is never decoded, and corruption in it is not noticed.  A touched chunk
+ *   is exactly the chunk bz3_hip_compress_device_delta writes for a block of o_j bytes with the content X'[p_j, p_j + o_j), split with k and coded
+ *   against the frame's block size; its chunk header carries the new coded size and o_j.  X' is X with the bytes [offset, offset + w) replaced by
+ *   data[0, w) -- with a base by (data[i] - base[i]) mod 256.  `base` holds the base's bytes OF THE RANGE, as in the range-decode call: base[i]
+ *   pairs with data[i]; NULL means none.  Consequence: if f == bz3_compress(bs, S(x)), then f' == bz3_compress(bs, S(x')) byte for byte.
+ *   Order of work.  The frame header and EVERY chunk header are walked and checked first, with the checks of the whole-frame decode that do not
+ *   concern capacity (the plain walk: a few microseconds per chunk, and all records are needed to place the copies); a malformed header BEHIND
+ *   the range is therefore reported, which is where the update is stricter than range decode.  Then every cut chunk of the call is decoded
+ *   whole, with its CRC and per-block checks as in the full call.  Only after both steps is anything written to `out`: on a header error, or
+ *   a cut chunk that fails to decode, the call returns that code with *out_size = 0 and `out` untouched.  On an encode error afterwards (not
+ *   expected) *out_size = 0 and out[0, cap) is unspecified.  `in`, `data` and `base` are never written; nothing outside out[0, cap) is ever
+ *   written (cap: *out_size on entry).
+ *   Range.  offset + w must not overflow and must be <= T, else BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor.  w == 0
+ *   gives a verbatim copy of the frame (its chunks, without anything that follows the last one in `in`); the headers are still checked.
+ *   Capacity.  need = 13 + sum over j of (8 + (touched_j ? bz3_bound(o_j) : c_j)), known after the walk; cap < need is BZ3_ERR_DATA_TOO_BIG
+ *   before any write.
+ *   Overlap.  out[0, cap) must not overlap in[0, in_size), data[0, w) or base[0, w): BZ3_ERR_INIT before any write.
+ * _many: n independent updates on ONE GPU; the same `in` may appear more than once; offsets, elem_sizes, bases and bases[i] may be NULL with their
+ * usual meanings (0, 1, none).  Whole-call checks, return value, rcs[], independence of frames and the headroom rule are those of
+ * bz3_hip_decompress_device_range_many; a frame that fails leaves out_sizes[i] = 0.  The touched chunks of all frames share windows in frame
+ * order: 256 frames with one touched chunk each are one CM decode launch at most and one CM encode launch, and the states are sized from the
+ * touched chunks, never from n_blocks.  A call whose touched chunks exceed one window decodes its cut chunks twice: once to check them before the
+ * first write, once in the window that codes them.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_update_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * data, size_t w,
+                                          const void * base, void * out, size_t * out_size);
+BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                               const uint64_t offsets[], const void * const datas[], const size_t ws[],
+                                               const void * const bases[], void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: one launch of the patch of an update call: n (src_off, base_off, dst_off, len, elem_size, a, b) septuples (host array of 7 n u64)
+ * relative to `src` / `base` / `dst`, the layout of bz3_hip_debug_range in the forward direction.  The `len` bytes at dst_off are a slot that
+ * holds split_k of a chunk; the chunk's bytes [a, b), a <= b <= len, get the values of the b - a bytes at src_off, less the b - a bytes at base_off
+ * unless base_off is UINT64_MAX: src_off and base_off address the clip's first byte.  No other byte of the slot, and nothing of `src` or `base`,
+ * is written.  One launch takes mixed elem_size.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
