@@ -75,7 +75,7 @@ void DeviceCtx::ensure_aux() {  // caller holds mu
     // stream is there and whose events are not (every later call would record on null events)
     hipStream_t st[AUX] = {}, sm[AUX] = {}, rs = nullptr, du = nullptr;
     hipEvent_t e0[AUX] = {}, e1[AUX] = {}, ep = nullptr;
-    int reserved = 0;
+    int reserved = 0, device_cus = 0;
     try {
         HIP_CHECK(hipEventCreate(&ep));
 #ifndef BZ3_EMU
@@ -99,6 +99,7 @@ void DeviceCtx::ensure_aux() {  // caller holds mu
                 }
             } else {
                 for (uint32_t wd : side) reserved += __builtin_popcount(wd);
+                device_cus = real_cus;
             }
         }
 #endif
@@ -126,6 +127,7 @@ void DeviceCtx::ensure_aux() {  // caller holds mu
     rest = rs;
     for (int k = 0; k < AUX; k++) aux_m[k] = sm[k];
     reserved_cus = reserved;
+    real_cus = device_cus;
     for (int k = 0; k < AUX; k++) {
         aux[k] = st[k];
         ev_d0[k] = e0[k];
@@ -391,6 +393,7 @@ BZIP3_API int bz3_hip_set_cm_mode(int mode) {
 BZIP3_API unsigned bz3_hip_cm_blocks_given_up(void) { return g_cm_given_up.load(); }
 
 BZIP3_API void bz3_hip_debug_bwt_big_rounds(int k) { bwt_set_big_rounds(k); }
+BZIP3_API void bz3_hip_debug_set_unbwt_log_stride(int log_stride) { unbwt_set_log_stride(log_stride); }
 
 BZIP3_API int bz3_hip_cm_variant_for(int device, int blocks, int encode) {
     DeviceCtx * c = get_ctx(device);

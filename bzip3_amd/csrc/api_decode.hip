@@ -90,8 +90,12 @@ void decode_front(bz3_state * st, u8 * buf, size_t buffer_size, s32 compressed_s
 }
 
 // After the CM kernel: index checks and inverse BWT.  Leaves the data in st->b1, the free buffer in st->b2.
-// Returns false when the block failed.
-bool decode_unbwt(bz3_state * st, Arena & arena, float cm_ms) {
+// Returns false when the block failed.  lanes: bwt_inverse's lane target (0 = the whole device).
+// bwt_inverse itself no longer waits for anything (no read-back of the splitter count, no wait at its end); the wait after it is kept HERE, and on
+// purpose.  With no wait at all the host runs a whole window ahead, some 900 launches deep, and the tail of 768 x 8 MiB blocks measured 0.87 s against
+// 0.75 s with this wait after every block (0.73 s after every third, 0.74 s after every tenth; the parent, which also read the count back: 0.90 s;
+// profiles/unbwt_tail_after.txt).  Nothing depends on it for correctness: every later user of the arena launches on st->xs.
+bool decode_unbwt(bz3_state * st, Arena & arena, float cm_ms, u32 lanes) {
     hipStream_t s = st->xs;
     st->t[BZ3_HIP_T_CM] = cm_ms;
     const s32 n = st->size_before_bwt;
@@ -111,7 +115,8 @@ bool decode_unbwt(bz3_state * st, Arena & arena, float cm_ms) {
         if (n == 1) HIP_CHECK(hipMemcpyAsync(b2, b1, 1, hipMemcpyDeviceToDevice, s));
     } else {
         if (st->bwt_idx <= 0) { st->last_error = BZ3_ERR_BWT; return false; }
-        bwt_inverse(b1, (u32)n, (u32)st->bwt_idx, b2, arena, s);  // :758
+        bwt_inverse(b1, (u32)n, (u32)st->bwt_idx, b2, arena, s, lanes);  // :758
+        HIP_CHECK(hipStreamSynchronize(s));
     }
     st->b1 = b2;
     st->b2 = b1;
@@ -353,6 +358,8 @@ void decode_group(bz3_state ** sts, u8 ** bufs, const size_t * buffer_sizes, con
         s = lead->ctx->rest;
         for (s32 i = 0; i < n; i++) sts[i]->xs = s;
     }
+    // the walk of the inverse BWT is sized to the lanes its stream's CUs keep resident: on the masked stream, the CUs that are not reserved
+    const u32 unbwt_lanes = s != s_cm && lead->ctx->real_cus > lead->ctx->reserved_cus ? (u32)(lead->ctx->real_cus - lead->ctx->reserved_cus) * UNBWT_LANES_PER_CU : 0u;
     DrainOnUnwind drain_rest{s == s_cm ? nullptr : s, side_streams == lead->ctx->aux ? nullptr : side_streams, side_streams == lead->ctx->aux ? 0 : DeviceCtx::AUX};
     const s32 nwin = (n + tail_window - 1) / tail_window;
     const s32 lag = tail_slots - 1;  // window k is finished in iteration k + lag
@@ -380,7 +387,7 @@ void decode_group(bz3_state ** sts, u8 ** bufs, const size_t * buffer_sizes, con
                 }
                 if (st->pending != bz3_state::DEC_CODED) continue;
                 borrow(i);
-                if (!decode_unbwt(st, arena, cm_ms)) continue;
+                if (!decode_unbwt(st, arena, cm_ms, unbwt_lanes)) continue;
                 w.alive[(size_t)(i - w.w0)] = 1;
                 if (st->model & 2) {
                     if (st->lzp_size < 4) {  // lzp_decompress: `if (n < 4) return -1` (:252) -> BZ3_ERR_CRC (:769-771)

@@ -66,6 +66,7 @@ struct DeviceCtx {
     hipStream_t aux_m[AUX] = {};  // the decoder's side streams, on the reserved CUs (the encoder's rings keep the plain ones: call 4 measured its
                                          // front end 6 % SLOWER with its LZP drivers confined to 32 CUs, profiles/r05_cu_partition_256x64MiB.txt)
     int reserved_cus = 0;
+    int real_cus = 0;             // the device's own CU count where the partition exists (0: none)
     static int reserved_cus_wanted() { return cu_reserve_setting(); }
     static int cu_reserve_setting() {
         static const int v = [] {

@@ -102,9 +102,14 @@ size_t bwt_workspace_bytes(u64 n);
 void bwt_set_big_rounds(int k);  // tests only: more windows for the big groups before the deep path (k < 0: the default, 1)
 
 // ---- inverse BWT (unbwt.hip) -- replaces libsais_unbwt, include/libsais.h:5260-5262 ----------
-// Synchronous.  idx must already be validated (0 < idx <= n).
-void bwt_inverse(const u8 * d_in, u32 n, u32 idx, u8 * d_out, Arena & tmp, hipStream_t s);
+// Asynchronous: no wait inside, and the scratch is back in `tmp` on return -- `tmp` must be an arena whose every user launches on `s`.
+// idx must already be validated (0 < idx <= n).  lanes: how many lanes the CUs that `s` runs on keep resident (2048 per CU; 0 = all
+// CUs of the current device); it picks the splitter stride (unbwt_log_stride), never the output.
+constexpr u32 UNBWT_LANES_PER_CU = 2048;  // 32 waves: what a CU keeps resident (the walk's 20 VGPRs allow 8 waves per SIMD)
+void bwt_inverse(const u8 * d_in, u32 n, u32 idx, u8 * d_out, Arena & tmp, hipStream_t s, u32 lanes = 0);
 size_t unbwt_workspace_bytes(u64 n);
+int unbwt_log_stride(u32 rows, u32 lanes);  // log2 of the rows per splitter
+void unbwt_set_log_stride(int v);           // tests / sweeps: 0..8 forces it for every block, -1 = the rule
 
 // ---- CM coder (cm.hip) -- replaces begin/encode_bytes/decode_bytes, src/libbz3.c:333-494 -----
 // One workgroup (= one CU: the 145.5 KiB model fills its LDS) per block; a batch is ONE launch with

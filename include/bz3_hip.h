@@ -42,6 +42,9 @@ BZIP3_API int bz3_hip_set_cm_mode(int mode);
 /* Test hook: how many more code windows the suffix sorter gives groups that are too large for its in-LDS kernels before rank doubling
  * takes them (0 = none: straight to the deep path; k < 0 = the default, 1).  Output bytes do not depend on it. */
 BZIP3_API void bz3_hip_debug_bwt_big_rounds(int k);
+/* Test hook of the inverse BWT: one splitter per 2^log_stride rows for every block (0..8; -1 = the rule, which sizes the splitter walk to the
+ * lanes the device keeps resident).  Output bytes do not depend on it. */
+BZIP3_API void bz3_hip_debug_set_unbwt_log_stride(int log_stride);
 /* Number of blocks the row-cache kernels have handed back to the full-model kernels so far (statistics). */
 BZIP3_API unsigned bz3_hip_cm_blocks_given_up(void);
 /* Number of blocks sent STRAIGHT to the whole-model CM kernels so far (statistics): blocks of batches that take a row-cache variant (more blocks than
