@@ -117,6 +117,7 @@ def _declare(L, strict=True):
         "bz3_hip_stage_lzp_decode": (i32, [vp, i32, vp, i32]),
         "bz3_hip_stage_bwt": (i32, [vp, vp, i32]),
         "bz3_hip_stage_unbwt": (i32, [vp, vp, i32, i32]),
+        "bz3_hip_debug_unbwt_many": (i32, [vp, vp, vp, vp, i32]),
         "bz3_hip_stage_last_ms": (C.c_float, []),
         "bz3_hip_debug_sort_u32": (i32, [vp, u32, C.c_int, C.c_int, vp, vp]),
         "bz3_hip_debug_scan_u32": (i32, [vp, u32, vp]),
@@ -230,6 +231,18 @@ class StageApi:
         out = (C.c_uint8 * max(1, len(data)))()
         rc = self.lib.bz3_hip_stage_unbwt(_cbuf(data, len(data)), out, len(data), idx)
         return rc, C.string_at(out, len(data))
+
+    def unbwt_many(self, jobs):
+        """jobs: (bytes, index) pairs, through the batched inverse BWT in runs of at most four in the order given.  (rc, [bytes, ...])."""
+        k = len(jobs)
+        ins = [_cbuf(d, len(d)) for d, _ in jobs]
+        outs = [(C.c_uint8 * max(1, len(d)))() for d, _ in jobs]
+        inp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in ins])
+        outp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in outs])
+        n = (C.c_int32 * max(1, k))(*[len(d) for d, _ in jobs])
+        idx = (C.c_int32 * max(1, k))(*[i for _, i in jobs])
+        rc = self.lib.bz3_hip_debug_unbwt_many(inp, outp, n, idx, k)
+        return rc, [C.string_at(o, len(d)) for o, (d, _) in zip(outs, jobs)]
 
     def cm_encode(self, data):
         out = (C.c_uint8 * (len(data) + len(data) // 50 + 64))()

@@ -89,19 +89,21 @@ void decode_front(bz3_state * st, u8 * buf, size_t buffer_size, s32 compressed_s
     st->pending = bz3_state::DEC_CODED;
 }
 
-// After the CM kernel: index checks and inverse BWT.  Leaves the data in st->b1, the free buffer in st->b2.
-// Returns false when the block failed.  lanes: bwt_inverse's lane target (0 = the whole device).
-// bwt_inverse itself no longer waits for anything (no read-back of the splitter count, no wait at its end); the wait after it is kept HERE, and on
-// purpose.  With no wait at all the host runs a whole window ahead, some 900 launches deep, and the tail of 768 x 8 MiB blocks measured 0.87 s against
-// 0.75 s with this wait after every block (0.73 s after every third, 0.74 s after every tenth; the parent, which also read the count back: 0.90 s;
-// profiles/unbwt_tail_after.txt).  Nothing depends on it for correctness: every later user of the arena launches on st->xs.
-bool decode_unbwt(bz3_state * st, Arena & arena, float cm_ms, u32 lanes) {
+// After the CM kernel: the index checks in front of the inverse BWT, and the choice of buffers.  Leaves the data-to-be in st->b1 and the free buffer
+// in st->b2, as the inverse BWT will have left them.  Returns -1 when the block failed, 0 when it needed no transform (n <= 1), 1 when `item`
+// is to go through bwt_inverse_batch.
+// The inverse BWTs themselves run in decode_group, collected per window and in runs of up to UB_MAX_BATCH blocks per launch sequence
+// (unbwt_batch_size), and the host waits for the stream once per RUN.  bwt_inverse_batch waits for nothing, and nothing depends on that wait
+// for correctness -- every later user of the arena launches on st->xs -- it is there for speed: with no wait at all the host runs a whole window
+// ahead, some 900 launches deep, and the tail of 768 x 8 MiB blocks measured 0.87 s against 0.75 s with a wait after every block (0.73 s after
+// every third, 0.74 s after every tenth: profiles/unbwt_tail_after.txt; with runs: profiles/unbwt_batch.txt).
+int decode_unbwt_check(bz3_state * st, float cm_ms, UbBatchItem & item) {
     hipStream_t s = st->xs;
     st->t[BZ3_HIP_T_CM] = cm_ms;
     const s32 n = st->size_before_bwt;
     if (st->bwt_idx > n) {  // :750-753
         st->last_error = BZ3_ERR_MALFORMED_HEADER;
-        return false;
+        return -1;
     }
     u8 *b1 = st->d_swap, *b2 = st->user;  // after the swap of :748
     if (st->lean) {  // lean state: the coder wrote into the caller's buffer; the borrowed swap buffer receives the text
@@ -110,19 +112,20 @@ bool decode_unbwt(bz3_state * st, Arena & arena, float cm_ms, u32 lanes) {
     }
     const double t0 = now_ms();
     // libsais_unbwt's own argument checks (include/libsais.h:5210-5232)
+    int queued = 0;
     if (n <= 1) {
-        if (st->bwt_idx != n) { st->last_error = BZ3_ERR_BWT; return false; }
+        if (st->bwt_idx != n) { st->last_error = BZ3_ERR_BWT; return -1; }
         if (n == 1) HIP_CHECK(hipMemcpyAsync(b2, b1, 1, hipMemcpyDeviceToDevice, s));
     } else {
-        if (st->bwt_idx <= 0) { st->last_error = BZ3_ERR_BWT; return false; }
-        bwt_inverse(b1, (u32)n, (u32)st->bwt_idx, b2, arena, s, lanes);  // :758
-        HIP_CHECK(hipStreamSynchronize(s));
+        if (st->bwt_idx <= 0) { st->last_error = BZ3_ERR_BWT; return -1; }
+        item = UbBatchItem{b1, b2, (u32)n, (u32)st->bwt_idx};  // :758
+        queued = 1;
     }
     st->b1 = b2;
     st->b2 = b1;
     st->size_src = n;
-    st->t[BZ3_HIP_T_BWT] = (float)(now_ms() - t0);
-    return true;
+    st->t[BZ3_HIP_T_BWT] = (float)(now_ms() - t0);  // (a queued block: its run's wall time / the run's blocks, set by decode_group)
+    return queued;
 }
 
 // After the LZP kernel (if any): mRLE decode, size checks, copy back, CRC.
@@ -361,6 +364,9 @@ void decode_group(bz3_state ** sts, u8 ** bufs, const size_t * buffer_sizes, con
     // the walk of the inverse BWT is sized to the lanes its stream's CUs keep resident: on the masked stream, the CUs that are not reserved
     const u32 unbwt_lanes = s != s_cm && lead->ctx->real_cus > lead->ctx->reserved_cus ? (u32)(lead->ctx->real_cus - lead->ctx->reserved_cus) * UNBWT_LANES_PER_CU : 0u;
     DrainOnUnwind drain_rest{s == s_cm ? nullptr : s, side_streams == lead->ctx->aux ? nullptr : side_streams, side_streams == lead->ctx->aux ? 0 : DeviceCtx::AUX};
+    std::vector<UbBatchItem> ub_items;
+    std::vector<u32> ub_sizes;
+    std::vector<s32> ub_owner;
     const s32 nwin = (n + tail_window - 1) / tail_window;
     const s32 lag = tail_slots - 1;  // window k is finished in iteration k + lag
     // BZ3_HIP_TRACE_RINGS=1 (diagnosis, read once): where this thread's wall time goes in the ring -- a line on stderr when the call ends
@@ -377,6 +383,10 @@ void decode_group(bz3_state ** sts, u8 ** bufs, const size_t * buffer_sizes, con
             w.lz_jobs.clear();
             w.lz_owner.clear();
             w.alive.assign((size_t)(w.w1 - w.w0), 0);
+            // the window's blocks first through their checks: the ones that fail keep their error and drop out, the rest are collected ...
+            ub_items.clear();
+            ub_sizes.clear();
+            ub_owner.clear();
             for (s32 i = w.w0; i < w.w1; i++) {
                 bz3_state * st = sts[i];
                 if (st->pending == bz3_state::DEC_STORED) {  // :686-691
@@ -387,8 +397,31 @@ void decode_group(bz3_state ** sts, u8 ** bufs, const size_t * buffer_sizes, con
                 }
                 if (st->pending != bz3_state::DEC_CODED) continue;
                 borrow(i);
-                if (!decode_unbwt(st, arena, cm_ms, unbwt_lanes)) continue;
+                UbBatchItem item{};
+                const int r = decode_unbwt_check(st, cm_ms, item);
+                if (r < 0) continue;
                 w.alive[(size_t)(i - w.w0)] = 1;
+                if (r > 0) {
+                    ub_items.push_back(item);
+                    ub_sizes.push_back(item.n);
+                    ub_owner.push_back(i);
+                }
+            }
+            // ... and go through the inverse BWT in runs: one launch sequence and one wait per run (decode_unbwt_check: why there is a wait)
+            for (size_t at = 0; at < ub_items.size();) {
+                const u32 b = unbwt_batch_size(ub_sizes.data() + at, (u32)(ub_items.size() - at), arena.cap - arena.used, unbwt_lanes);
+                const double t0 = now_ms();
+                // every block's stride is picked for ALL of the stream's lanes, as for a block alone: a stride picked for lanes / b measured slower
+                // (tail 0.650 against 0.633 s at 768 x 8 MiB: profiles/unbwt_batch.txt)
+                bwt_inverse_batch(ub_items.data() + at, b, arena, s, unbwt_lanes);
+                HIP_CHECK(hipStreamSynchronize(s));
+                const float each = (float)(now_ms() - t0) / (float)b;
+                for (u32 j = 0; j < b; j++) sts[ub_owner[at + j]]->t[BZ3_HIP_T_BWT] = each;
+                at += b;
+            }
+            for (s32 i = w.w0; i < w.w1; i++) {
+                bz3_state * st = sts[i];
+                if (!w.alive[(size_t)(i - w.w0)]) continue;
                 if (st->model & 2) {
                     if (st->lzp_size < 4) {  // lzp_decompress: `if (n < 4) return -1` (:252) -> BZ3_ERR_CRC (:769-771)
                         st->last_error = BZ3_ERR_CRC;

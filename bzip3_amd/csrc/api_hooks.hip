@@ -174,6 +174,46 @@ BZIP3_API int32_t bz3_hip_stage_unbwt(const uint8_t * in, uint8_t * out, int32_t
     });
 }
 
+// Tests and sweeps only: the inverse BWT of `count` blocks on host buffers, through bwt_inverse_batch in runs of at most UB_MAX_BATCH in the order
+// given (blocks of fewer than 2 bytes apart) -- the way to put chosen sizes into one batch.  Synchronous.  The arena is sized for a full run of the
+// largest block.  Returns 0, or -1 when a block's arguments are ones libsais_unbwt refuses (nothing is written then).
+BZIP3_API int32_t bz3_hip_debug_unbwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, const int32_t * idx, int32_t count) {
+    return stage_guard([&]() -> s32 {
+        if (count < 0 || (count > 0 && (!in || !out || !n || !idx))) return -1;
+        u64 largest = 0;
+        for (s32 k = 0; k < count; k++) {
+            if (n[k] < 0 || (n[k] <= 1 ? idx[k] != n[k] : (idx[k] <= 0 || idx[k] > n[k]))) return -1;
+            if ((u64)n[k] > largest) largest = (u64)n[k];
+        }
+        std::vector<UbBatchItem> items;
+        std::vector<u32> sizes;
+        std::vector<s32> owner;
+        StageEnv e;
+        for (s32 k = 0; k < count; k++) {
+            if (n[k] == 1) out[k][0] = in[k][0];
+            if (n[k] < 2) continue;
+            const u8 * d = e.dev((size_t)n[k] + 64, in[k], (size_t)n[k]);
+            items.push_back(UbBatchItem{d, e.dev((size_t)n[k] + 64), (u32)n[k], (u32)idx[k]});
+            sizes.push_back((u32)n[k]);
+            owner.push_back(k);
+        }
+        if (items.empty()) return 0;
+        const size_t plain = workspace_bytes_for(largest + 64), full = unbwt_batch_workspace_bytes(largest + 64, UB_MAX_BATCH);
+        Arena a = e.ctx->arena_for(plain > full ? plain : full);
+        HIP_CHECK(hipStreamSynchronize(e.s));
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t at = 0; at < items.size();) {
+            const u32 b = unbwt_batch_size(sizes.data() + at, (u32)(items.size() - at), a.cap - a.used, 0u);
+            bwt_inverse_batch(items.data() + at, b, a, e.s);
+            HIP_CHECK(hipStreamSynchronize(e.s));
+            at += b;
+        }
+        g_stage_ms.store(std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        for (size_t j = 0; j < items.size(); j++) e.down(out[owner[j]], items[j].out, (size_t)items[j].n);
+        return 0;
+    });
+}
+
 // Tests only: the CU masks of the partition (DeviceCtx::cu_masks) for a device of `cus` CUs and `reserve` reserved ones: words = (cus + 31) / 32 each.
 BZIP3_API int32_t bz3_hip_debug_cu_masks(int cus, int reserve, uint32_t * side, uint32_t * rest) {
     if (cus < 32 || cus > 1024 || reserve < 8 || !side || !rest) return -1;

@@ -46,23 +46,28 @@ __device__ __forceinline__ void scan_load_items(const u32 * __restrict__ data, u
     }
 }
 
-__global__ void __launch_bounds__(SC_BLOCK) k_scan_reduce(const u32 * __restrict__ data, u64 n, u32 * __restrict__ sums) {
+// The kernels' bodies are __device__ functions of the tile (`bx`): the single form runs them on blockIdx.x, the batched form (further down:
+// several independent tables in one launch, grid.y = table) on the same index after it has picked its table by blockIdx.y.
+__device__ __forceinline__ void scan_reduce_body(const u32 * __restrict__ data, u64 n, u32 * __restrict__ sums, u32 bx) {
     __shared__ u32 lds[SC_BLOCK / WAVE + 1];
-    const u64 base = (u64)blockIdx.x * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
+    const u64 base = (u64)bx * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
     u32 v[SC_ITEMS];
     scan_load_items(data, n, base, v);
     u32 acc = 0;
 #pragma unroll
     for (int k = 0; k < SC_ITEMS; k++) acc += v[k];
     u32 tot = block_sum<SC_BLOCK>(acc, lds);
-    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+    if (threadIdx.x == 0) sums[bx] = tot;
+}
+__global__ void __launch_bounds__(SC_BLOCK) k_scan_reduce(const u32 * __restrict__ data, u64 n, u32 * __restrict__ sums) {
+    scan_reduce_body(data, n, sums, blockIdx.x);
 }
 
-// Local exclusive scan of one tile; `sums` (may be null) holds the exclusive prefix of every tile.
-__global__ void __launch_bounds__(SC_BLOCK) k_scan_apply(u32 * __restrict__ data, u64 n, const u32 * __restrict__ sums,
-                                                         u32 * __restrict__ total_out) {
+// Local exclusive scan of one tile; `sums` (may be null) holds the exclusive prefix of every tile.  one_tile: the table is this tile alone.
+__device__ __forceinline__ void scan_apply_body(u32 * __restrict__ data, u64 n, const u32 * __restrict__ sums, u32 * __restrict__ total_out, u32 bx,
+                                                bool one_tile) {
     __shared__ u32 lds[SC_BLOCK / WAVE + 1];
-    const u64 base = (u64)blockIdx.x * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
+    const u64 base = (u64)bx * SC_TILE + (u64)threadIdx.x * SC_ITEMS;
     u32 v[SC_ITEMS];
     scan_load_items(data, n, base, v);
     u32 acc = 0;
@@ -70,7 +75,7 @@ __global__ void __launch_bounds__(SC_BLOCK) k_scan_apply(u32 * __restrict__ data
     for (int k = 0; k < SC_ITEMS; k++) acc += v[k];
     u32 tot;
     u32 pre = block_excl_add<SC_BLOCK>(acc, lds, tot);
-    if (sums) pre += sums[blockIdx.x];
+    if (sums) pre += sums[bx];
     if (base + SC_ITEMS <= n && (reinterpret_cast<uintptr_t>(data) & 15u) == 0) {
         uint4 a, b;
         a.x = pre; a.y = a.x + v[0]; a.z = a.y + v[1]; a.w = a.z + v[2];
@@ -84,7 +89,11 @@ __global__ void __launch_bounds__(SC_BLOCK) k_scan_apply(u32 * __restrict__ data
             pre += v[k];
         }
     }
-    if (total_out && gridDim.x == 1 && threadIdx.x == 0) *total_out = tot;
+    if (total_out && one_tile && threadIdx.x == 0) *total_out = tot;
+}
+__global__ void __launch_bounds__(SC_BLOCK) k_scan_apply(u32 * __restrict__ data, u64 n, const u32 * __restrict__ sums,
+                                                         u32 * __restrict__ total_out) {
+    scan_apply_body(data, n, sums, total_out, blockIdx.x, gridDim.x == 1);
 }
 
 __global__ void k_add_last(const u32 * __restrict__ sums_excl, const u32 * __restrict__ last_tile_total, u32 * out) {
@@ -98,7 +107,7 @@ __global__ void k_add_last(const u32 * __restrict__ sums_excl, const u32 * __res
 // passes per block paid ~1.5 ms (profiles/r05_call6_kernels_*: 123 k_scan_apply + 68 k_scan_reduce launches per 256 MiB block).
 constexpr int SC1_BLOCK = 1024;
 constexpr u64 SC1_MAX = 262144;
-__global__ void __launch_bounds__(SC1_BLOCK) k_scan_single(u32 * __restrict__ data, u64 n, u32 * __restrict__ total_out) {
+__device__ __forceinline__ void scan_single_body(u32 * __restrict__ data, u64 n, u32 * __restrict__ total_out) {
     __shared__ u32 lds[SC1_BLOCK / WAVE + 1];
     const u64 quads = (n + 3) / 4;                                  // the table in groups of four words
     const u64 per = (quads + SC1_BLOCK - 1) / SC1_BLOCK;            // groups per thread
@@ -137,6 +146,15 @@ __global__ void __launch_bounds__(SC1_BLOCK) k_scan_single(u32 * __restrict__ da
     }
     if (total_out && threadIdx.x == 0) *total_out = tot;
 }
+__global__ void __launch_bounds__(SC1_BLOCK) k_scan_single(u32 * __restrict__ data, u64 n, u32 * __restrict__ total_out) {
+    scan_single_body(data, n, total_out);
+}
+
+// (experiments: the recursive scan for every size, as up to round 4; read once)
+static bool scan_no_single() {
+    static const bool v = getenv("BZ3_SCAN_NO_SINGLE") != nullptr;
+    return v;
+}
 
 static void scan_rec(u32 * d, u64 n, u32 * d_total, Arena & tmp, hipStream_t s) {
     if (n == 0) {
@@ -147,8 +165,7 @@ static void scan_rec(u32 * d, u64 n, u32 * d_total, Arena & tmp, hipStream_t s) 
         launch(k_scan_apply, dim3(1), dim3(SC_BLOCK), 0, s, d, n, (const u32 *)nullptr, d_total);
         return;
     }
-    static const bool no_single = getenv("BZ3_SCAN_NO_SINGLE") != nullptr;  // (experiments: the recursive scan for every size, as up to round 4; read once)
-    if (n <= SC1_MAX && !no_single) {
+    if (n <= SC1_MAX && !scan_no_single()) {
         launch(k_scan_single, dim3(1), dim3(SC1_BLOCK), 0, s, d, n, d_total);
         return;
     }
@@ -162,6 +179,75 @@ static void scan_rec(u32 * d, u64 n, u32 * d_total, Arena & tmp, hipStream_t s) 
 }
 
 void exclusive_scan_u32(u32 * d_data, u64 n, u32 * d_total, Arena & tmp, hipStream_t s) { scan_rec(d_data, n, d_total, tmp, s); }
+
+// ---- several tables in one launch per step -------------------------------------------------------------------------------------------
+// The job table travels by value, as a kernel argument; grid = (tiles of the longest table, table), and a workgroup whose tile lies
+// beyond its own table leaves at once.  The path (one tile / one workgroup / recursive) is the longest table's; every kernel works on
+// its own table's length, however short.
+struct ScanBatch {
+    u32 count;
+    struct Job {
+        u32 * data;
+        u32 * sums;   // k_scan_reduce_many writes them, k_scan_apply_many reads them (null: none)
+        u32 * total;  // may be null
+        u64 n;        // >= 1
+    } job[SORT_MAX_BATCH];
+};
+__global__ void __launch_bounds__(SC_BLOCK) k_scan_reduce_many(ScanBatch b) {
+    const ScanBatch::Job & j = b.job[blockIdx.y];
+    if ((u64)blockIdx.x * SC_TILE >= j.n) return;
+    scan_reduce_body(j.data, j.n, j.sums, blockIdx.x);
+}
+__global__ void __launch_bounds__(SC_BLOCK) k_scan_apply_many(ScanBatch b) {
+    const ScanBatch::Job & j = b.job[blockIdx.y];
+    if ((u64)blockIdx.x * SC_TILE >= j.n) return;
+    scan_apply_body(j.data, j.n, j.sums, j.total, blockIdx.x, j.n <= (u64)SC_TILE);
+}
+__global__ void __launch_bounds__(SC1_BLOCK) k_scan_single_many(ScanBatch b) {
+    const ScanBatch::Job & j = b.job[blockIdx.y];
+    scan_single_body(j.data, j.n, j.total);
+}
+
+static void scan_rec_many(ScanBatch b, Arena & tmp, hipStream_t s) {
+    u64 longest = 0;
+    for (u32 k = 0; k < b.count; k++) longest = b.job[k].n > longest ? b.job[k].n : longest;
+    for (u32 k = 0; k < b.count; k++) b.job[k].sums = nullptr;
+    if (longest <= SC_TILE) {
+        launch(k_scan_apply_many, dim3(1, b.count), dim3(SC_BLOCK), 0, s, b);
+        return;
+    }
+    if (longest <= SC1_MAX && !scan_no_single()) {
+        launch(k_scan_single_many, dim3(1, b.count), dim3(SC1_BLOCK), 0, s, b);
+        return;
+    }
+    const u32 tiles = (u32)((longest + SC_TILE - 1) / SC_TILE);
+    size_t m = tmp.mark();
+    ScanBatch sub = b, top = b;
+    for (u32 k = 0; k < b.count; k++) {
+        const u64 t = (b.job[k].n + SC_TILE - 1) / SC_TILE;
+        u32 * sums = tmp.take<u32>(t + 1);
+        top.job[k].sums = sums;
+        top.job[k].total = nullptr;  // the grand total comes out of the scan of the tile sums
+        sub.job[k].data = sums;
+        sub.job[k].n = t;
+    }
+    launch(k_scan_reduce_many, dim3(tiles, b.count), dim3(SC_BLOCK), 0, s, top);
+    scan_rec_many(sub, tmp, s);
+    launch(k_scan_apply_many, dim3(tiles, b.count), dim3(SC_BLOCK), 0, s, top);
+    tmp.release(m);
+}
+
+void exclusive_scan_u32_many(u32 * const * d_data, const u64 * n, u32 * const * d_totals, u32 count, Arena & tmp, hipStream_t s) {
+    if (count == 0 || count > SORT_MAX_BATCH) throw HipError{hipErrorUnknown, "scan batch of a size the job table does not hold", __FILE__, __LINE__};
+    ScanBatch b;
+    b.count = count;
+    for (u32 k = 0; k < SORT_MAX_BATCH; k++) {
+        const u32 j = k < count ? k : 0;  // (unused entries repeat the first: no uninitialised bytes in the argument)
+        if (n[j] == 0) throw HipError{hipErrorUnknown, "scan batch with an empty table", __FILE__, __LINE__};
+        b.job[k] = ScanBatch::Job{d_data[j], nullptr, d_totals ? d_totals[j] : nullptr, n[j]};
+    }
+    scan_rec_many(b, tmp, s);
+}
 
 // ---------------------------------------------------------------------------------------------
 // radix pass
@@ -181,7 +267,7 @@ __device__ __forceinline__ u32 rs_tile_of_block(u32 b, u32 tiles, bool xcd) {
     const u32 per = (tiles + 7u) / 8u;
     return (b & 7u) * per + (b >> 3);
 }
-inline u32 rs_grid(u32 tiles, bool xcd) { return xcd ? 8u * ((tiles + 7u) / 8u) : tiles; }
+__host__ __device__ inline u32 rs_grid(u32 tiles, bool xcd) { return xcd ? 8u * ((tiles + 7u) / 8u) : tiles; }
 
 template <typename K, int BITS>
 __device__ __forceinline__ u32 rs_digit(K key, int shift) {
@@ -191,12 +277,12 @@ __device__ __forceinline__ u32 rs_digit(K key, int shift) {
 // BITS = digit width: 8 (256 bins, the default) or 9 (512 bins: the LZP predecessor build sorts its 18-bit hashes in two passes
 // instead of three, round 5).  A thread owns RADIX / RS_BLOCK neighbouring digits wherever a digit needs a thread.
 template <typename K, int BITS>
-__global__ void __launch_bounds__(RS_BLOCK) k_rs_hist(const K * __restrict__ keys, u64 n, int shift, u32 * __restrict__ hist, u32 tiles, u32 xcd) {
+__device__ __forceinline__ void rs_hist_body(const K * __restrict__ keys, u64 n, int shift, u32 * __restrict__ hist, u32 tiles, u32 xcd, u32 bx) {
     constexpr int RADIX = 1 << BITS;
     __shared__ u32 bins[RADIX];
     // same tile assignment as the scatter: the counts of neighbouring tiles are neighbouring words of the digit-major table, so
     // the tiles of one XCD fill whole lines of it in that XCD's L2 (and the scatter finds its tile's keys in the L2 that read them)
-    const u32 tile = rs_tile_of_block(blockIdx.x, tiles, xcd != 0u);
+    const u32 tile = rs_tile_of_block(bx, tiles, xcd != 0u);
     if (tile >= tiles) return;
 #pragma unroll
     for (int d = threadIdx.x; d < RADIX; d += RS_BLOCK) bins[d] = 0;
@@ -219,6 +305,10 @@ __global__ void __launch_bounds__(RS_BLOCK) k_rs_hist(const K * __restrict__ key
 #pragma unroll
     for (int d = threadIdx.x; d < RADIX; d += RS_BLOCK) hist[(u64)d * tiles + tile] = bins[d];
 }
+template <typename K, int BITS>
+__global__ void __launch_bounds__(RS_BLOCK) k_rs_hist(const K * __restrict__ keys, u64 n, int shift, u32 * __restrict__ hist, u32 tiles, u32 xcd) {
+    rs_hist_body<K, BITS>(keys, n, shift, hist, tiles, xcd, blockIdx.x);
+}
 
 // The tile is first put in digit order in LDS, then written out with consecutive lanes on consecutive destinations -- a digit's ~16
 // keys of a tile leave as one run instead of 16 separate 8-byte stores.  Measured in round 3 on a 256 MiB block (full-n pass of
@@ -236,149 +326,53 @@ template <typename K, bool IOTA, bool WKEYS, int BITS, bool RAW>
 __global__ void __launch_bounds__(RS_BLOCK) k_rs_scatter(const K * __restrict__ kin, K * __restrict__ kout, const u32 * __restrict__ vin,
                                                                u32 * __restrict__ vout, u64 n, int shift, const u32 * __restrict__ offs, u32 tiles,
                                                                u32 iota_split, u32 out_base, u32 xcd) {
-    constexpr int RADIX = 1 << BITS;
-    constexpr int DPT = RADIX / RS_BLOCK;  // digits per thread: d = DPT * threadIdx.x + j
-    static_assert(RADIX % RS_BLOCK == 0 && DPT >= 1, "a thread owns whole digits");
-    __shared__ u32 cnt[RS_WAVES][RADIX];
-    __shared__ u32 dstart[RADIX];   // first slot of a digit inside the tile
-    __shared__ u32 gdelta[RADIX];   // global destination of a digit's first key - dstart (mod 2^32)
-    __shared__ u32 scan_lds[RS_BLOCK / WAVE + 1];
-    __shared__ K skey[RS_TILE];
-    __shared__ u32 sval[RS_TILE];
-    const u32 tile = rs_tile_of_block(blockIdx.x, tiles, xcd != 0u);
-    if (tile >= tiles) return;
-    const int w = wave_id(), l = lane_id();
-#pragma unroll
-    for (int k = 0; k < RS_WAVES; k++)
-#pragma unroll
-        for (int d = threadIdx.x; d < RADIX; d += RS_BLOCK) cnt[k][d] = 0;
-    __syncthreads();
+#include "sort_scatter_body.hpp"  // (shared with k_rs_scatter_many by inclusion: see the file)
+}
 
-    const u64 tile_base = (u64)tile * RS_TILE;
-    const u64 wbase = tile_base + (u64)w * RS_WAVE_SPAN + l;
-    K key[RS_ROUNDS];
-    u32 local[RS_ROUNDS];
-    const u64 lt = lanemask_lt();
-    const u64 last = n - 1;
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; r++) {
-        const u64 i = wbase + (u64)r * WAVE;
-        key[r] = kin[i < n ? i : last];
-    }
-    // RAW: this thread's digits' rows of the count table, requested before the ranking below so that their latency hides behind it
-    u32 row_total[DPT], row_before[DPT];
-    if (RAW) {
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const u32 * __restrict__ row = offs + (u64)(DPT * threadIdx.x + j) * tiles;
-            u32 tot = 0, bef = 0;
-#pragma unroll 4
-            for (u32 t = 0; t < tiles; t++) {
-                const u32 c = row[t];
-                tot += c;
-                bef += t < tile ? c : 0u;
-            }
-            row_total[j] = tot;
-            row_before[j] = bef;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; r++) {
-        const u64 i = wbase + (u64)r * WAVE;
-        const bool valid = i < n;
-        const u32 d = rs_digit<K, BITS>(key[r], shift);
-        u64 peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < BITS; b++) {
-            const bool bit = (d >> b) & 1u;
-            const u64 bal = __ballot(bit);
-            peers &= bit ? bal : ~bal;
-        }
-        const u32 below = (u32)__popcll(peers & lt);
-        const u32 pre = valid ? cnt[w][d] : 0u;
-        wave_sync();
-        if (valid && below == 0) cnt[w][d] = pre + (u32)__popcll(peers);
-        wave_sync();
-        local[r] = pre + below;
-    }
-    u32 val[RS_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; r++) {
-        const u64 i = wbase + (u64)r * WAVE;
-        val[r] = IOTA ? (u32)i + ((u32)i >= iota_split ? 1u : 0u) : vin[i < n ? i : last];
-    }
-    __syncthreads();
-    {
-        u32 run[DPT];
-        u32 mine = 0;
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const u32 d = DPT * threadIdx.x + j;
-            u32 acc = 0;
-#pragma unroll
-            for (int k = 0; k < RS_WAVES; k++) {
-                u32 c = cnt[k][d];
-                cnt[k][d] = acc;
-                acc += c;
-            }
-            run[j] = acc;
-            mine += acc;
-        }
-        u32 total;
-        u32 start = block_excl_add<RS_BLOCK>(mine, scan_lds, total);  // ends with a barrier
-        u32 gbase = 0;
-        if (RAW) {
-            u32 rt = 0;
-#pragma unroll
-            for (int j = 0; j < DPT; j++) rt += row_total[j];
-            u32 all;
-            gbase = block_excl_add<RS_BLOCK>(rt, scan_lds, all);  // keys of smaller digits, all tiles
-        }
-#pragma unroll
-        for (int j = 0; j < DPT; j++) {
-            const u32 d = DPT * threadIdx.x + j;
-            dstart[d] = start;
-            if (RAW) {
-                gdelta[d] = gbase + row_before[j] + out_base - start;
-                gbase += row_total[j];
-            } else {
-                gdelta[d] = offs[(u64)d * tiles + tile] + out_base - start;
-            }
-            start += run[j];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; r++) {
-        const u32 d = rs_digit<K, BITS>(key[r], shift);
-        local[r] += dstart[d] + cnt[w][d];
-    }
-#pragma unroll
-    for (int r = 0; r < RS_ROUNDS; r++) {
-        const u64 i = wbase + (u64)r * WAVE;
-        if (i < n) {
-            skey[local[r]] = key[r];
-            sval[local[r]] = val[r];
-        }
-    }
-    __syncthreads();
-    const u64 left = n - tile_base;
-    const u32 count = left < (u64)RS_TILE ? (u32)left : (u32)RS_TILE;
-#pragma unroll
-    for (int q = 0; q < RS_ROUNDS; q++) {
-        const u32 j = (u32)q * RS_BLOCK + threadIdx.x;
-        if (j < count) {
-            const K k = skey[j];
-            const u32 pos = gdelta[rs_digit<K, BITS>(k, shift)] + j;
-            if (WKEYS) kout[pos] = k;
-            vout[pos] = sval[j];
-        }
-    }
+// The pass of several independent key arrays in one launch per step (the inverse BWT's psi build: generated values, no keys out).  grid =
+// (workgroups of the longest array, array); every array has its own length, count table, split and output.  A workgroup beyond its own
+// array's padded grid must leave BEFORE the tile assignment: rs_tile_of_block maps such an index back onto a tile of a shorter array.
+struct RsBatch8 {
+    u32 count;
+    struct Job {
+        const u8 * keys;
+        u32 * vout;
+        u32 * hist;
+        u64 n;  // >= 1
+        u32 tiles, iota_split;
+    } job[SORT_MAX_BATCH];
+};
+__global__ void __launch_bounds__(RS_BLOCK) k_rs_hist_many(RsBatch8 b, int shift, u32 xcd) {
+    const RsBatch8::Job & j = b.job[blockIdx.y];
+    if (blockIdx.x >= rs_grid(j.tiles, xcd != 0u)) return;
+    rs_hist_body<u8, 8>(j.keys, j.n, shift, j.hist, j.tiles, xcd, blockIdx.x);
+}
+template <bool RAW>
+__global__ void __launch_bounds__(RS_BLOCK) k_rs_scatter_many(RsBatch8 b, int shift, u32 out_base, u32 xcd) {
+    typedef u8 K;
+    constexpr bool IOTA = true, WKEYS = false;
+    constexpr int BITS = 8;
+    const RsBatch8::Job & j = b.job[blockIdx.y];
+    if (blockIdx.x >= rs_grid(j.tiles, xcd != 0u)) return;
+    const u8 * __restrict__ kin = j.keys;
+    u8 * __restrict__ kout = nullptr;
+    const u32 * __restrict__ vin = nullptr;
+    u32 * __restrict__ vout = j.vout;
+    const u32 * __restrict__ offs = j.hist;
+    const u64 n = j.n;
+    const u32 tiles = j.tiles, iota_split = j.iota_split;
+#include "sort_scatter_body.hpp"  // (k_rs_scatter's body, on the names declared above)
 }
 
 // Passes of up to this many tiles (512 Ki keys) skip the scan: the scatter's workgroups read the count table themselves (RAW above).
 // Every workgroup reads the whole table -- tiles * 2^BITS words from L2 -- so the bound keeps that at 128 KiB (8-bit digits) per workgroup.
 constexpr u32 RS_RAW_TILES = 128;
+
+// (experiments: the scanned table for every pass, as up to round 4; read once)
+static bool rs_no_raw() {
+    static const bool v = getenv("BZ3_RS_NO_RAW") != nullptr;
+    return v;
+}
 
 template <typename K, int BITS>
 void radix_pass_bits(const K * kin, K * kout, const u32 * vin, u32 * vout, u64 n, int shift, u32 iota_split, u32 out_base, Arena & tmp,
@@ -391,8 +385,7 @@ void radix_pass_bits(const K * kin, K * kout, const u32 * vin, u32 * vout, u64 n
     const u32 xcd = 1u;  // contiguous tiles per XCD (measured round 3: 2.37 against 3.58 ms per full-n pass with tile = blockIdx)
     const dim3 sgrid(rs_grid(tiles, xcd != 0u));
     launch(k_rs_hist<K, BITS>, sgrid, dim3(RS_BLOCK), 0, s, kin, n, shift, hist, tiles, xcd);
-    static const bool no_raw = getenv("BZ3_RS_NO_RAW") != nullptr;  // (experiments: the scanned table for every pass, as up to round 4; read once)
-    const bool raw = tiles <= RS_RAW_TILES && !no_raw;
+    const bool raw = tiles <= RS_RAW_TILES && !rs_no_raw();
     if (!raw) exclusive_scan_u32(hist, (u64)tiles * RADIX, nullptr, tmp, s);
     const bool iota = vin == nullptr, wkeys = kout != nullptr;
 #define BZ3_RS_LAUNCH(I, W, R) \
@@ -408,6 +401,34 @@ void radix_pass_bits(const K * kin, K * kout, const u32 * vin, u32 * vout, u64 n
     else BZ3_RS_DISPATCH(false);
 #undef BZ3_RS_DISPATCH
 #undef BZ3_RS_LAUNCH
+    tmp.release(m);
+}
+
+// Raw or scanned count tables: decided by the longest array, for all of them (either is exact at any size; the bound is about speed).
+void radix_pass_iota_u8_many(const RadixIotaJob * jobs, u32 count, u32 out_base, Arena & tmp, hipStream_t s) {
+    if (count == 0 || count > SORT_MAX_BATCH) throw HipError{hipErrorUnknown, "radix batch of a size the job table does not hold", __FILE__, __LINE__};
+    RsBatch8 b;
+    b.count = count;
+    size_t m = tmp.mark();
+    u32 most = 0;
+    u32 * tables[SORT_MAX_BATCH];
+    u64 words[SORT_MAX_BATCH];
+    for (u32 k = 0; k < count; k++) {
+        if (jobs[k].n == 0) throw HipError{hipErrorUnknown, "radix batch with an empty array", __FILE__, __LINE__};
+        const u32 tiles = (u32)((jobs[k].n + RS_TILE - 1) / RS_TILE);
+        words[k] = (u64)tiles * RS_RADIX;
+        tables[k] = tmp.take<u32>((size_t)words[k]);
+        b.job[k] = RsBatch8::Job{jobs[k].keys, jobs[k].vout, tables[k], jobs[k].n, tiles, jobs[k].iota_split};
+        most = tiles > most ? tiles : most;
+    }
+    for (u32 k = count; k < SORT_MAX_BATCH; k++) b.job[k] = b.job[0];
+    const u32 xcd = 1u;
+    const dim3 grid(rs_grid(most, true), count);
+    launch(k_rs_hist_many, grid, dim3(RS_BLOCK), 0, s, b, 0, xcd);
+    const bool raw = most <= RS_RAW_TILES && !rs_no_raw();
+    if (!raw) exclusive_scan_u32_many(tables, words, nullptr, count, tmp, s);
+    if (raw) launch(k_rs_scatter_many<true>, grid, dim3(RS_BLOCK), 0, s, b, 0, out_base, xcd);
+    else launch(k_rs_scatter_many<false>, grid, dim3(RS_BLOCK), 0, s, b, 0, out_base, xcd);
     tmp.release(m);
 }
 

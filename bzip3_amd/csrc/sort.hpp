@@ -44,6 +44,20 @@ inline size_t radix_temp_bytes(u64 n, int bits = 8) {  // scratch of one pass wi
 // In-place exclusive prefix sum of n u32 values; if d_total != nullptr the grand total is written there.
 void exclusive_scan_u32(u32 * d_data, u64 n, u32 * d_total, Arena & tmp, hipStream_t s);
 
+// Batched forms (the inverse BWT of several blocks at once): up to SORT_MAX_BATCH independent jobs in one launch per step, the same kernel
+// bodies on a grid of (extent of the largest job, job).  The job table is a kernel argument: nothing of it has to outlive the call.
+constexpr u32 SORT_MAX_BATCH = 4;
+// The scan of `count` tables of n[k] >= 1 values each; d_totals (may be null, as may any entry) receives the grand totals.
+void exclusive_scan_u32_many(u32 * const * d_data, const u64 * n, u32 * const * d_totals, u32 count, Arena & tmp, hipStream_t s);
+// radix_pass<u8> with generated values and no keys out, shift 0, of `count` arrays: vout[out_base + stable rank of keys[i]] = i + (i >= iota_split).
+struct RadixIotaJob {
+    const u8 * keys;
+    u32 * vout;
+    u64 n;  // >= 1
+    u32 iota_split;
+};
+void radix_pass_iota_u8_many(const RadixIotaJob * jobs, u32 count, u32 out_base, Arena & tmp, hipStream_t s);
+
 // One stable radix pass on digit (key >> shift) & 0xFF.
 //   K       : u8 / u32 / u64 keys
 //   vin     : values (nullptr => value of element i is  i + (i >= iota_split ? 1 : 0))

@@ -107,6 +107,20 @@ void bwt_set_big_rounds(int k);  // tests only: more windows for the big groups 
 // CUs of the current device); it picks the splitter stride (unbwt_log_stride), never the output.
 constexpr u32 UNBWT_LANES_PER_CU = 2048;  // 32 waves: what a CU keeps resident (the walk's 20 VGPRs allow 8 waves per SIMD)
 void bwt_inverse(const u8 * d_in, u32 n, u32 idx, u8 * d_out, Arena & tmp, hipStream_t s, u32 lanes = 0);
+// Several blocks through the same launch sequence at once: one launch per step for `count` <= UB_MAX_BATCH blocks (n >= 2 and 0 < idx <= n each;
+// smaller blocks never enter a batch), all scratch from `tmp`, job after job, released on return with the kernels in flight -- the contract of
+// bwt_inverse, which is a batch of one.  Each block keeps the stride its own rows and `lanes` give it.
+constexpr u32 UB_MAX_BATCH = 4;
+struct UbBatchItem {
+    const u8 * in;
+    u8 * out;
+    u32 n, idx;
+};
+void bwt_inverse_batch(const UbBatchItem * items, u32 count, Arena & tmp, hipStream_t s, u32 lanes = 0);
+// How many of the first `count` blocks (sizes n[k]) one batch takes, given the bytes the arena has free and the stream's lanes (0 = the device's):
+// 1 to UB_MAX_BATCH.
+u32 unbwt_batch_size(const u32 * n, u32 count, size_t arena_free, u32 lanes);
+size_t unbwt_batch_workspace_bytes(u64 n, u32 b);  // b workspaces of a block of n bytes (more than unbwt_workspace_bytes each only under a forced stride)
 size_t unbwt_workspace_bytes(u64 n);
 int unbwt_log_stride(u32 rows, u32 lanes);  // log2 of the rows per splitter
 void unbwt_set_log_stride(int v);           // tests / sweeps: 0..8 forces it for every block, -1 = the rule

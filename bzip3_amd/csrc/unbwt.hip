@@ -1,4 +1,4 @@
-// unbwt.hip -- inverse Burrows-Wheeler transform of one block on gfx950.
+// unbwt.hip -- inverse Burrows-Wheeler transform on gfx950: one block, or up to UB_MAX_BATCH blocks through one launch sequence (bwt_inverse_batch).
 // Replaces libsais_unbwt (reference include/libsais.h:5260-5262; init :4593-4617, decode :4618-4636),
 // which builds a bigram psi table and then follows ONE dependent pointer chain of n/2 steps.
 //
@@ -64,9 +64,34 @@ __device__ __forceinline__ u32 ub_sid(const u32 * __restrict__ sid, u32 row, u32
     return v < bound ? v : bound - 1;
 }
 
+// Every kernel takes a job table, BY VALUE as a kernel argument (a few hundred bytes: nothing of it has to outlive the call), and runs on a grid of
+// (x = extent of the largest job, y = job): it picks its job by blockIdx.y and leaves where its index lies beyond its own job's extent.  Each job
+// keeps its own stride, bound and slab size, because the rows differ.  One block is a batch of one, through the same kernels.  No kernel waits
+// for another workgroup: batching adds a grid dimension and nothing else.
+struct UbJob {
+    const u8 * in;
+    u8 * out;
+    u32 n, idx, rows;
+    int log_stride;
+    u32 bound, cap;
+    u32 *psi, *sid, *hist, *cum, *d_total, *split_row, *seg_len, *resume;
+    u32 * succ[2];
+    u32 * dist[2];
+    u8 * slab;
+};
+struct UbBatch {
+    u32 count;
+    UbJob job[UB_MAX_BATCH];
+};
+
 // 64 bytes per thread, 16 at a time, every load of a group in flight before the first is counted (a grid-stride loop of single-byte
 // loads is one exposed HBM round trip per byte: 1.2 ms for 256 MiB in round 2's profile; same pattern as bwt.hip k_bwt_sym_hist).
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_hist(const u8 * __restrict__ in, u32 n, u32 * __restrict__ hist) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_hist(UbBatch b) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u8 * __restrict__ in = J.in;
+    const u32 n = J.n;
+    u32 * __restrict__ hist = J.hist;
+    if ((u64)blockIdx.x * (UB_BLOCK * 64) >= n) return;
     __shared__ u32 bins[256];
     bins[threadIdx.x] = 0;
     __syncthreads();
@@ -90,7 +115,12 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_hist(const u8 * __restrict__ in
 }
 
 // cum[c] = 1 + number of bytes smaller than c; cum[256] = n + 1.  Also closes the cycle psi[0] = idx.
-__global__ void __launch_bounds__(256) k_ub_cum(const u32 * __restrict__ hist, u32 * __restrict__ cum, u32 * __restrict__ psi, u32 idx) {
+__global__ void __launch_bounds__(256) k_ub_cum(UbBatch b) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u32 * __restrict__ hist = J.hist;
+    u32 * __restrict__ cum = J.cum;
+    u32 * __restrict__ psi = J.psi;
+    const u32 idx = J.idx;
     __shared__ u32 lds[256 / WAVE + 1];
     u32 tot;
     u32 pre = block_excl_add<256>(hist[threadIdx.x], lds, tot);
@@ -101,16 +131,18 @@ __global__ void __launch_bounds__(256) k_ub_cum(const u32 * __restrict__ hist, u
     }
 }
 
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_flags(u32 rows, u32 idx, int log_stride, u32 * __restrict__ flags) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_flags(UbBatch b) {
+    const UbJob & J = b.job[blockIdx.y];
     const u32 r = blockIdx.x * UB_BLOCK + threadIdx.x;
-    if (r < rows) flags[r] = ub_is_splitter(r, idx, log_stride) ? 1u : 0u;
+    if (r < J.rows) J.sid[r] = ub_is_splitter(r, J.idx, J.log_stride) ? 1u : 0u;
 }
 
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_collect(u32 rows, u32 idx, int log_stride, const u32 * __restrict__ sid, u32 bound, u32 * __restrict__ split_row) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_collect(UbBatch b) {
+    const UbJob & J = b.job[blockIdx.y];
     const u32 r = blockIdx.x * UB_BLOCK + threadIdx.x;
-    if (r < rows && ub_is_splitter(r, idx, log_stride)) {
-        const u32 j = sid[r];
-        if (j < bound) split_row[j] = r;
+    if (r < J.rows && ub_is_splitter(r, J.idx, J.log_stride)) {
+        const u32 j = J.sid[r];
+        if (j < J.bound) J.split_row[j] = r;
     }
 }
 
@@ -132,10 +164,22 @@ __device__ __forceinline__ u32 ub_symbol_lds(const u32 * c, u32 r) {
 // segment length; the few longer segments leave the row they reached in `resume` and k_ub_walk_long finishes them).  Bytes are
 // collected four at a time: one store per four steps.  The segment length goes to seg_len as well as to dist: the jumping rounds turn
 // dist into the distance to the terminal, and k_ub_place needs both.
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_walk(const u32 * __restrict__ psi, const u32 * __restrict__ sid, const u32 * __restrict__ split_row,
-                                                     const u32 * __restrict__ d_total, u32 bound, u32 idx, int log_stride, u32 rows, const u32 * __restrict__ cum,
-                                                     u32 cap, u32 * __restrict__ succ, u32 * __restrict__ dist, u32 * __restrict__ seg_len, u8 * __restrict__ slab,
-                                                     u32 * __restrict__ resume) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_walk(UbBatch b) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u32 bound = J.bound;
+    if (blockIdx.x * UB_BLOCK >= bound) return;  // (the whole workgroup: before the barrier)
+    const u32 * __restrict__ psi = J.psi;
+    const u32 * __restrict__ sid = J.sid;
+    const u32 * __restrict__ split_row = J.split_row;
+    const u32 * __restrict__ d_total = J.d_total;
+    const u32 * __restrict__ cum = J.cum;
+    const u32 idx = J.idx, rows = J.rows, cap = J.cap;
+    const int log_stride = J.log_stride;
+    u32 * __restrict__ succ = J.succ[0];
+    u32 * __restrict__ dist = J.dist[0];
+    u32 * __restrict__ seg_len = J.seg_len;
+    u8 * __restrict__ slab = J.slab;
+    u32 * __restrict__ resume = J.resume;
     __shared__ u32 c[257];
     for (int k = threadIdx.x; k < 257; k += UB_BLOCK) c[k] = cum[k];
     __syncthreads();
@@ -170,11 +214,16 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_walk(const u32 * __restrict__ p
     seg_len[j] = len;
 }
 
-// One pointer-jumping round: dist = distance to the terminal, succ = 2^k-th successor.
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_jump(const u32 * __restrict__ succ_in, const u32 * __restrict__ dist_in, const u32 * __restrict__ d_total, u32 bound,
-                                                     u32 * __restrict__ succ_out, u32 * __restrict__ dist_out) {
+// One pointer-jumping round: dist = distance to the terminal, succ = 2^k-th successor.  cur: which of the two buffers holds the list (the same
+// for every job: all of them run every round of the longest list, and a round past a list's own need leaves it as it is).
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_jump(UbBatch b, int cur) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u32 * __restrict__ succ_in = J.succ[cur];
+    const u32 * __restrict__ dist_in = J.dist[cur];
+    u32 * __restrict__ succ_out = J.succ[cur ^ 1];
+    u32 * __restrict__ dist_out = J.dist[cur ^ 1];
     const u32 j = blockIdx.x * UB_BLOCK + threadIdx.x;
-    if (j >= ub_count(d_total, bound)) return;
+    if (j >= ub_count(J.d_total, J.bound)) return;
     const u32 sj = succ_in[j];
     u64 d = (u64)dist_in[j] + dist_in[sj];
     dist_out[j] = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)d;
@@ -183,9 +232,16 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_jump(const u32 * __restrict__ s
 
 // After the list ranking: the parked bytes of every segment go to their place.  16 lanes per segment, 16 bytes per lane and trip
 // (the slab is aligned, the destination is not: 128-bit stores at any byte address).  seg_len: the walk's segment lengths.
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_place(const u8 * __restrict__ slab, const u32 * __restrict__ seg_len, const u32 * __restrict__ dist,
-                                                      const u32 * __restrict__ succ, const u32 * __restrict__ sid, u32 idx, u32 cap,
-                                                      const u32 * __restrict__ d_total, u32 bound, u32 n, u8 * __restrict__ out) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_place(UbBatch b, int cur) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u8 * __restrict__ slab = J.slab;
+    const u32 * __restrict__ seg_len = J.seg_len;
+    const u32 * __restrict__ dist = J.dist[cur];
+    const u32 * __restrict__ succ = J.succ[cur];
+    const u32 * __restrict__ sid = J.sid;
+    const u32 * __restrict__ d_total = J.d_total;
+    const u32 idx = J.idx, cap = J.cap, bound = J.bound, n = J.n;
+    u8 * __restrict__ out = J.out;
     const u32 t = blockIdx.x * UB_BLOCK + threadIdx.x;
     const u32 j = t >> 4, part = t & 15u;
     if (j >= ub_count(d_total, bound)) return;
@@ -215,10 +271,20 @@ __global__ void __launch_bounds__(UB_BLOCK) k_ub_place(const u8 * __restrict__ s
 
 // The segments that did not fit their slab (longer than 4 x the mean: ~2 % of them, ~9 % of the rows) are walked on from the row
 // the first walk left in `resume`, their bytes going straight to their place.
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_walk_long(const u32 * __restrict__ psi, const u32 * __restrict__ resume, const u32 * __restrict__ seg_len,
-                                                          const u32 * __restrict__ dist, const u32 * __restrict__ succ, const u32 * __restrict__ sid, u32 idx,
-                                                          const u32 * __restrict__ cum, u32 cap, const u32 * __restrict__ d_total, u32 bound, u32 n,
-                                                          u8 * __restrict__ out) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_walk_long(UbBatch b, int cur) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u32 bound = J.bound;
+    if (blockIdx.x * UB_BLOCK >= bound) return;  // (the whole workgroup: before the barrier)
+    const u32 * __restrict__ psi = J.psi;
+    const u32 * __restrict__ resume = J.resume;
+    const u32 * __restrict__ seg_len = J.seg_len;
+    const u32 * __restrict__ dist = J.dist[cur];
+    const u32 * __restrict__ succ = J.succ[cur];
+    const u32 * __restrict__ sid = J.sid;
+    const u32 * __restrict__ cum = J.cum;
+    const u32 * __restrict__ d_total = J.d_total;
+    const u32 idx = J.idx, cap = J.cap, n = J.n;
+    u8 * __restrict__ out = J.out;
     __shared__ u32 c[257];
     for (int k = threadIdx.x; k < 257; k += UB_BLOCK) c[k] = cum[k];
     __syncthreads();
@@ -253,8 +319,15 @@ __device__ __forceinline__ u32 ub_first_symbol(const u32 * __restrict__ cum, u32
 
 // What the reference leaves behind the chain (nothing for a genuine BWT, where D = n), and U[n-1] = first BWT byte.
 // Rules and their derivation from include/libsais.h:4534-4636: oracle/bz3_oracle.c, orc_unbwt.
-__global__ void __launch_bounds__(UB_BLOCK) k_ub_tail(const u8 * __restrict__ in, const u32 * __restrict__ psi, const u32 * __restrict__ cum,
-                                                     const u32 * __restrict__ dist, const u32 * __restrict__ sid, u32 idx, u32 bound, u32 n, u8 * __restrict__ out) {
+__global__ void __launch_bounds__(UB_BLOCK) k_ub_tail(UbBatch b, int cur) {
+    const UbJob & J = b.job[blockIdx.y];
+    const u8 * __restrict__ in = J.in;
+    const u32 * __restrict__ psi = J.psi;
+    const u32 * __restrict__ cum = J.cum;
+    const u32 * __restrict__ dist = J.dist[cur];
+    const u32 * __restrict__ sid = J.sid;
+    const u32 idx = J.idx, bound = J.bound, n = J.n;
+    u8 * __restrict__ out = J.out;
     const u32 D = dist[ub_sid(sid, idx, bound)];
     const u32 limit = n & ~1u;
     const u32 lastc = in[0];
@@ -331,62 +404,136 @@ int unbwt_log_stride(u32 rows, u32 lanes) {
     return log_stride;
 }
 
+// What one job takes from the arena at a given stride, rounding of the allocator included.  At the strides the rule picks it stays under
+// unbwt_workspace_bytes; a stride forced below 8 rows (tests) needs more.
+static size_t ub_job_bytes(u64 n, int log_stride) {
+    const u64 rows = n + 1;
+    const u64 bound = ub_split_bound((u32)rows, log_stride);
+    return rows * 8 + radix_temp_bytes(n) + scan_temp_words(rows) * 4 + bound * 28 + bound * (4u << log_stride) + (1u << 16);
+}
+
+// How many of the first `count` jobs go into one pass: the largest b <= UB_MAX_BATCH for which b workspaces of the largest job fit into
+// `arena_free` bytes and b x (rows >> UB_MAX_LOG_STRIDE) lanes -- the fewest splitters the rule ever gives that job -- are lanes the stream
+// keeps resident.  A block of 256 MiB therefore goes alone, with the launch sequence of a single block; blocks of 8 MiB go four at a time.
+size_t unbwt_batch_workspace_bytes(u64 n, u32 b) {
+    size_t each = unbwt_workspace_bytes(n);
+    const int forced = g_ub_force_log_stride.load();
+    if (forced >= 0 && ub_job_bytes(n, forced) > each) each = ub_job_bytes(n, forced);
+    return each * b;
+}
+
+u32 unbwt_batch_size(const u32 * n, u32 count, size_t arena_free, u32 lanes) {
+    if (count <= 1) return count;
+    if (lanes == 0) lanes = ub_device_lanes();
+    u32 b = 1;
+    u64 largest = n[0];
+    while (b < count && b < UB_MAX_BATCH) {
+        const u64 big = n[b] > largest ? n[b] : largest;
+        if (unbwt_batch_workspace_bytes(big, b + 1) > arena_free || (u64)(b + 1) * ((big + 1) >> UB_MAX_LOG_STRIDE) > lanes) break;
+        largest = big;
+        b++;
+    }
+    return b;
+}
+
 // Nothing in here waits for the stream: the host sizes arrays and grids from ub_split_bound() instead of reading the splitter count back, and the
 // scratch goes back to the arena when the function returns, with its kernels still in flight.  That is sound because an arena belongs to one
 // stream at a time: whoever takes the same bytes next launches on `s` as well, so its kernels queue behind these -- the argument of
-// encode_front_b for the suffix sorter's scratch.  Both callers wait for the stream right after the call, for reasons of their own
-// (decode_unbwt: see there; bz3_hip_stage_unbwt reads the text back).
+// encode_front_b for the suffix sorter's scratch.  The callers wait for the stream right after the call, for reasons of their own
+// (decode_group: see there; the hooks read the text back).
+// A fixed launch sequence, whatever the data: `count` blocks go through it together, one launch per step.  Every item has n >= 2 and 0 < idx <= n.
+void bwt_inverse_batch(const UbBatchItem * items, u32 count, Arena & tmp, hipStream_t s, u32 lanes) {
+    if (count == 0) return;
+    if (count > UB_MAX_BATCH) throw HipError{hipErrorUnknown, "inverse BWT batch of more blocks than the job table holds", __FILE__, __LINE__};
+    const size_t mk = tmp.mark();
+    if (lanes == 0) lanes = ub_device_lanes();
+    UbBatch b;
+    b.count = count;
+    u32 * hists = tmp.take<u32>((size_t)256 * count);  // (one piece: one memset)
+    u32 most_n = 0, most_rows = 0, most_bound = 0;
+    RadixIotaJob rj[UB_MAX_BATCH];
+    u32 * sids[UB_MAX_BATCH];
+    u32 * totals[UB_MAX_BATCH];
+    u64 lens[UB_MAX_BATCH];
+    for (u32 k = 0; k < count; k++) {
+        UbJob & J = b.job[k];
+        if (items[k].n < 2) throw HipError{hipErrorUnknown, "inverse BWT batch with a block of fewer than 2 bytes", __FILE__, __LINE__};
+        J.in = items[k].in;
+        J.out = items[k].out;
+        J.n = items[k].n;
+        J.idx = items[k].idx;
+        J.rows = J.n + 1;
+        J.log_stride = unbwt_log_stride(J.rows, lanes);
+        J.bound = ub_split_bound(J.rows, J.log_stride);
+        J.cap = 4u << J.log_stride;  // bytes per slab: 4 x the mean segment length (splitters are one row in 2^log_stride)
+        J.psi = tmp.take<u32>(J.rows);
+        J.sid = tmp.take<u32>(J.rows);
+        J.hist = hists + (size_t)256 * k;
+        J.cum = tmp.take<u32>(257);
+        J.d_total = tmp.take<u32>(1);
+        most_n = J.n > most_n ? J.n : most_n;
+        most_rows = J.rows > most_rows ? J.rows : most_rows;
+        most_bound = J.bound > most_bound ? J.bound : most_bound;
+        rj[k] = RadixIotaJob{J.in, J.psi, J.n, J.idx};
+        sids[k] = J.sid;
+        totals[k] = J.d_total;
+        lens[k] = J.rows;
+    }
+    // 1. psi by one stable radix pass: value of byte k is its row k + (k >= idx), destination base 1
+    HIP_CHECK(hipMemsetAsync(hists, 0, (size_t)256 * 4 * count, s));
+    // (the entries past `count` repeat the first job until step 2 has filled the real ones: no uninitialised bytes in a kernel argument)
+    for (u32 k = 0; k < UB_MAX_BATCH; k++) {
+        UbJob & J = b.job[k];
+        if (k >= count) J = b.job[0];
+        J.split_row = J.seg_len = J.resume = J.succ[0] = J.succ[1] = J.dist[0] = J.dist[1] = nullptr;
+        J.slab = nullptr;
+    }
+    launch(k_ub_hist, dim3((u32)(((u64)most_n + UB_BLOCK * 64 - 1) / (UB_BLOCK * 64)), count), dim3(UB_BLOCK), 0, s, b);
+    launch(k_ub_cum, dim3(1, count), dim3(256), 0, s, b);
+    radix_pass_iota_u8_many(rj, count, 1u, tmp, s);
+
+    // 2. splitters: ids by a scan of the flags (the exact count stays in d_total), then THE walk
+    const dim3 grows((most_rows + UB_BLOCK - 1) / UB_BLOCK, count);
+    launch(k_ub_flags, grows, dim3(UB_BLOCK), 0, s, b);
+    exclusive_scan_u32_many(sids, lens, totals, count, tmp, s);
+    for (u32 k = 0; k < count; k++) {
+        UbJob & J = b.job[k];
+        J.split_row = tmp.take<u32>(J.bound);
+        J.seg_len = tmp.take<u32>(J.bound);
+        J.resume = tmp.take<u32>(J.bound);
+        J.succ[0] = tmp.take<u32>(J.bound);
+        J.succ[1] = tmp.take<u32>(J.bound);
+        J.dist[0] = tmp.take<u32>(J.bound);
+        J.dist[1] = tmp.take<u32>(J.bound);
+        J.slab = tmp.take<u8>((size_t)J.bound * J.cap + 64);
+    }
+    for (u32 k = count; k < UB_MAX_BATCH; k++) b.job[k] = b.job[0];
+    const dim3 gs((most_bound + UB_BLOCK - 1) / UB_BLOCK, count);
+    launch(k_ub_collect, grows, dim3(UB_BLOCK), 0, s, b);
+    launch(k_ub_walk, gs, dim3(UB_BLOCK), 0, s, b);
+
+    // 3. rank the splitter lists: 2^rounds >= the largest bound >= every list's length (the terminal points at itself with distance 0: further
+    // rounds change nothing, so a shorter list sits through the longest one's rounds unchanged)
+    int cur = 0;
+    for (u64 span = 1; span < most_bound; span <<= 1) {
+        launch(k_ub_jump, gs, dim3(UB_BLOCK), 0, s, b, cur);
+        cur ^= 1;
+    }
+    // 4. the parked bytes to their places, the long segments' rest straight there
+    launch(k_ub_place, dim3((u32)(((u64)most_bound * 16 + UB_BLOCK - 1) / UB_BLOCK), count), dim3(UB_BLOCK), 0, s, b, cur);
+    launch(k_ub_walk_long, gs, dim3(UB_BLOCK), 0, s, b, cur);
+    launch(k_ub_tail, dim3(256, count), dim3(UB_BLOCK), 0, s, b, cur);
+    tmp.release(mk);
+}
+
 void bwt_inverse(const u8 * d_in, u32 n, u32 idx, u8 * d_out, Arena & tmp, hipStream_t s, u32 lanes) {
     if (n == 0) return;
     if (n == 1) {
         HIP_CHECK(hipMemcpyAsync(d_out, d_in, 1, hipMemcpyDeviceToDevice, s));
         return;
     }
-    const size_t mk = tmp.mark();
-    const u32 rows = n + 1;
-    u32 * psi = tmp.take<u32>(rows);
-    u32 * sid = tmp.take<u32>(rows);
-    u32 * hist = tmp.take<u32>(256);
-    u32 * cum = tmp.take<u32>(257);
-    u32 * d_total = tmp.take<u32>(1);
-
-    // 1. psi by one stable radix pass: value of byte k is its row k + (k >= idx), destination base 1
-    HIP_CHECK(hipMemsetAsync(hist, 0, 256 * 4, s));
-    launch(k_ub_hist, dim3((u32)(((u64)n + UB_BLOCK * 64 - 1) / (UB_BLOCK * 64))), dim3(UB_BLOCK), 0, s, d_in, n, hist);
-    launch(k_ub_cum, dim3(1), dim3(256), 0, s, (const u32 *)hist, cum, psi, idx);
-    radix_pass<u8>(d_in, (u8 *)nullptr, (const u32 *)nullptr, psi, n, 0, idx, 1u, tmp, s);
-
-    // 2. splitters: ids by a scan of the flags (the exact count stays in d_total), then THE walk
-    const int log_stride = unbwt_log_stride(rows, lanes ? lanes : ub_device_lanes());
-    const u32 bound = ub_split_bound(rows, log_stride);
-    const dim3 grows((rows + UB_BLOCK - 1) / UB_BLOCK);
-    launch(k_ub_flags, grows, dim3(UB_BLOCK), 0, s, rows, idx, log_stride, sid);
-    exclusive_scan_u32(sid, rows, d_total, tmp, s);
-    u32 * split_row = tmp.take<u32>(bound);
-    u32 * seg_len = tmp.take<u32>(bound);
-    u32 * resume = tmp.take<u32>(bound);
-    u32 * succ[2] = {tmp.take<u32>(bound), tmp.take<u32>(bound)};
-    u32 * dist[2] = {tmp.take<u32>(bound), tmp.take<u32>(bound)};
-    const u32 cap = 4u << log_stride;  // bytes per slab: 4 x the mean segment length (splitters are one row in 2^log_stride)
-    u8 * slab = tmp.take<u8>((size_t)bound * cap + 64);
-    const dim3 gs((bound + UB_BLOCK - 1) / UB_BLOCK);
-    launch(k_ub_collect, grows, dim3(UB_BLOCK), 0, s, rows, idx, log_stride, (const u32 *)sid, bound, split_row);
-    launch(k_ub_walk, gs, dim3(UB_BLOCK), 0, s, (const u32 *)psi, (const u32 *)sid, (const u32 *)split_row, (const u32 *)d_total, bound, idx, log_stride, rows,
-           (const u32 *)cum, cap, succ[0], dist[0], seg_len, slab, resume);
-
-    // 3. rank the splitter list: 2^rounds >= bound >= its length (the terminal points at itself with distance 0: further rounds change nothing)
-    int cur = 0;
-    for (u64 span = 1; span < bound; span <<= 1) {
-        launch(k_ub_jump, gs, dim3(UB_BLOCK), 0, s, (const u32 *)succ[cur], (const u32 *)dist[cur], (const u32 *)d_total, bound, succ[cur ^ 1], dist[cur ^ 1]);
-        cur ^= 1;
-    }
-    // 4. the parked bytes to their places, the long segments' rest straight there
-    launch(k_ub_place, dim3((u32)(((u64)bound * 16 + UB_BLOCK - 1) / UB_BLOCK)), dim3(UB_BLOCK), 0, s, (const u8 *)slab, (const u32 *)seg_len, (const u32 *)dist[cur],
-           (const u32 *)succ[cur], (const u32 *)sid, idx, cap, (const u32 *)d_total, bound, n, d_out);
-    launch(k_ub_walk_long, gs, dim3(UB_BLOCK), 0, s, (const u32 *)psi, (const u32 *)resume, (const u32 *)seg_len, (const u32 *)dist[cur], (const u32 *)succ[cur],
-           (const u32 *)sid, idx, (const u32 *)cum, cap, (const u32 *)d_total, bound, n, d_out);
-    launch(k_ub_tail, dim3(256), dim3(UB_BLOCK), 0, s, d_in, (const u32 *)psi, (const u32 *)cum, (const u32 *)dist[cur], (const u32 *)sid, idx, bound, n, d_out);
-    tmp.release(mk);
+    const UbBatchItem one{d_in, d_out, n, idx};
+    bwt_inverse_batch(&one, 1, tmp, s, lanes);
 }
 
 }  // namespace bz3

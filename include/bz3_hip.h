@@ -407,7 +407,7 @@ enum {
     BZ3_HIP_T_CRC = 0,
     BZ3_HIP_T_RLE = 1,
     BZ3_HIP_T_LZP = 2,
-    BZ3_HIP_T_BWT = 3,
+    BZ3_HIP_T_BWT = 3,  /* decode: the inverse BWTs of a window run up to four blocks at a time; a block's value is its run's wall time / the run's blocks */
     BZ3_HIP_T_CM = 4,   /* CM kernel alone, measured with HIP events on the state's stream */
     BZ3_HIP_T_COPY = 5, /* host<->device and device<->device block copies */
     BZ3_HIP_T_COUNT = 8
@@ -436,6 +436,10 @@ BZIP3_API int32_t bz3_hip_debug_cu_masks(int cus, int reserve, uint32_t * side, 
 BZIP3_API int32_t bz3_hip_debug_scan_u32(uint32_t * data, uint32_t n, uint32_t * total);
 /* tests only: sort.hip's stable LSD radix sort of (keys[i], i) over key bits [0, key_bits), digits of 8 or 9 bits; returns the passes run */
 BZIP3_API int32_t bz3_hip_debug_sort_u32(const uint32_t * keys, uint32_t n, int key_bits, int digit_bits, uint32_t * sorted_keys, uint32_t * sorted_index);
+/* Tests and sweeps only: the inverse BWT of `count` blocks on host buffers in one call, through the batched pass of the decoder's tail in runs of
+ * at most four blocks, in the order given (blocks of fewer than 2 bytes are handled apart).  Synchronous.  0, or -1 if a block's (n, idx) is one
+ * libsais_unbwt refuses.  bz3_hip_stage_last_ms() then covers all runs of the call. */
+BZIP3_API int32_t bz3_hip_debug_unbwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, const int32_t * idx, int32_t count);
 BZIP3_API float bz3_hip_stage_last_ms(void); /* wall ms of the transform inside the last bz3_hip_stage_bwt / _unbwt call (allocations and PCIe copies excluded) */
 BZIP3_API int32_t bz3_hip_stage_cm_encode(const uint8_t * in, int32_t n, uint8_t * out);            /* encode_bytes    */
 BZIP3_API void bz3_hip_stage_cm_decode(const uint8_t * in, int32_t in_size, uint8_t * out, int32_t n); /* decode_bytes  */

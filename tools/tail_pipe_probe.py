@@ -3,7 +3,7 @@ inverse BWTs of the following windows and the mRLE / CRC stages of the preceding
 One batch of `blocks` text blocks of `MiB` each is encoded once on the GPU; the coded blocks are stashed in device memory and decoded
 again under every "window,slots" setting given (BZ3_HIP_TAIL_PIPE; "default" = what decode_group picks itself), `trials` times each.
 Prints t_dec, the CM launch and what is left (the tail) per trial.  No torch import: device memory through the HIP runtime directly.
-    python tools/tail_pipe_probe.py [MiB=8] [blocks=768] [--settings=default,8x8,4x8] [--trials=2] [--emu]
+    python tools/tail_pipe_probe.py [MiB=8] [blocks=768] [--settings=default,8x8,4x8] [--trials=2] [--lib=<another build>] [--emu]
 (--emu: the CPU emulator build and host memory -- checks the script, not the GPU.)"""
 import ctypes as C
 import json
@@ -94,7 +94,11 @@ def main():
         lib = bzip3_amd.load(build_emu())
         mem = HostMem()
     else:
-        lib = bzip3_amd.load()
+        if "lib" in opt:  # --lib=<another build>: same-box A/B of two code states, on the HIP runtime load() would pick
+            bzip3_amd._share_hip_runtime_with_torch()
+            lib = bzip3_amd.load(opt["lib"])
+        else:
+            lib = bzip3_amd.load()
         assert lib.bz3_hip_device_count() > 0
         mem = HipMem()
     lib.bz3_hip_bind_device(0)
