@@ -115,6 +115,7 @@ def _declare(L, strict=True):
         "bz3_hip_stage_mrle_decode": (C.c_int, [vp, vp, i32, i32]),
         "bz3_hip_stage_lzp_encode": (i32, [vp, i32, vp]),
         "bz3_hip_stage_lzp_decode": (i32, [vp, i32, vp, i32]),
+        "bz3_hip_debug_lzp_encode": (i32, [vp, i32, vp, vp]),
         "bz3_hip_stage_bwt": (i32, [vp, vp, i32]),
         "bz3_hip_stage_unbwt": (i32, [vp, vp, i32, i32]),
         "bz3_hip_debug_unbwt_many": (i32, [vp, vp, vp, vp, i32]),
@@ -216,6 +217,14 @@ class StageApi:
         out = (C.c_uint8 * (len(data) + 64))()
         n = self.lib.bz3_hip_stage_lzp_encode(_cbuf(data, len(data)), len(data), out)
         return n, (C.string_at(out, n) if n > 0 else b"")
+
+    def lzp_encode_stats(self, data):
+        """lzp_encode plus the driver's record (bz3_hip_debug_lzp_encode): (n, bytes, dict)."""
+        out = (C.c_uint8 * (len(data) + 64))()
+        st = (C.c_uint32 * 6)()
+        n = self.lib.bz3_hip_debug_lzp_encode(_cbuf(data, len(data)), len(data), out, st)
+        keys = ("end_pos", "n_matches", "iterations", "evaluated", "event_cap", "window_positions")
+        return n, (C.string_at(out, n) if n > 0 else b""), dict(zip(keys, (int(x) for x in st)))
 
     def lzp_decode(self, data, maxout):
         out = (C.c_uint8 * max(8, maxout))()

@@ -114,6 +114,27 @@ BZIP3_API int32_t bz3_hip_stage_lzp_encode(const uint8_t * in, int32_t n, uint8_
     });
 }
 
+// Tests only: bz3_hip_stage_lzp_encode plus what the serial driver did (lzp.hip k_lzp_driver, LzDriverOut) and its two constants.
+BZIP3_API int32_t bz3_hip_debug_lzp_encode(const uint8_t * in, int32_t n, uint8_t * out, uint32_t stats[6]) {
+    return stage_guard([&]() -> s32 {
+        StageEnv e;
+        u8 * d = e.dev((size_t)n + 64, in, (size_t)n);
+        u8 * o = e.dev((size_t)n + 64);
+        Arena a = e.ctx->arena_for(workspace_bytes_for((u64)n + 64));
+        LzDriverOut drv;
+        const s32 r = lzp_encode(d, (u32)n, o, a, e.s, &drv);
+        if (r > 0) e.down(out, o, (size_t)r);
+        if (stats) {
+            stats[0] = drv.end_pos;
+            stats[1] = drv.n_matches;
+            stats[2] = drv.iterations;
+            stats[3] = drv.evaluated;
+            lzp_driver_geometry(stats[4], stats[5]);
+        }
+        return r;
+    });
+}
+
 BZIP3_API int32_t bz3_hip_stage_lzp_decode(const uint8_t * in, int32_t n, uint8_t * out, int32_t max) {
     return stage_guard([&]() -> s32 {
         StageEnv e;

@@ -417,6 +417,9 @@ __global__ void __launch_bounds__(LZ_DRV) k_lzp_driver(const LzpDriverJob * __re
                 }
             }
             __syncthreads();
+            // (heur has not been observable in the output: the :145 gate only saves work on positions that would fail at 40 anyway, a position that
+            //  starts a true 40-byte match passes it, and one that does not emits nothing either way -- resetting heur every iteration, or dropping
+            //  the gate, changed no byte on any input of the suite.  It is kept as the reference has it; no test pins it.)
             if (tid == 0) {  // one lane; masks only, no memory traffic
                 u32 heur = s_heur;
                 u32 accept = 0xFFFFFFFFu;
@@ -674,20 +677,30 @@ s32 lzp_encode_finish(const LzpEncodeCtx & c, u8 * d_out, Arena & tmp, hipStream
     return result;
 }
 
-// One block, start to finish (stage hook).
-s32 lzp_encode(const u8 * d_in, u32 n, u8 * d_out, Arena & tmp, hipStream_t s) {
+// One block, start to finish (stage hook).  h_drv (tests): receives the driver's result record, zeroes where LZP declines for size.
+s32 lzp_encode(const u8 * d_in, u32 n, u8 * d_out, Arena & tmp, hipStream_t s, LzDriverOut * h_drv) {
     const size_t mk = tmp.mark();
     LzpEncodeCtx c;
     lzp_encode_prepare(d_in, n, c, tmp, s);
     s32 r = -1;
+    if (h_drv) *h_drv = LzDriverOut{0u, 0u, 0u, 0u};
     if (c.active) {
         LzpDriverJob job = lzp_driver_job(c);
         LzpDriverJob * d_job = tmp.take<LzpDriverJob>(1);
         lzp_driver_batch(&job, d_job, 1, s);
         r = lzp_encode_finish(c, d_out, tmp, s);
+        if (h_drv) {  // (the context stays in the arena until the release below)
+            HIP_CHECK(hipMemcpyAsync(h_drv, c.d_res, sizeof *h_drv, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
     }
     tmp.release(mk);
     return r;
+}
+
+void lzp_driver_geometry(u32 & event_cap, u32 & window_positions) {
+    event_cap = (u32)LZ_EV_CAP;
+    window_positions = (u32)LZ_WIN_WORDS * 32u;
 }
 
 // ---- decode -------------------------------------------------------------------------------------

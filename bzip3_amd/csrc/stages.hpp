@@ -74,7 +74,8 @@ void lzp_encode_prepare(const u8 * d_in, u32 n, LzpEncodeCtx & c, Arena & ctx, A
 LzpDriverJob lzp_driver_job(const LzpEncodeCtx & c);
 void lzp_driver_batch(const LzpDriverJob * h_jobs, LzpDriverJob * d_jobs, u32 njobs, hipStream_t s);
 s32 lzp_encode_finish(const LzpEncodeCtx & c, u8 * d_out, Arena & tmp, hipStream_t s);  // encoded size or -1
-s32 lzp_encode(const u8 * d_in, u32 n, u8 * d_out, Arena & tmp, hipStream_t s);         // one block, all three phases
+s32 lzp_encode(const u8 * d_in, u32 n, u8 * d_out, Arena & tmp, hipStream_t s, LzDriverOut * h_drv = nullptr);  // one block, all three phases
+void lzp_driver_geometry(u32 & event_cap, u32 & window_positions);  // tests: events resolved per driver iteration, positions per bitmap window
 // Decode: one workgroup per block, so a batch of blocks decodes concurrently (one launch, grid = jobs).
 struct LzpDecodeJob {  // device addresses as integers: see prims.hpp global_ptr()
     u64 in;

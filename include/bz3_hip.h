@@ -428,6 +428,10 @@ BZIP3_API int32_t bz3_hip_stage_mrle_encode(const uint8_t * in, int32_t n, uint8
 BZIP3_API int bz3_hip_stage_mrle_decode(const uint8_t * in, uint8_t * out, int32_t outlen, int32_t maxin); /* mrled    */
 BZIP3_API int32_t bz3_hip_stage_lzp_encode(const uint8_t * in, int32_t n, uint8_t * out);           /* lzp_compress    */
 BZIP3_API int32_t bz3_hip_stage_lzp_decode(const uint8_t * in, int32_t n, uint8_t * out, int32_t max); /* lzp_decompress */
+/* tests only: bz3_hip_stage_lzp_encode, and in stats what the encoder's serial driver did: [0] the position it stopped at (>= n - 72), [1] matches taken,
+ * [2] loop iterations, [3] flagged positions resolved (all zero where n < 72), then its constants: [4] events resolved per iteration, [5] positions per
+ * bitmap window.  Output bytes are those of the stage hook. */
+BZIP3_API int32_t bz3_hip_debug_lzp_encode(const uint8_t * in, int32_t n, uint8_t * out, uint32_t stats[6]);
 BZIP3_API int32_t bz3_hip_stage_bwt(const uint8_t * in, uint8_t * out, int32_t n);                  /* libsais_bwt     */
 BZIP3_API int32_t bz3_hip_stage_unbwt(const uint8_t * in, uint8_t * out, int32_t n, int32_t idx);   /* libsais_unbwt   */
 /* tests only: the two CU masks of the decoder's partition (side streams / everything else) for `cus` CUs of which `reserve` are set aside; returns the words per mask */

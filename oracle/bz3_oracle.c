@@ -154,7 +154,9 @@ static u32 lzp_slot(const u8 * at) { /* hash of the 4 bytes preceding `at` */
 /* LZP encoder.  Restates lzp_compress -> lzp_encode_block (src/libbz3.c:243-249, :124-198).
  * `out` needs n + 16 bytes.  Returns the encoded size, or -1 when n < 72 or when the output
  * reaches n - 8 bytes (:128, :197). */
-ORC_API s32 orc_lzp_encode(const u8 * in, s32 n, u8 * out) {
+static s32 lzp_encode_core(const u8 * in, s32 n, u8 * out, s32 * mpos, s32 * mlen, s32 mcap, s32 * mcount) {
+    s32 nm = 0;
+    if (mcount) *mcount = 0;
     if (n < ORC_LZP_MIN + 32) return -1;
     s32 * tab = (s32 *)calloc((size_t)1 << ORC_LZP_BITS, sizeof(s32));
     if (!tab) return -1;
@@ -178,6 +180,8 @@ ORC_API s32 orc_lzp_encode(const u8 * in, s32 n, u8 * out) {
                     len += in[ip + len] == in[cand + len]; /* :157-159 */
                     len += in[ip + len] == in[cand + len];
                     len += in[ip + len] == in[cand + len];
+                    if (nm < mcap) { mpos[nm] = ip; mlen[nm] = len; }
+                    nm++;
                     ip += len;
                     out[op++] = ORC_LZP_ESC;
                     len -= ORC_LZP_MIN;
@@ -206,7 +210,22 @@ ORC_API s32 orc_lzp_encode(const u8 * in, s32 n, u8 * out) {
         if (b == ORC_LZP_ESC && cand > 0) out[op++] = 255;
     }
     free(tab);
+    if (mcount) *mcount = nm;
     return op >= out_lim ? -1 : op;
+}
+
+ORC_API s32 orc_lzp_encode(const u8 * in, s32 n, u8 * out) { return lzp_encode_core(in, n, out, NULL, NULL, 0, NULL); }
+
+/* The match list of the encoder above (the same loop): start and length of every match it takes, in order; the first `cap` are
+ * stored.  Returns their number (also when the encoder gives up for size: the matches taken until then), or -1 when n < 72. */
+ORC_API s32 orc_lzp_matches(const u8 * in, s32 n, s32 * pos, s32 * len, s32 cap) {
+    if (n < ORC_LZP_MIN + 32) return -1;
+    u8 * out = (u8 *)malloc((size_t)n + 16);
+    if (!out) return -1;
+    s32 nm = 0;
+    (void)lzp_encode_core(in, n, out, pos, len, cap < 0 ? 0 : cap, &nm);
+    free(out);
+    return nm;
 }
 
 /* LZP decoder.  Restates lzp_decompress -> lzp_decode_block (src/libbz3.c:251-257, :200-241).

@@ -46,6 +46,8 @@ class Oracle:
         L.orc_lzp_encode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.orc_lzp_decode.restype = C.c_int32
         L.orc_lzp_decode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.orc_lzp_matches.restype = C.c_int32
+        L.orc_lzp_matches.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         L.orc_bwt.restype = C.c_int32
         L.orc_bwt.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.orc_unbwt.restype = C.c_int32
@@ -80,6 +82,14 @@ class Oracle:
         out = (C.c_uint8 * (len(data) + 64))()
         n = self.lib.orc_lzp_encode(_buf(data), len(data), out)
         return n, (C.string_at(out, n) if n > 0 else b"")
+
+    def lzp_matches(self, data):
+        """[(start, length)] of every match the oracle's encoder takes, in order ([] where LZP declines for n < 72)."""
+        cap = len(data) // 40 + 2
+        pos, ln = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+        k = self.lib.orc_lzp_matches(_buf(data), len(data), pos, ln, cap)
+        assert k <= cap
+        return [(pos[i], ln[i]) for i in range(max(k, 0))]
 
     def lzp_decode(self, data, maxout):
         out = (C.c_uint8 * max(8, maxout))()
