@@ -119,6 +119,8 @@ def _declare(L, strict=True):
         "bz3_hip_stage_bwt": (i32, [vp, vp, i32]),
         "bz3_hip_stage_unbwt": (i32, [vp, vp, i32, i32]),
         "bz3_hip_debug_unbwt_many": (i32, [vp, vp, vp, vp, i32]),
+        "bz3_hip_debug_bwt_many": (i32, [vp, vp, vp, vp, i32]),
+        "bz3_hip_debug_set_bwt_batch": (None, [C.c_int]),
         "bz3_hip_stage_last_ms": (C.c_float, []),
         "bz3_hip_debug_sort_u32": (i32, [vp, u32, C.c_int, C.c_int, vp, vp]),
         "bz3_hip_debug_scan_u32": (i32, [vp, u32, vp]),
@@ -240,6 +242,18 @@ class StageApi:
         out = (C.c_uint8 * max(1, len(data)))()
         rc = self.lib.bz3_hip_stage_unbwt(_cbuf(data, len(data)), out, len(data), idx)
         return rc, C.string_at(out, len(data))
+
+    def bwt_many(self, blocks):
+        """blocks: bytes objects, through the batched forward BWT in runs of at most four in the order given.  (rc, [(index, bytes), ...])."""
+        k = len(blocks)
+        ins = [_cbuf(d, len(d)) for d in blocks]
+        outs = [(C.c_uint8 * max(1, len(d)))() for d in blocks]
+        inp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in ins])
+        outp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in outs])
+        n = (C.c_int32 * max(1, k))(*[len(d) for d in blocks])
+        idx = (C.c_int32 * max(1, k))()
+        rc = self.lib.bz3_hip_debug_bwt_many(inp, outp, n, idx, k)
+        return rc, [(int(i), C.string_at(o, len(d))) for i, o, d in zip(idx, outs, blocks)]
 
     def unbwt_many(self, jobs):
         """jobs: (bytes, index) pairs, through the batched inverse BWT in runs of at most four in the order given.  (rc, [bytes, ...])."""

@@ -94,9 +94,12 @@ void encode_front_a(bz3_state * st, u8 * buf, s32 data_size, Arena & arena, Aren
     st->pending = bz3_state::ENC_CODED;
 }
 
-// Phase 1b (after the LZP drivers of the window have run): LZP emission, BWT, header.
-void encode_front_b(bz3_state * st, Arena & arena, const LzpEncodeCtx & c, float driver_ms) {
-    if (st->pending != bz3_state::ENC_CODED) return;
+// Phase 1b (after the LZP drivers of the window have run) comes in two halves around the transform, so that the blocks of a window can go
+// through the suffix sorter in runs (bwt_forward_batch).  First half: LZP emission and the choice of the transform's buffers.  Returns false
+// for a block that is not in the pipeline (stored, failed, skipped); otherwise `item` describes its transform and `copy_to` is where the
+// output has to be copied afterwards (lean state whose input sits in the caller's buffer; nullptr otherwise).
+bool encode_front_b_collect(bz3_state * st, Arena & arena, const LzpEncodeCtx & c, float driver_ms, BwtBatchItem & item, u8 *& copy_to) {
+    if (st->pending != bz3_state::ENC_CODED) return false;
     st->pending = bz3_state::FAILED;
     hipStream_t s = st->xs;
     u8 *b1 = st->b1, *b2 = st->b2;
@@ -111,32 +114,70 @@ void encode_front_b(bz3_state * st, Arena & arena, const LzpEncodeCtx & c, float
     st->lzp_size = lzp_size;
     st->t[BZ3_HIP_T_LZP] += driver_ms + (float)(now_ms() - t0);
 
-    t0 = now_ms();
     u32 * const d_idx = st->d_words + 6;  // the primary index never visits the host
     u32 * const d_out8 = st->d_words + 8;  // bytes outside the block's 40 most frequent values: decides the CM kernel variant (run_cm_jobs)
+    copy_to = nullptr;
     if (!st->lean) {
-        (void)bwt_forward(b1, n, b2, arena, s, &st->bwt, d_idx, d_out8);  // :623-627
+        item = BwtBatchItem{b1, n, b2, d_idx, d_out8, &st->bwt, 0};  // :623-627
     } else {
         // Lean state: the coder will work IN PLACE in the caller's buffer (capacity bz3_bound(size), libbz3.h:172-174):
         // the BWT output goes to the END of that buffer, the coded bytes grow from its start (cm.hip CmSink).
         u8 * tail = st->user + bz3_bound((size_t)st->size) - n;
         if (b1 != st->user) {
-            (void)bwt_forward(b1, n, tail, arena, s, &st->bwt, d_idx, d_out8);
+            item = BwtBatchItem{b1, n, tail, d_idx, d_out8, &st->bwt, 0};
         } else {
-            (void)bwt_forward(b1, n, b2, arena, s, &st->bwt, d_idx, d_out8);
-            HIP_CHECK(hipMemcpyAsync(tail, b2, n, hipMemcpyDeviceToDevice, s));
+            item = BwtBatchItem{b1, n, b2, d_idx, d_out8, &st->bwt, 0};
+            copy_to = tail;
         }
-        b1 = st->user;  // receives header + coded bytes
-        b2 = tail;      // CM input
     }
-    if (st->timed) {
-        HIP_CHECK(hipStreamSynchronize(s));
-        st->t[BZ3_HIP_T_BWT] = (float)(now_ms() - t0);
+    st->b1 = b1;
+    st->b2 = b2;
+    st->n_cm = n;
+    return true;
+}
+
+// The transforms of the collected blocks, in runs of bwt_batch_size's choosing.  A timed block's BWT figure is its run's wall time divided by the
+// run's blocks (as the inverse transform's figure on the decode side); timing a run means waiting for the stream.
+void encode_front_b_transform(bz3_state * const * owners, BwtBatchItem * items, size_t count, Arena & arena, hipStream_t s) {
+    std::vector<u32> sizes(count);
+    for (size_t k = 0; k < count; k++) sizes[k] = items[k].n;
+    for (size_t at = 0; at < count;) {
+        const double t0 = now_ms();
+        u32 b = 1;
+        if (items[at].n < 2) {  // (never part of a batch)
+            (void)bwt_forward(items[at].in, items[at].n, items[at].out, arena, s, items[at].stats, items[at].d_idx, items[at].d_outside);
+        } else {
+            u32 avail = 0;
+            while (at + avail < count && avail < BWT_MAX_BATCH && items[at + avail].n >= 2) avail++;
+            b = bwt_batch_size(sizes.data() + at, avail, arena.cap - arena.used);
+            bwt_forward_batch(items + at, b, arena, s);
+        }
+        bool timed = false;
+        for (u32 k = 0; k < b; k++) timed = timed || owners[at + k]->timed;
+        if (timed) {
+            HIP_CHECK(hipStreamSynchronize(s));
+            const float each = (float)(now_ms() - t0) / (float)b;
+            for (u32 k = 0; k < b; k++)
+                if (owners[at + k]->timed) owners[at + k]->t[BZ3_HIP_T_BWT] = each;
+        }
+        at += b;
+    }
+}
+
+// Second half, per block in block order: the copy a lean state may need, the header, the swap buffer's way back.
+void encode_front_b_header(bz3_state * st, const BwtBatchItem & item, u8 * copy_to) {
+    hipStream_t s = st->xs;
+    u8 *b1 = st->b1, *b2 = st->b2;
+    const u32 n = st->n_cm;
+    if (st->lean) {
+        if (copy_to) HIP_CHECK(hipMemcpyAsync(copy_to, b2, n, hipMemcpyDeviceToDevice, s));
+        b2 = copy_to ? copy_to : item.out;  // CM input: the end of the caller's buffer
+        b1 = st->user;                      // receives header + coded bytes
     }
     s32 overhead = 2;  // :630-632
     if (st->model & 2) overhead++;
     if (st->model & 4) overhead++;
-    launch(k_write_header, dim3(1), dim3(64), 0, s, b1, (const u32 *)(st->d_words + 1), (const u32 *)d_idx, (u32)st->model, (u32)lzp_size, (u32)st->rle_size);  // :641-647
+    launch(k_write_header, dim3(1), dim3(64), 0, s, b1, (const u32 *)(st->d_words + 1), (const u32 *)item.d_idx, (u32)st->model, (u32)st->lzp_size, (u32)st->rle_size);  // :641-647
     // The swap buffer goes back to the pool.  Whoever borrows it next is a later block of this group -- the group holds the device's
     // mutex for the whole call and every kernel that touches the buffer, this block's and the next borrower's, is launched on the group's
     // ONE stream (the side streams only run LZP drivers, behind events recorded on it) --, so stream order is what protects it; rounds 1-3
@@ -144,7 +185,6 @@ void encode_front_b(bz3_state * st, Arena & arena, const LzpEncodeCtx & c, float
     if (st->lean && !st->hold_swap) lean_return(st);
     st->b1 = b1;
     st->b2 = b2;
-    st->n_cm = n;
     st->overhead = overhead;
     st->pending = bz3_state::ENC_CODED;
 }
@@ -252,7 +292,16 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
     // ends (below): the decode call that follows needs the room for staged payloads and the swap buffers of its tail windows.
     const size_t headroom = ws_headroom();
     const size_t fixed = (size_t)n * (sizeof(CmEncodeJob) + CM_SIDE_BYTES + 256) + cm_scratch_bytes((size_t)n) + 65536 + (size_t)DeviceCtx::AUX * 8 * (sizeof(LzpDriverJob) + 256);
-    size_t contexts = ((size_t)32 << 30) / ctx_bytes;
+    // The suffix sorter takes the blocks of a window in runs (bwt_forward_batch): the workspaces of a run's other blocks come on top of `need`,
+    // only for block sizes at which bwt_batch_size grants a run at all, and only beside the ring: where memory is short enough for them to cost
+    // an LZP context or the headroom, they are not taken, and bwt_batch_size finds room for one block at a time.
+    size_t bwt_extra = 0;
+    if (n > 1) {
+        const u32 sz[BWT_MAX_BATCH] = {(u32)n_max, (u32)n_max, (u32)n_max, (u32)n_max};
+        const u32 b = bwt_batch_size(sz, (u32)(n < (s32)BWT_MAX_BATCH ? n : (s32)BWT_MAX_BATCH), ~(size_t)0);
+        bwt_extra = (size_t)(b - 1) * bwt_workspace_bytes(n_max + 64);
+    }
+    size_t contexts = ((size_t)32 << 30) / ctx_bytes, contexts_beside_runs = contexts;
     {
         // Swap buffers the previous call left idle in the pool (a decode call's tail ring holds up to 4 x 16 of them, 17 GB at 256 MiB)
         // are memory this call's ring of LZP contexts cannot use: round 4's full-size run had a ring of 4 x 4 contexts and an encode
@@ -264,11 +313,15 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
         if (lead->lean && lead->ctx->temp_idle_bytes() > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             if (ring_contexts_for(free_b, lead->ctx->ws_cap, need, fixed, ctx_bytes, lead->cap, true, headroom) < (size_t)(n < full ? n : full)) lead->ctx->temp_trim();
         }
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             contexts = ring_contexts_for(free_b, lead->ctx->ws_cap, need, fixed, ctx_bytes, lead->cap, lead->lean, headroom);
+            contexts_beside_runs = ring_contexts_for(free_b, lead->ctx->ws_cap, need + bwt_extra, fixed, ctx_bytes, lead->cap, lead->lean, headroom);
+        }
     }
     s32 window = 1, ns = 2;
     pipeline_shape((s32)(contexts < 1024 ? contexts : 1024), n, window, ns);
+    // granted only where the ring as shaped above still fits beside them: then ring, runs and headroom all lie inside what ring_contexts_for counted
+    if (contexts_beside_runs < (size_t)ns * (size_t)window) bwt_extra = 0;
     lead->ctx->ensure_aux();
     hipStream_t s = lead->stream;
     DrainOnUnwind drain{s, lead->ctx->aux, DeviceCtx::AUX};
@@ -282,13 +335,14 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
     Arena arena;
     for (;;) {  // hipMemGetInfo's figure is not a promise (fragmentation, another process on the device): shrink the ring before giving up
         try {
-            arena = lead->ctx->arena_for(need + (size_t)ns * (size_t)window * (ctx_bytes + sizeof(LzpDriverJob) + 256) +
+            arena = lead->ctx->arena_for(need + bwt_extra + (size_t)ns * (size_t)window * (ctx_bytes + sizeof(LzpDriverJob) + 256) +
                                          (size_t)n * (sizeof(CmEncodeJob) + CM_SIDE_BYTES + 256) + cm_scratch_bytes((size_t)n) + 65536);
             break;
         } catch (const HipError &) {  // out of memory, or whatever else the runtime answers to a size it does not like
-            if (ns == 2 && window == 1) throw;
+            if (ns == 2 && window == 1 && bwt_extra == 0) throw;
             (void)hipGetLastError();
-            if (ns > 2) ns = 2;
+            if (bwt_extra) bwt_extra = 0;  // the sorter's runs go first (bwt_batch_size then finds room for one block at a time): never an LZP context
+            else if (ns > 2) ns = 2;
             else window = (window + 1) / 2;
         }
     }
@@ -309,6 +363,10 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
     }
     std::vector<CmEncodeJob> jobs;
     std::vector<s32> job_owner;
+    std::vector<BwtBatchItem> fb_items;  // phase B of one window: the blocks that reach the transform ...
+    std::vector<bz3_state *> fb_owner;   // ... their states ...
+    std::vector<u8 *> fb_copy;           // ... where a lean state's output goes afterwards ...
+    std::vector<s32> fb_slot;            // ... and a block's place among them (-1: it left the pipeline before)
     const s32 nwin = (n + window - 1) / window;
     const s32 lag = ns - 1;  // window k is finished in iteration k + lag
     static const bool trace_rings = getenv("BZ3_HIP_TRACE_RINGS") != nullptr;  // (diagnosis, read once: see decode_group)
@@ -349,11 +407,31 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
             (void)hipEventElapsedTime(&driver_ms, lead->ctx->ev_d0[q], lead->ctx->ev_d1[q]);
             tr_wait += now_ms() - t0;
         }
+        // the window's blocks first all go through the LZP emission and the buffer choice, then through the suffix sorter in runs of up to
+        // BWT_MAX_BATCH; header, swap buffer and CM job follow per block, in block order
+        fb_items.clear();
+        fb_owner.clear();
+        fb_copy.clear();
+        fb_slot.assign((size_t)(w.w1 - w.w0), -1);
         for (s32 i = w.w0; i < w.w1; i++) {
             sts[i]->xs = sf;
-            sts[i]->hold_swap = held != nullptr;
-            encode_front_b(sts[i], scr, w.ctxs[(size_t)(i - w.w0)], driver_ms);
-            sts[i]->hold_swap = false;
+            BwtBatchItem item{};
+            u8 * copy_to = nullptr;
+            if (encode_front_b_collect(sts[i], scr, w.ctxs[(size_t)(i - w.w0)], driver_ms, item, copy_to)) {
+                fb_slot[(size_t)(i - w.w0)] = (s32)fb_items.size();
+                fb_items.push_back(item);
+                fb_owner.push_back(sts[i]);
+                fb_copy.push_back(copy_to);
+            }
+        }
+        encode_front_b_transform(fb_owner.data(), fb_items.data(), fb_items.size(), scr, sf);
+        for (s32 i = w.w0; i < w.w1; i++) {
+            const s32 slot = fb_slot[(size_t)(i - w.w0)];
+            if (slot >= 0) {
+                sts[i]->hold_swap = held != nullptr;
+                encode_front_b_header(sts[i], fb_items[(size_t)slot], fb_copy[(size_t)slot]);
+                sts[i]->hold_swap = false;
+            }
             if (sts[i]->pending == bz3_state::ENC_CODED) {
                 CmEncodeJob j2{dev_addr(sts[i]->b2), dev_addr(sts[i]->b1 + sts[i]->overhead * 4 + 1), dev_addr(sts[i]->d_words + 2), sts[i]->n_cm, 0u};  // :634-638
                 if (sts[i]->lean) {  // in place: input at the end of the caller's buffer, output behind the header

@@ -172,6 +172,51 @@ BZIP3_API int32_t bz3_hip_stage_bwt(const uint8_t * in, uint8_t * out, int32_t n
     });
 }
 
+// Tests and sweeps only: the forward BWT of `count` blocks on host buffers, through bwt_forward_batch in runs of at most BWT_MAX_BATCH in the
+// order given (blocks of fewer than 2 bytes apart) -- the forward twin of bz3_hip_debug_unbwt_many.  Synchronous.  The arena is sized for a
+// full run of the largest block; how long a run is, is bwt_batch_size's decision (bz3_hip_debug_set_bwt_batch forces it).  idx_out[k] receives
+// block k's primary index (0 for an empty block, 1 for one byte).  Returns 0, or -1 on bad arguments.
+BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count) {
+    return stage_guard([&]() -> s32 {
+        if (count < 0 || (count > 0 && (!in || !out || !n || !idx_out))) return -1;
+        u64 largest = 0;
+        for (s32 k = 0; k < count; k++) {
+            if (n[k] < 0) return -1;
+            if ((u64)n[k] > largest) largest = (u64)n[k];
+        }
+        std::vector<BwtBatchItem> items;
+        std::vector<u32> sizes;
+        std::vector<s32> owner;
+        StageEnv e;
+        for (s32 k = 0; k < count; k++) {
+            idx_out[k] = n[k];  // (n < 2: the block is its own transform)
+            if (n[k] == 1) out[k][0] = in[k][0];
+            if (n[k] < 2) continue;
+            const u8 * d = e.dev((size_t)n[k] + 64, in[k], (size_t)n[k]);
+            items.push_back(BwtBatchItem{d, (u32)n[k], e.dev((size_t)n[k] + 64), nullptr, nullptr, nullptr, 0});
+            sizes.push_back((u32)n[k]);
+            owner.push_back(k);
+        }
+        if (items.empty()) return 0;
+        const size_t plain = workspace_bytes_for(largest + 64), full = (size_t)BWT_MAX_BATCH * bwt_workspace_bytes(largest + 64);
+        Arena a = e.ctx->arena_for(plain > full ? plain : full);
+        HIP_CHECK(hipStreamSynchronize(e.s));
+        const auto t0 = std::chrono::steady_clock::now();
+        for (size_t at = 0; at < items.size();) {
+            const u32 b = bwt_batch_size(sizes.data() + at, (u32)(items.size() - at), a.cap - a.used);
+            bwt_forward_batch(items.data() + at, b, a, e.s);
+            at += b;
+        }
+        g_stage_ms.store(std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        for (size_t j = 0; j < items.size(); j++) {
+            e.down(out[owner[j]], items[j].out, (size_t)items[j].n);
+            idx_out[owner[j]] = items[j].idx;
+        }
+        return 0;
+    });
+}
+BZIP3_API void bz3_hip_debug_set_bwt_batch(int b) { bwt_set_batch(b); }
+
 BZIP3_API int32_t bz3_hip_stage_unbwt(const uint8_t * in, uint8_t * out, int32_t n, int32_t idx) {
     return stage_guard([&]() -> s32 {
         if (n < 0) return -1;

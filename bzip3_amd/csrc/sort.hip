@@ -364,6 +364,44 @@ __global__ void __launch_bounds__(RS_BLOCK) k_rs_scatter_many(RsBatch8 b, int sh
 #include "sort_scatter_body.hpp"  // (k_rs_scatter's body, on the names declared above)
 }
 
+// The same for the forward sorter's passes: 4- or 8-byte keys that are written out, values generated (IOTA) or read, every array with its own
+// digit position (the suffix sorter's jobs differ in how many key bits they have).
+template <typename K>
+struct RsBatchKV {
+    struct Job {
+        const K * kin;
+        K * kout;
+        const u32 * vin;  // unused by the IOTA form
+        u32 * vout;
+        u32 * hist;
+        u64 n;  // >= 1
+        u32 tiles;
+        int shift;
+    } job[SORT_MAX_BATCH];
+};
+template <typename K>
+__global__ void __launch_bounds__(RS_BLOCK) k_rs_hist_kv_many(RsBatchKV<K> b, u32 xcd) {
+    const typename RsBatchKV<K>::Job & j = b.job[blockIdx.y];
+    if (blockIdx.x >= rs_grid(j.tiles, xcd != 0u)) return;
+    rs_hist_body<K, 8>(j.kin, j.n, j.shift, j.hist, j.tiles, xcd, blockIdx.x);
+}
+template <typename K, bool IOTA, bool RAW>
+__global__ void __launch_bounds__(RS_BLOCK) k_rs_scatter_kv_many(RsBatchKV<K> b, u32 xcd) {
+    constexpr bool WKEYS = true;
+    constexpr int BITS = 8;
+    const typename RsBatchKV<K>::Job & j = b.job[blockIdx.y];
+    if (blockIdx.x >= rs_grid(j.tiles, xcd != 0u)) return;
+    const K * __restrict__ kin = j.kin;
+    K * __restrict__ kout = j.kout;
+    const u32 * __restrict__ vin = j.vin;
+    u32 * __restrict__ vout = j.vout;
+    const u32 * __restrict__ offs = j.hist;
+    const u64 n = j.n;
+    const int shift = j.shift;
+    const u32 tiles = j.tiles, iota_split = 0xFFFFFFFFu, out_base = 0u;
+#include "sort_scatter_body.hpp"  // (k_rs_scatter's body, on the names declared above)
+}
+
 // Passes of up to this many tiles (512 Ki keys) skip the scan: the scatter's workgroups read the count table themselves (RAW above).
 // Every workgroup reads the whole table -- tiles * 2^BITS words from L2 -- so the bound keeps that at 128 KiB (8-bit digits) per workgroup.
 constexpr u32 RS_RAW_TILES = 128;
@@ -432,6 +470,44 @@ void radix_pass_iota_u8_many(const RadixIotaJob * jobs, u32 count, u32 out_base,
     tmp.release(m);
 }
 
+// One array goes through radix_pass: the single kernels, launch for launch what a block alone has always had (the metric's 256 MiB blocks).
+template <typename K>
+void radix_pass_many(const RadixPairJob<K> * jobs, u32 count, Arena & tmp, hipStream_t s) {
+    if (count == 0 || count > SORT_MAX_BATCH) throw HipError{hipErrorUnknown, "radix batch of a size the job table does not hold", __FILE__, __LINE__};
+    if (count == 1) {
+        radix_pass<K>(jobs[0].kin, jobs[0].kout, jobs[0].vin, jobs[0].vout, jobs[0].n, jobs[0].shift, 0xFFFFFFFFu, 0u, tmp, s);
+        return;
+    }
+    RsBatchKV<K> b;
+    size_t m = tmp.mark();
+    u32 most = 0;
+    u32 * tables[SORT_MAX_BATCH];
+    u64 words[SORT_MAX_BATCH];
+    const bool iota = jobs[0].vin == nullptr;
+    for (u32 k = 0; k < count; k++) {
+        if (jobs[k].n == 0 || !jobs[k].kout || (jobs[k].vin == nullptr) != iota) throw HipError{hipErrorUnknown, "radix batch with an empty or a mixed array", __FILE__, __LINE__};
+        const u32 tiles = (u32)((jobs[k].n + RS_TILE - 1) / RS_TILE);
+        words[k] = (u64)tiles * RS_RADIX;
+        tables[k] = tmp.take<u32>((size_t)words[k]);
+        b.job[k] = typename RsBatchKV<K>::Job{jobs[k].kin, jobs[k].kout, jobs[k].vin, jobs[k].vout, tables[k], jobs[k].n, tiles, jobs[k].shift};
+        most = tiles > most ? tiles : most;
+    }
+    for (u32 k = count; k < SORT_MAX_BATCH; k++) b.job[k] = b.job[0];
+    const u32 xcd = 1u;
+    const dim3 grid(rs_grid(most, true), count);
+    launch(k_rs_hist_kv_many<K>, grid, dim3(RS_BLOCK), 0, s, b, xcd);
+    const bool raw = most <= RS_RAW_TILES && !rs_no_raw();
+    if (!raw) exclusive_scan_u32_many(tables, words, nullptr, count, tmp, s);
+    if (iota) {
+        if (raw) launch(k_rs_scatter_kv_many<K, true, true>, grid, dim3(RS_BLOCK), 0, s, b, xcd);
+        else launch(k_rs_scatter_kv_many<K, true, false>, grid, dim3(RS_BLOCK), 0, s, b, xcd);
+    } else {
+        if (raw) launch(k_rs_scatter_kv_many<K, false, true>, grid, dim3(RS_BLOCK), 0, s, b, xcd);
+        else launch(k_rs_scatter_kv_many<K, false, false>, grid, dim3(RS_BLOCK), 0, s, b, xcd);
+    }
+    tmp.release(m);
+}
+
 void radix_hist_bits9(const u32 * keys, u64 n, int shift, u32 * hist, u32 tiles, hipStream_t s) {
     launch(k_rs_hist<u32, 9>, dim3(rs_grid(tiles, true)), dim3(RS_BLOCK), 0, s, keys, n, shift, hist, tiles, 1u);
 }
@@ -459,6 +535,8 @@ template void radix_pass<u8>(const u8 *, u8 *, const u32 *, u32 *, u64, int, u32
 template void radix_pass<u32>(const u32 *, u32 *, const u32 *, u32 *, u64, int, u32, u32, Arena &, hipStream_t);
 template void radix_pass<u64>(const u64 *, u64 *, const u32 *, u32 *, u64, int, u32, u32, Arena &, hipStream_t);
 template void radix_pass_bits<u32, 9>(const u32 *, u32 *, const u32 *, u32 *, u64, int, u32, u32, Arena &, hipStream_t);
+template void radix_pass_many<u32>(const RadixPairJob<u32> *, u32, Arena &, hipStream_t);
+template void radix_pass_many<u64>(const RadixPairJob<u64> *, u32, Arena &, hipStream_t);
 template int radix_sort_pairs<u32>(u32 *, u32 *, u32 *, u32 *, u64, int, int, Arena &, hipStream_t);
 template int radix_sort_pairs<u64>(u64 *, u64 *, u32 *, u32 *, u64, int, int, Arena &, hipStream_t);
 

@@ -67,6 +67,21 @@ template <typename K>
 void radix_pass(const K * kin, K * kout, const u32 * vin, u32 * vout, u64 n, int shift, u32 iota_split, u32 out_base,
                 Arena & tmp, hipStream_t s);
 
+// radix_pass<K> (keys written out, out_base 0, no split) of `count` arrays in one launch per step: the forward suffix sorter of several blocks.
+// vin == nullptr generates the values (element i carries i), in every job of a call or in none.  Raw or scanned count tables are decided by
+// the longest array, as in radix_pass_iota_u8_many.  A batch of one IS radix_pass<K>.
+template <typename K>
+struct RadixPairJob {
+    const K * kin;
+    K * kout;
+    const u32 * vin;
+    u32 * vout;
+    u64 n;  // >= 1
+    int shift;
+};
+template <typename K>
+void radix_pass_many(const RadixPairJob<K> * jobs, u32 count, Arena & tmp, hipStream_t s);
+
 // The same with digits of BITS bits (8 or 9): digit = (key >> shift) & (2^BITS - 1).
 template <typename K, int BITS>
 void radix_pass_bits(const K * kin, K * kout, const u32 * vin, u32 * vout, u64 n, int shift, u32 iota_split, u32 out_base,

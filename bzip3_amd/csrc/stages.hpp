@@ -101,6 +101,27 @@ constexpr int BWT_ROUTE_KEEP = 40;
 s32 bwt_forward(const u8 * d_in, u32 n, u8 * d_out, Arena & tmp, hipStream_t s, BwtStats * stats, u32 * d_idx = nullptr, u32 * d_outside = nullptr);
 size_t bwt_workspace_bytes(u64 n);
 void bwt_set_big_rounds(int k);  // tests only: more windows for the big groups before the deep path (k < 0: the default, 1)
+// Several blocks through the same launch sequence at once: one launch per step for `count` <= BWT_MAX_BATCH blocks of n >= 2 bytes (smaller blocks
+// never enter a batch), one read-back per pass for all of them, all scratch from `tmp`, job after job.  Every launch is built from the jobs that
+// need it (they diverge: done, one more window, rank doubling).  Output, primary index, d_outside and the statistics of a block are what the block
+// gets alone -- bwt_forward is a batch of one.  The call waits for the stream at the end only if a job has no d_idx; `idx` then holds its index.
+constexpr u32 BWT_MAX_BATCH = 4;
+struct BwtBatchItem {
+    const u8 * in;
+    u32 n;
+    u8 * out;
+    u32 * d_idx;      // device word for the primary index (nullptr: returned in `idx`)
+    u32 * d_outside;  // may be nullptr
+    BwtStats * stats; // may be nullptr
+    s32 idx;          // out
+};
+void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t s);
+// How many of the first `count` blocks (sizes n[k]) one run takes, given the bytes the arena has free: 1 to BWT_MAX_BATCH.  Blocks above
+// BWT_BATCH_MAX_N bytes go alone: 64 MiB is the largest size at which a run has been measured (it still gains a quarter there, profiles/bwt_batch.txt),
+// and the metric's 256 MiB blocks keep the launch sequence and the workspace of a block alone.
+constexpr u32 BWT_BATCH_MAX_N = 64u << 20;
+u32 bwt_batch_size(const u32 * n, u32 count, size_t arena_free);
+void bwt_set_batch(int b);  // tests / sweeps: 1..BWT_MAX_BATCH forces the run length where memory allows, -1 = the rule
 
 // ---- inverse BWT (unbwt.hip) -- replaces libsais_unbwt, include/libsais.h:5260-5262 ----------
 // Asynchronous: no wait inside, and the scratch is back in `tmp` on return -- `tmp` must be an arena whose every user launches on `s`.
