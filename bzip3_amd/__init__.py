@@ -108,6 +108,10 @@ def _declare(L, strict=True):
         "bz3_hip_update_device_range_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp),
                                                        C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_patch": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_update_device_select": (C.c_int, [u32, vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), vp, sz, vp, vp, C.POINTER(sz)]),
+        "bz3_hip_update_device_select_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)),
+                                                        C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_patch_select": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), C.c_uint64]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -701,6 +705,92 @@ def update_tensor_range(frame, offset, data, planes=1, base=None, lib=None, bloc
                                     block_sizes=None if block_size is None else [block_size])[0]
     except Bz3Error as e:
         raise Bz3Error(e.code, "bz3_hip_update_device_range") from None
+
+
+def _joined_pieces(pl):
+    """The number of pieces of a list once the empty ones are dropped and neighbours that touch are joined."""
+    n, end = 0, None
+    for a, l in pl:
+        if l:
+            n += a != end
+            end = a + l
+    return n
+
+
+def update_tensors_select(frames, offsets, strides, counts, pieces, datas, planes=1, bases=None, lib=None, block_sizes=None):
+    """New frames in which an index set of what frames[i] decodes to is replaced by datas[i], for many frames in ONE call
+    (bz3_hip_update_device_select_many): the index set is that of decompress_tensors_select -- counts[i] periods strides[i] bytes apart from
+    offsets[i] on, of every period the pieces pieces[i] as (start, len) -- and datas[i] holds its new bytes in output order, all
+    counts[i] * sum(len) of them (ValueError otherwise: an update names all its bytes).  Only the chunks that hold a byte of a piece are coded
+    again; of those the ones the set does not cover whole are decoded first, each once however many pieces it holds, and every other chunk is
+    copied as it is, undecoded ("Index update").  Result i is byte for byte the frame compress_tensor gives for the updated bytes.
+    Pieces shorter than 16 elements of planes[i] bytes are scattered byte by byte: correct and slow.  The set must lie inside what its frame
+    decodes to (Bz3Error with BZ3_ERR_DATA_TOO_BIG); an empty one gives a copy of the frame.  `bases[i]`: None, or for a frame made against a
+    base the base's bytes OF THE INDEX SET in output order, as many as datas[i].  ValueError for what decompress_tensors_select refuses.  The 13
+    header bytes of all frames are read from the device once; with the block size bs (block_sizes[i] where given) and the number of chunks they
+    size the outputs, views of one allocation of frames[i].numel() + min(chunks, W // bs + 2 * pieces * counts[i]) * bz3_bound(bs) bytes each
+    (pieces: after joining neighbours that touch; .clone() a result to drop the rest).  The inputs are never written.  Raises Bz3Error with
+    .index / .codes / .outs as update_tensors_range does; a frame that fails has no output.  [] returns []."""
+    import torch
+
+    name = "update_tensors_select"
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
+    cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
+    lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
+    if any(len(col) != n for col in cols) or len(lists) != n or len(datas) != n:
+        raise ValueError(f"{name}: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists, {len(datas)} data tensors")
+    params = list(zip(*cols)) if n else []
+    for i, ((o, s, c), pl, d) in enumerate(zip(params, lists, datas)):
+        if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
+            raise ValueError(f"{name}: offsets, strides, counts and pieces must not be negative")
+        if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
+            raise ValueError(f"{name}: the pieces of frame {i} do not ascend")
+        L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
+        if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
+            raise ValueError(f"{name}: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
+        if d.numel() != c * L:
+            raise ValueError(f"{name}: datas[{i}] holds {d.numel()} bytes, the index set of frame {i} {c * L}")
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
+    dev = _same_device(frames + datas, name)
+    L = lib or load()
+    heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
+    if block_sizes is None:
+        block_sizes = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
+    bss = [min(max(int(b), _KiB65), _MiB511) for b in block_sizes]  # (a header that lies: the call refuses it, or finds the output too small)
+    if len(bss) != n:
+        raise ValueError(f"{name}: {n} frames and {len(bss)} block sizes")
+    chunks = [int.from_bytes(bytes(h[9:13]), "little") for h in heads]
+    caps = [f.numel() + min(nb, d.numel() // bs + 2 * _joined_pieces(pl) * c) * L.bz3_bound(bs) for f, d, bs, nb, pl, (_, _, c) in zip(frames, datas, bss, chunks, lists, params)]
+    outs = _carve(sum(caps), caps, dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
+    ptrs = (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs])
+    torch.cuda.synchronize(dev)
+    rc = L.bz3_hip_update_device_select_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                             (C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]), ptrs, _ptrs(datas),
+                                             (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(codes[idx], "bz3_hip_update_device_select_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def update_tensor_select(frame, offset, stride, count, pieces, data, planes=1, base=None, lib=None, block_size=None):
+    """The frame in which `count` periods' pieces (start, len), `stride` bytes apart from `offset` on, of what `frame` decodes to are replaced by
+    `data` (bz3_hip_update_device_select): update_tensors_select for one frame."""
+    try:
+        return update_tensors_select([frame], [offset], [stride], [count], [pieces], [data], planes=planes, bases=None if base is None else [base], lib=lib,
+                                     block_sizes=None if block_size is None else [block_size])[0]
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_update_device_select") from None
 
 
 def decompress_tensors_strided(frames, offsets, runs, strides, counts, outs=None, planes=1, bases=None, lib=None):
@@ -1322,6 +1412,133 @@ def unpack_tensor_index(p, dim, index, out=None, base=None, lib=None):
     if out is None:
         return torch.index_select(part, d, order)
     torch.index_select(part, d, order, out=out)
+    return out
+
+
+def _update_parts_many(ps, sels, values, bases, lib, names=None):
+    """For every PackedTensor sels[i] = (dim, index) (strictly increasing) or a slice (dim, start, stop): the PackedTensors with that part replaced
+    by values[i], a tensor of the part's shape, through ONE bz3_hip_update_device_select_many call.  bases[i]: the same part of the base.  Every
+    argument is checked before any GPU work."""
+    import torch
+
+    reqs, raws, braws = [], [], []
+    for i, (p, sel, v, b) in enumerate(zip(ps, sels, values, _bases_arg(bases, len(ps)))):
+        what = f"tensor {i}" if names is None else repr(names[i])
+        shape, q, _ = _index_of(p, sel, f"update: {what}")
+        if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
+            raise TypeError(f"update: the values of {what} must be a torch tensor on a GPU")
+        if v.dtype != p.dtype or tuple(v.shape) != tuple(shape):
+            raise TypeError(f"update: the values of {what} must be {p.dtype} of shape {tuple(shape)}")
+        if p.delta and b is None:
+            raise ValueError(f"update: {what} was packed against a base, whose part is needed to code the new one")
+        if not p.delta:
+            b = None
+        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != tuple(shape):
+            raise ValueError(f"update: the base of {what} must hold the same part of the base: {p.dtype} {tuple(shape)}")
+        raw = _as_bytes(v, f"the values of {what}")
+        reqs.append(q)
+        raws.append(raw)
+        braws.append(_base_bytes(b, raw.numel(), p.frame.device, f"the base of {what}"))
+    frames = update_tensors_select([p.frame for p in ps], *zip(*reqs), raws, planes=[p.planes for p in ps], bases=braws, lib=lib, block_sizes=[p.block_size for p in ps])
+    return [PackedTensor(f, p.dtype, p.shape, p.planes, p.block_size, p.nbytes, p.delta, p.base_crc, None) for f, p in zip(frames, ps)]
+
+
+def update_tensor_slice(p, dim, start, stop, values, base=None, lib=None):
+    """The write mirror of unpack_tensor_slice: a new PackedTensor that holds p's tensor x with x.narrow(dim, start, stop - start) replaced by
+    `values`, on the frame's GPU, without the tensor ever being materialised (bz3_hip_update_device_select with one piece per period: a
+    column block of a weight matrix).  Its frame is byte for byte the one pack_tensor gives for the updated tensor at p.block_size and p.planes.
+    Only the chunks that hold a byte of the slice are coded again; a slice of an inner dimension usually touches every chunk, and each is then
+    decoded once and coded once -- what the call saves is the full-size tensor and the chunks between two runs where there are any.  Runs
+    shorter than 16 elements of p.planes bytes are scattered byte by byte: correct and slow.  `values`: a GPU tensor of p's dtype and of the
+    slice's shape (TypeError otherwise; any strides); ValueError for a 0-d tensor, a bad `dim` and unless 0 <= start <= stop <= p.shape[dim].  All
+    of that is checked before any GPU work.  A tensor packed against a base needs `base`: THE SAME SLICE of the base.  Everything but `crc`,
+    which is None as after update_tensor_rows, is carried over; `p` is unchanged."""
+    return _update_parts_many([p], [(dim, start, stop)], [values], [base], lib)[0]
+
+
+def _update_index_arg(p, dim, index, values, has_base, what):
+    """((dim, the sorted index), values in that order) for an index_copy: duplicates are a ValueError, and an index that is not increasing is
+    sorted on the host and `values` permuted once on the device."""
+    import torch
+
+    idx = _index_list(index, what)
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"{what}: the index holds duplicates, for which index_copy has no defined result")
+    if all(a < b for a, b in zip(idx, idx[1:])):
+        return (dim, idx), values
+    if has_base:
+        raise ValueError(f"{what}: a tensor packed against a base takes a strictly increasing index (its base is given in the index's order)")
+    order = sorted(range(len(idx)), key=idx.__getitem__)
+    sel = (dim, [idx[j] for j in order])
+    shape, _, _ = _index_of(p, sel, what)  # (validates p, dim and the index's range before anything is moved)
+    if not isinstance(values, torch.Tensor) or values.device.type != "cuda":
+        raise TypeError(f"{what}: the values must be a torch tensor on a GPU")
+    if values.dtype != p.dtype or tuple(values.shape) != tuple(shape):
+        raise TypeError(f"{what}: the values must be {p.dtype} of shape {tuple(shape)}")
+    return sel, torch.index_select(values, int(dim) % len(p.shape), torch.tensor(order, dtype=torch.int64, device=values.device))
+
+
+def update_tensor_index(p, dim, index, values, base=None, lib=None):
+    """A new PackedTensor that holds x.index_copy(dim, index, values) of the tensor x a PackedTensor holds, on the frame's GPU, without the tensor
+    ever being materialised (bz3_hip_update_device_select): the embedding rows a sparse optimiser step touched, a handful of experts of an
+    [E, ...] tensor, scattered columns.  Its frame is byte for byte the one pack_tensor gives for the updated tensor at p.block_size and
+    p.planes.  `index` is what unpack_tensor_index accepts, with values in [0, p.shape[dim]), but duplicates are a ValueError: index_copy with
+    duplicates has no defined result.  Every run of consecutive indices is one piece, as there.  Only the chunks of the frame that hold a byte of
+    a piece are coded again; of those the ones the pieces do not cover whole are decoded first, each once however many pieces it holds, and
+    every other chunk is copied undecoded.  Pieces shorter than 16 elements of p.planes bytes are scattered byte by byte: correct and slow.  An
+    index that is not increasing is sorted on the host and `values` permuted once on the device with torch.index_select; with a base such an
+    index is a ValueError, as on the read side.  `values`: a GPU tensor of p's dtype and of the shape of x.index_select(dim, index) (TypeError
+    otherwise).  All of that is checked before any GPU work.  A tensor packed against a base needs `base`: THE SAME index_select of the base.
+    planes, block_size, dtype, shape, nbytes, delta and base_crc are carried over; `crc` of the result is None (update_tensor_rows says why).  An
+    empty index gives a copy of the frame.  `p` is unchanged."""
+    if not isinstance(p, PackedTensor):
+        raise TypeError("update: a PackedTensor is expected")
+    sel, values = _update_index_arg(p, dim, index, values, p.delta, "update_tensor_index")
+    return _update_parts_many([p], [sel], [values], [base], lib)[0]
+
+
+def update_state_dict(packed, rows=None, slices=None, index=None, base=None, lib=None):
+    """The write mirror of unpack_state_dict's three keywords: `rows` is {name: (start, values)} (update_tensor_rows), `slices`
+    {name: (dim, start, stop, values)} (update_tensor_slice) and `index` {name: (dim, index, values)} (update_tensor_index).  Every named tensor goes
+    through ONE bz3_hip_update_device_select_many call, and the result is a new dict in which those names have new PackedTensors (crc None) and
+    every other name the PackedTensor of `packed` itself.  `base`: {name: the same part of that tensor's base}, needed for the named tensors that
+    were packed against one.  A name in more than one keyword, or one that is not in `packed`: ValueError.  Everything is checked before any GPU
+    work; `packed` is unchanged."""
+    import torch
+
+    want = {}
+    for arg, d in (("rows", rows), ("slices", slices), ("index", index)):
+        for k, v in (d or {}).items():
+            if k in want:
+                raise ValueError(f"update_state_dict: {k!r} is named by more than one of rows, slices and index")
+            if k not in packed:
+                raise ValueError(f"update_state_dict: {arg} for {k!r}, which is not in the dict")
+            want[k] = (arg, tuple(v))
+    names = list(want)
+    out = dict(packed)
+    if not names:
+        return out
+    sels, values = [], []
+    for k in names:
+        arg, v = want[k]
+        p = packed[k]
+        if not isinstance(p, PackedTensor):
+            raise TypeError("update: a PackedTensor is expected")
+        if arg == "rows":
+            start, vals = v
+            _row_bytes(p, repr(k))
+            if not isinstance(vals, torch.Tensor):
+                raise TypeError(f"update: the rows of {k!r} must be a torch tensor on a GPU")
+            sels.append((0, int(start), int(start) + (vals.shape[0] if vals.dim() else 0)))
+        elif arg == "slices":
+            dim, start, stop, vals = v
+            sels.append((dim, start, stop))
+        else:
+            dim, idx, vals = v
+            sel, vals = _update_index_arg(p, dim, idx, vals, p.delta, f"update_state_dict: {k!r}")
+            sels.append(sel)
+        values.append(vals)
+    out.update(zip(names, _update_parts_many([packed[k] for k in names], sels, values, [None if base is None else base.get(k) for k in names], lib, names)))
     return out
 
 

@@ -119,12 +119,13 @@ struct GatherList {
     };
     std::vector<Entry> v;
     int level = SEG_DELTA;
-    bool patched = false;  // the list holds a clipped split: the launch is k_patch_segments, and holds no partial merge
+    bool patched = false;  // the list holds a clipped or a select split: the launch is k_patch_segments or k_patch_select_segments, and holds no partial merge
+    bool merged = false;   // the list holds a partial merge
     size_t size() const { return v.size(); }
     void clear() {
         v.clear();
         level = SEG_DELTA;
-        patched = false;
+        patched = merged = false;
     }
     // A segment as it is: a copy, a split, a merge, with or without a base.
     void plain(const CopySeg & sg) { v.push_back({sg, {}}); }
@@ -134,6 +135,7 @@ struct GatherList {
         if (k <= 1 || a == b || (a == 0 && b == s)) return plain({slot + (k <= 1 ? a : 0), dst, b - a, k | PLANES_INVERSE, base});
         v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_CLIP, base}, {a, b}});
         level = std::max<int>(level, SEG_CLIP);
+        merged = true;
     }
     // The write mirror of range(): the chunk bytes [a, b) of the chunk of s bytes that `slot` holds in split form get the new values src[0, b - a)
     // (less base[0, b - a), or 0), which address the clip's first byte.  A whole chunk and every k = 1 clip are ordinary segments, the rest clipped
@@ -150,6 +152,7 @@ struct GatherList {
         if (nbytes <= first) return range(slot, s, k, c0, c0 + nbytes, dst, base);
         v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_STRIDED, base}, {c0, first, run, stride, nbytes}});
         level = std::max<int>(level, SEG_STRIDED);
+        merged = true;
     }
     // The same for a chunk of which a select request wants the nbytes > 0 bytes c(u) (planes.hpp, "Select merge": rel, stride, q0, r0 < L, the
     // table t at device address d_tab): a share within one piece is the clipped or whole segment above, anything else a select merge.
@@ -161,11 +164,25 @@ struct GatherList {
         }
         v.push_back({{slot, dst, s, k | PLANES_INVERSE | PLANES_SELECT, base}, {rel, stride, q0, r0, nbytes, d_tab, t.m}});
         level = SEG_SELECT;
+        merged = true;
+    }
+    // The write mirror of select(): the chunk bytes c(u), u < nbytes (nbytes > 0), of the chunk of s bytes that `slot` holds in split form get the
+    // new values src[0, nbytes) (less base[0, nbytes), or 0).  A share within one piece is the clipped or whole split of patch(), anything else a
+    // select split (planes.hpp, "Select split").
+    void patch_select(u64 src, u64 base, u64 slot, u64 s, u64 k, u64 rel, u64 stride, const PieceTable & t, u64 d_tab, u64 q0, u64 r0, u64 nbytes) {
+        const u64 j = piece_of(t.tab.data(), (u32)t.m, r0);
+        if (nbytes <= t.P(j + 1) - r0) {
+            const u64 c0 = rel + q0 * stride + t.s(j) + (r0 - t.P(j));
+            return patch(src, base, slot, s, k, c0, c0 + nbytes);
+        }
+        v.push_back({{src, slot, s, k | PLANES_SELECT, base}, {rel, stride, q0, r0, nbytes, d_tab, t.m}});
+        level = SEG_SELECT;
+        patched = true;
     }
 };
 
 // Copies the segments of g (absolute device addresses) in one launch on stream s; d_tab holds table_bytes(g.size(), g.level) bytes.  The kernel
-// is k_patch_segments for a list with a clipped split, else the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
+// is k_patch_segments for a list with a clipped split (k_patch_select_segments where it holds a select split as well), else the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
 // k_copy_segments (planes.hpp).  The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
 void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
     const size_t n = g.size(), bytes = table_bytes(n, g.level), seg_bytes = align16(n * sizeof(CopySeg));
@@ -195,7 +212,7 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
         planes |= k > 1;
         delta |= sg.base != 0;
     }
-    if (g.patched && g.level != SEG_CLIP) throw std::logic_error("clipped splits and partial merges in one launch");
+    if (g.patched && g.merged) throw std::logic_error("patch segments and partial merges in one launch");
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
@@ -206,7 +223,8 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
     const u64 * d_clips = (const u64 *)(d_tab + clip_off);
     const u64 * d_periods = (const u64 *)(d_tab + period_off);
     const u64 * d_selects = (const u64 *)(d_tab + select_off);
-    if (g.patched) launch(k_patch_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
+    if (g.patched && g.level == SEG_SELECT) launch(k_patch_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_selects);
+    else if (g.patched) launch(k_patch_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
     else if (g.level == SEG_SELECT) launch(k_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods, d_selects);
     else if (g.level == SEG_STRIDED) launch(k_strided_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods);
     else if (g.level == SEG_CLIP) launch(k_range_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
@@ -919,21 +937,28 @@ void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t *
 //      segments per frame.  (A frame may hold empty chunks between touched ones; each such gap is a run of its own, and the launch is split
 //      where its table is full.)
 // A frame that fails in 1 or 2 has its code, size 0 and an untouched `out`; one that fails in 3 (not expected) its code and size 0.
-void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u64 * offsets, const u8 * const * datas,
+// The bytes to replace are those of reqs[i], cut at ws[i] (bz3_hip.h, "Index update"): a request in range form is the range above, bit for bit; one
+// with a piece table names the bytes phi(t), t < w, and data[t] (base[t]) pairs with phi(t).  Whatever the form, chunk j's new bytes are
+// data[ta, tb) with ta = below(p_j), tb = below(p_j + o_j): one contiguous piece of data and of base.  It is touched iff tb > ta, covered iff
+// tb - ta == o_j and cut otherwise, and a cut chunk is decoded once however many pieces and periods it holds.  Its patch segment is a whole split,
+// a clipped split where its new bytes are one run of the chunk, and a select split otherwise (GatherList::patch_select); the piece tables of a call
+// are uploaded once, beside the walk's arguments, as decompress_frames uploads them.  The walk stays the plain walk: the copies need every record.
+// A call whose touched chunks exceed one window still decodes its cut chunks twice; parking the decoded chunks is open.
+void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const Request * reqs, const u8 * const * datas,
                    const size_t * ws, const u8 * const * bases, u8 * const * outs, size_t * out_sizes, int * rcs) {
-    struct Frame {
-        u64 lo = 0, hi = 0;     // the range; hi < lo: offset + w does not fit 64 bits
-        u64 need = 13, end = 0;  // the capacity the frame needs; the offset behind its last chunk
+    struct Frame : Request {    // cut at ws[i]: w bytes, the last of them phi(w - 1) = hi - 1 (hi == UINT64_MAX: it does not fit 64 bits)
+        u64 need = 13, tail = 0;  // the capacity the frame needs; the offset behind its last chunk
         size_t cap = 0, pos = 0;
         u64 in_next = 0;         // the frame's bytes before it are in `out`
-        u32 count = 0, packed = 0;  // its touched chunks, and those of them that are packed
+        u32 chunks = 0, packed = 0;  // its touched chunks, and those of them that are packed
     };
     struct Touched {
         s32 frame;
         WalkChunk rec;
-        u64 a, b;  // the chunk's bytes [a, b) are replaced
-        bool cut() const { return a != 0 || b != (u64)rec.orig; }
+        u64 ta, tb;  // the chunk's new bytes are data[ta, tb) (Request::below of its two ends), of base too
+        bool cut() const { return tb - ta != (u64)rec.orig; }
     };
+    std::vector<u64> tables;  // the piece tables of the frames that patch with one, as they are uploaded
     std::vector<Frame> fr((size_t)n);
     std::vector<WalkPos> pos((size_t)n);
     std::vector<char> live((size_t)n, 0);
@@ -943,8 +968,12 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
         rcs[i] = BZ3_OK;
         fr[i].cap = out_sizes[i];
         out_sizes[i] = 0;
-        fr[i].lo = offsets ? offsets[i] : 0;
-        fr[i].hi = fr[i].lo + (u64)ws[i];
+        static_cast<Request &>(fr[i]) = reqs[i];
+        fr[i].cut((u64)ws[i]);
+        if (fr[i].sel) {
+            fr[i].d_tab = tables.size() * sizeof(u64);
+            tables.insert(tables.end(), fr[i].sel->tab.begin(), fr[i].sel->tab.end());
+        }
         if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
         else live[i] = any = 1;
     }
@@ -957,8 +986,14 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     DeviceFrames f;
     u32 bs_max = 0;
     try {
-        if (!f.open(dev, (size_t)n, 0, 2)) throw std::runtime_error("no device");
+        if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64), 2)) throw std::runtime_error("no device");
         DeviceGuard g(dev);
+        if (!tables.empty()) {  // the piece tables: one upload per call
+            HIP_CHECK(hipMemcpyAsync(f.meta + f.lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, f.s));
+            HIP_CHECK(hipStreamSynchronize(f.s));
+            for (s32 i = 0; i < n; i++)
+                if (fr[i].sel) fr[i].d_tab += (u64)(f.meta + f.lay.pieces);
+        }
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
         std::vector<WalkArg> args;
         std::vector<s32> who;
@@ -984,11 +1019,12 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
                 for (u32 r = 0; r < tails[q].count; r++) {
                     const WalkChunk & c = rec[args[q].rec_base + r];
                     const u64 p = c.out_off, o = (u64)c.orig;
-                    const bool touched = x.lo < x.hi && o > 0 && p < x.hi && p + o > x.lo;
+                    const u64 ta = o > 0 ? x.below(p) : 0, tb = o > 0 ? x.below(p + o) : 0;  // (touched iff the chunk holds phi(t) for some t < w)
+                    const bool touched = tb > ta;
                     x.need += 8 + (touched ? (u64)bz3_bound((size_t)o) : (u64)c.size);
                     if (!touched) continue;
-                    touch.push_back({i, c, std::max(x.lo, p) - p, std::min(x.hi, p + o) - p});
-                    x.count++;
+                    touch.push_back({i, c, ta, tb});
+                    x.chunks++;
                 }
                 pos[i].take(tails[q]);
                 if (tails[q].err != BZ3_OK) fail(i, tails[q].err);
@@ -996,8 +1032,8 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
         }
         for (s32 i = 0; i < n; i++) {
             if (!live[i]) continue;
-            fr[i].end = pos[i].off;
-            if (fr[i].hi < fr[i].lo || fr[i].hi > pos[i].planned || fr[i].cap < fr[i].need) fail(i, BZ3_ERR_DATA_TOO_BIG);
+            fr[i].tail = pos[i].off;
+            if (fr[i].hi > pos[i].planned || fr[i].cap < fr[i].need) fail(i, BZ3_ERR_DATA_TOO_BIG);
         }
         touch.erase(std::remove_if(touch.begin(), touch.end(), [&](const Touched & t) { return !live[t.frame]; }), touch.end());
         for (const Touched & t : touch) bs_max = std::max(bs_max, pos[t.frame].block_size);
@@ -1061,8 +1097,8 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
             fr[i].in_next = to;
         };
         for (s32 i = 0; i < n; i++)  // a frame without a touched chunk is one run
-            if (live[i] && fr[i].count == 0) {
-                run(i, 0, fr[i].end);
+            if (live[i] && fr[i].chunks == 0) {
+                run(i, 0, fr[i].tail);
                 out_sizes[i] = fr[i].pos;
             }
         for (size_t w0 = 0; w0 < total; w0 += W) {
@@ -1081,8 +1117,11 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
                 const Touched & c = touch[w0 + k];
                 const s32 i = c.frame;
                 if (!live[i]) continue;
-                const u64 rel = c.rec.out_off + c.a - fr[i].lo, es = elem_sizes ? (u64)elem_sizes[i] : 1;  // the clip's first byte in data and base
-                f.gather.patch((u64)(datas[i] + rel), bases && bases[i] ? (u64)(bases[i] + rel) : 0, (u64)f.slot(k), (u64)c.rec.orig, es, c.a, c.b);
+                const Frame & x = fr[i];
+                const u64 p = c.rec.out_off, es = elem_sizes ? (u64)elem_sizes[i] : 1;
+                const u64 src = (u64)(datas[i] + c.ta), b = bases && bases[i] ? (u64)(bases[i] + c.ta) : 0;  // the chunk's first new byte in data and base
+                if (x.sel) f.gather.patch_select(src, b, (u64)f.slot(k), (u64)c.rec.orig, es, x.lo - p, x.stride, *x.sel, x.d_tab, c.ta / x.run, c.ta % x.run, c.tb - c.ta);
+                else f.gather.patch(src, b, (u64)f.slot(k), (u64)c.rec.orig, es, x.lo + c.ta - p, x.lo + c.tb - p);
                 f.states[k]->block_size = (s32)pos[i].block_size;
                 f.states[k]->last_error = BZ3_OK;
                 sts.push_back(f.states[k]);
@@ -1114,8 +1153,8 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
                 f.gather.plain({(u64)slots[j], (u64)(outs[i] + x.pos + 8), (u64)osz});
                 x.pos += (size_t)osz + 8;
                 x.in_next = c.rec.in_off + 8 + (u64)c.rec.size;
-                if (++x.packed == x.count) {
-                    run(i, x.in_next, x.end);
+                if (++x.packed == x.chunks) {
+                    run(i, x.in_next, x.tail);
                     out_sizes[i] = x.pos;
                 }
             }
@@ -1125,10 +1164,10 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     } catch (const HipError & e) {
         fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
         for (s32 i = 0; i < n; i++)
-            if (live[i] && (fr[i].packed < fr[i].count || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+            if (live[i] && (fr[i].packed < fr[i].chunks || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
     } catch (...) {
         for (s32 i = 0; i < n; i++)
-            if (live[i] && (fr[i].packed < fr[i].count || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+            if (live[i] && (fr[i].packed < fr[i].chunks || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
     }
 }
 
@@ -1380,14 +1419,17 @@ BZIP3_API int bz3_hip_decompress_device_range(uint32_t elem_size, const void * i
     return bz3_hip_decompress_device_range_many(1, &elem_size, ins, &in_size, &offset, bases, &base_size, outs, out_size, &rc);
 }
 
-// Range update (bz3_hip.h).  Whole-call checks as in the range calls; then, before any write, the overlaps of a frame's out[0, cap) with its input,
-// its data and its base.
-BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], const uint64_t offsets[],
-                                               const void * const datas[], const size_t ws[], const void * const bases[], void * const outs[], size_t out_sizes[],
-                                               int rcs[]) {
+// Range and index update (bz3_hip.h).  Whole-call checks as in the range calls; frame i's request from make(i, request) (false: an invalid one, which
+// fails the whole call before any write); then, before any write, the overlaps of a frame's out[0, cap) with its input, its data and its base.
+namespace {
+int update_requests(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], bool params_ok, const void * const datas[], const size_t ws[],
+                    const void * const bases[], void * const outs[], size_t out_sizes[], int rcs[], const std::function<bool(s32, Request &)> & make) {
     if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !datas || !ws || !outs || !out_sizes || !rcs) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    if (n < 0 || !ins || !in_sizes || !datas || !ws || !outs || !out_sizes || !rcs || !params_ok) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    std::vector<Request> reqs((size_t)n);
+    for (s32 i = 0; i < n; i++)
+        if (!make(i, reqs[(size_t)i])) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
     if (dev < 0) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (every frame is empty and has no room: nothing to walk, nowhere to write)
     for (s32 i = 0; i < n; i++) {
@@ -1397,8 +1439,60 @@ BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_si
             (base && ranges_overlap(outs[i], out_sizes[i], base, ws[i])))
             return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     }
-    update_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, offsets, (const u8 * const *)datas, ws, (const u8 * const *)bases, (u8 * const *)outs, out_sizes, rcs);
+    update_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, reqs.data(), (const u8 * const *)datas, ws, (const u8 * const *)bases, (u8 * const *)outs, out_sizes, rcs);
     return first_error(n, rcs);
+}
+}  // namespace
+
+BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], const uint64_t offsets[],
+                                               const void * const datas[], const size_t ws[], const void * const bases[], void * const outs[], size_t out_sizes[],
+                                               int rcs[]) {
+    return update_requests(n, elem_sizes, ins, in_sizes, true, datas, ws, bases, outs, out_sizes, rcs, [&](s32 i, Request & r) {
+        r = Request::range(offsets ? offsets[i] : 0);
+        return true;
+    });
+}
+
+// params: per frame (offset, stride, count, m); pieces[i]: m pairs (s_j, l_j) in host memory, valid as the index decode demands; ws[i] must be
+// W = count L.  The normal form: no byte named is the empty range (offset is not looked at); one piece left with count == 1 or stride == L is the
+// range (offset + s_0, W), which takes the range update's path bit for bit; everything else patches with its piece table, one piece included (a
+// strided update is the one-piece table: planes.hpp has no strided split).
+BZIP3_API int bz3_hip_update_device_select_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], const uint64_t params[],
+                                                const uint64_t * const pieces[], const void * const datas[], const size_t ws[], const void * const bases[],
+                                                void * const outs[], size_t out_sizes[], int rcs[]) {
+    std::vector<PieceTable> tables;  // (sized once the whole-call checks have passed)
+    return update_requests(n, elem_sizes, ins, in_sizes, params != nullptr, datas, ws, bases, outs, out_sizes, rcs, [&](s32 i, Request & r) {
+        const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
+        tables.resize((size_t)n);
+        PieceTable & t = tables[(size_t)i];
+        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return false;
+        if (t.L == 0 || count == 0) {  // W = 0: the verbatim copy
+            r = Request::range(0);
+            return ws[i] == 0;
+        }
+        const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
+        if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX || (u64)W != (u64)ws[i]) return false;
+        if (t.m == 1 && (count == 1 || stride == t.L)) {
+            r = Request::range(offset + t.s(0));
+        } else {
+            r = Request::strided(offset, t.L, stride, count);
+            r.sel = &t;
+        }
+        return true;
+    });
+}
+
+BZIP3_API int bz3_hip_update_device_select(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t stride, uint64_t count, uint64_t m,
+                                           const uint64_t * pieces, const void * data, size_t w, const void * base, void * out, size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * datas[1] = {data};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    const uint64_t params[4] = {offset, stride, count, m};
+    const uint64_t * lists[1] = {pieces};
+    int rc = BZ3_OK;
+    return bz3_hip_update_device_select_many(1, &elem_size, ins, &in_size, params, lists, datas, &w, bases, outs, out_size, &rc);
 }
 
 BZIP3_API int bz3_hip_update_device_range(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, const void * data, size_t w, const void * base, void * out,
@@ -1560,34 +1654,45 @@ BZIP3_API int32_t bz3_hip_debug_strided(const void * src, const void * base, voi
     });
 }
 
+namespace {
+// The checks the two select hooks share on their n tuples of 12 u64, whose fifth field must be elem_size | mode_bits: the tables of the tuples as
+// they are given (tabs), one after the other as they are uploaded (all), and whether a tuple has a base.  False for what bz3_hip.h refuses.
+bool debug_select_tuples(const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces, u64 mode_bits, std::vector<PieceTable> & tabs, std::vector<u64> & all,
+                         bool & any_base) {
+    if (n < 0 || (n > 0 && !segs) || (n_pieces && !pieces)) return false;
+    tabs.resize((size_t)std::max(n, 0));
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)12 * i;
+        const u64 len = q[3], rel = q[5], stride = q[6], q0 = q[7], r0 = q[8], nbytes = q[9], first = q[10], m = q[11];
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != mode_bits || len >= ((u64)1 << 31) || nbytes > len) return false;
+        if (first > n_pieces || m > n_pieces - first || m >= ((u64)1 << 31)) return false;
+        PieceTable & t = tabs[(size_t)i];
+        if (!t.take(m ? pieces + 2 * first : nullptr, m, false)) return false;
+        all.insert(all.end(), t.tab.begin(), t.tab.end());
+        any_base |= q[1] != UINT64_MAX;
+        if (!nbytes) continue;
+        if (t.L == 0 || r0 >= t.L || (nbytes > t.L - r0 && stride < t.given_end)) return false;
+        for (const u64 u : {(u64)0, nbytes - 1}) {  // c(0) and c(nbytes - 1) lie in the chunk (c increases)
+            const u64 x = r0 + u;
+            const unsigned __int128 period = (unsigned __int128)q0 + x / t.L;
+            if (stride && period > UINT64_MAX / stride) return false;
+            const __int128 c = (__int128)(s64)rel + (__int128)(period * stride) + t.byte(x % t.L);
+            if (c < 0 || c >= (__int128)len) return false;
+        }
+    }
+    return true;
+}
+}  // namespace
+
 // n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, rel, stride, q0, r0, nbytes, first_piece, m): of the merge of the `len`
 // bytes at src_off the nbytes bytes c(u) (planes.hpp, "Select merge") of the m pieces (s_j, l_j) from pieces[2 first_piece] on, to dst_off (plus the
 // bytes at base_off unless it is UINT64_MAX), one launch through the segments a select call's gather makes of them.  The pieces are taken as they
 // are, empty ones and neighbours that touch included.
 BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces) {
-    if (n < 0 || (n > 0 && !segs) || (n_pieces && !pieces)) return BZ3_ERR_INIT;
     bool any_base = false;
-    std::vector<PieceTable> tabs((size_t)n);
-    std::vector<u64> all;  // the tables one after the other, as they are uploaded
-    for (s32 i = 0; i < n; i++) {
-        const uint64_t * q = segs + (size_t)12 * i;
-        const u64 len = q[3], rel = q[5], stride = q[6], q0 = q[7], r0 = q[8], nbytes = q[9], first = q[10], m = q[11];
-        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || len >= ((u64)1 << 31) || nbytes > len) return BZ3_ERR_INIT;
-        if (first > n_pieces || m > n_pieces - first || m >= ((u64)1 << 31)) return BZ3_ERR_INIT;
-        PieceTable & t = tabs[(size_t)i];
-        if (!t.take(m ? pieces + 2 * first : nullptr, m, false)) return BZ3_ERR_INIT;
-        all.insert(all.end(), t.tab.begin(), t.tab.end());
-        any_base |= q[1] != UINT64_MAX;
-        if (!nbytes) continue;
-        if (t.L == 0 || r0 >= t.L || (nbytes > t.L - r0 && stride < t.given_end)) return BZ3_ERR_INIT;
-        for (const u64 u : {(u64)0, nbytes - 1}) {  // c(0) and c(nbytes - 1) lie in the chunk (c increases)
-            const u64 x = r0 + u;
-            const unsigned __int128 period = (unsigned __int128)q0 + x / t.L;
-            if (stride && period > UINT64_MAX / stride) return BZ3_ERR_INIT;
-            const __int128 c = (__int128)(s64)rel + (__int128)(period * stride) + t.byte(x % t.L);
-            if (c < 0 || c >= (__int128)len) return BZ3_ERR_INIT;
-        }
-    }
+    std::vector<PieceTable> tabs;
+    std::vector<u64> all;
+    if (!debug_select_tuples(segs, n, pieces, n_pieces, 1, tabs, all, any_base)) return BZ3_ERR_INIT;
     return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
         if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
         size_t at = 0;
@@ -1595,6 +1700,27 @@ BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void
             const uint64_t * q = segs + (size_t)12 * i;
             const PieceTable & t = tabs[(size_t)i];
             if (q[9]) g.select((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, (u64)d_tabs + at * sizeof(u64), q[7], q[8], q[9], (u64)dst + q[2], debug_base(base, q[1]));
+            at += t.tab.size();
+        }
+    });
+}
+
+// bz3_hip_debug_select in the forward direction: n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size, rel, stride, q0, r0, nbytes, first_piece,
+// m).  The slot of `len` bytes at dst_off holds a chunk in split form, of which the nbytes bytes c(u) (planes.hpp, "Select split") of the m pieces
+// from pieces[2 first_piece] on get the values at src_off (less the bytes at base_off unless it is UINT64_MAX), one launch through the segments an
+// update call's patch makes of them.  The pieces are taken as they are, empty ones and neighbours that touch included.
+BZIP3_API int32_t bz3_hip_debug_patch_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces) {
+    bool any_base = false;
+    std::vector<PieceTable> tabs;
+    std::vector<u64> all;
+    if (!debug_select_tuples(segs, n, pieces, n_pieces, 0, tabs, all, any_base)) return BZ3_ERR_INIT;
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
+        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+        size_t at = 0;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)12 * i;
+            const PieceTable & t = tabs[(size_t)i];
+            if (q[9]) g.patch_select((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6], t, (u64)d_tabs + at * sizeof(u64), q[7], q[8], q[9]);
             at += t.tab.size();
         }
     });

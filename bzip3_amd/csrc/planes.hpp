@@ -118,6 +118,20 @@
 // share of [dst, dst + nbytes)).  In place (dst == base): the tile argument of the strided merge holds word for word, because the tiling, the
 // lanes' destination bytes and phase 2 are the same and only the SOURCE byte of a destination byte differs.  No scratch, and the LDS of
 // k_strided_segments.
+//
+// Select split (CopySeg::mode & PLANES_SELECT without PLANES_INVERSE; bz3_hip_update_device_select, api_frames.hip).  The write mirror of the select
+// merge: dst is a slot that holds split_k of a chunk of len bytes, and the chunk bytes c(u) of the formula above, u < nbytes, get the new values
+// src[u] (less base[u] where there is a base): src and base are the CONTIGUOUS side and address the segment's first byte.  Chunk byte c is stored
+// where split_k keeps it, dst[(c % k) m + c / k] below m k and dst[c] in the tail, and NO OTHER BYTE OF THE SLOT is: the rest is the old chunk,
+// which the encode that follows reads.  select_split_tile tiles the SOURCE as select_tile tiles its destination, and a lane finds its piece the
+// same way.  A lane whose 16 k bytes are 16 whole elements of the chunk inside one piece (select_tile's condition) takes load_elems16, sub_bytes
+// and deinterleave, the fast path of clip_split_tile; every other lane moves its bytes one by one, so PIECES SHORTER THAN 16 ELEMENTS GO WHOLLY
+// THROUGH THE BYTE PATH: correct and slow.  Every granule loaded from src or base holds a byte of the lane's own 16 k bytes of src[0, nbytes) or
+// base[0, nbytes).  The stores leave the lane directly, without the LDS stage of the other tiles: the wanted bytes of different lanes are disjoint
+// but a tile's share of a plane is no contiguous range (neighbouring lanes may lie in different pieces and periods), and the bytes between two
+// lanes' shares are the old chunk's, so there is no granule a second phase could own without reading them back.  The rule is therefore: the 16
+// bytes a lane has for one plane are ONE 16-byte store where they are an aligned granule, and 16 byte stores otherwise; never a read-modify-write.
+// No scratch; the kernel's LDS is that of the clipped and whole splits beside it.
 #pragma once
 #include "frame.hpp"
 
@@ -131,7 +145,7 @@ constexpr u64 PLANES_INVERSE = 0x100;                       // CopySeg::mode = e
 constexpr u64 PLANES_CLIP = 0x200;                          // a merge of which only the bytes [a, b) are stored (k_range_segments and the kernels above it); without PLANES_INVERSE a split that replaces only them (k_patch_segments)
 constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which a periodic byte set is stored (k_strided_segments and k_select_segments)
 constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
-constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone)
+constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone); without PLANES_INVERSE a split that replaces only them (k_patch_select_segments)
 constexpr u32 SELECT_PARAMS = 7;                            // u64 per segment in its side table: rel, stride, q0, r0, nbytes, the piece table's address, m
 
 __host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
@@ -821,29 +835,133 @@ __global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg 
     segments_tile<SEG_SELECT>(segs, tile_start, nseg, clips, periods, selects, (u8 *)lds);
 }
 
-// The kernel of an update's patch launch (bz3_hip_update_device_range, api_frames.hip): clipped splits, whose [a, b) are clips[2 i], clips[2 i + 1],
-// beside segments that are moved whole.  It holds no merge that is clipped, strided or selected, and the kernels above hold no clipped split: a
-// launch has segments of one family (copy_segments sees to it).
-__global__ void __launch_bounds__(COPY_THREADS) k_patch_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
-                                                                 const u64 * __restrict__ clips) {
-    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+// ---- select split --------------------------------------------------------------------------------------------------------------------
+// Tile `tile` of a select split INTO the `len` < 2^31 bytes at `dst`, which hold split_k of a chunk: the chunk bytes c(u), u < nbytes (the head of
+// this file, "Select split"; sp: the segment's SELECT_PARAMS), get src[u]; with D, less base[u].  Workgroups: strided_tiles(nbytes, k); the first
+// 255 lanes of one own 16 k source bytes each (the tiling of the select merge's destination, which needs its 256th lane for the straddling
+// granule alone: here nothing straddles).  No LDS and no barrier: every store leaves the lane that loaded the byte.
+template <int K, bool D>
+__device__ __forceinline__ void select_split_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, const u64 * __restrict__ sp, u32 tile) {
+    const u32 m = len / K, nbytes = (u32)sp[4];
+    const u32 u0 = tile * (PLANES_TILE_ELEMS * K) + 16 * K * threadIdx.x;
+    if (threadIdx.x >= COPY_THREADS - 1 || u0 >= nbytes) return;
+    const u64 * __restrict__ tab = (const u64 *)sp[5];
+    const u32 np = (u32)sp[6], stride = (u32)sp[1];  // (chunk bytes are taken mod 2^32: every c(u) that is written lies below 2^31)
+    const u64 L = tab[2 * np + 1], x = sp[3] + u0;
+    u64 q, r;  // x = q L + r
+    if (L >> 31) {
+        q = x >= L ? 1 : 0;
+        r = x - (q ? L : 0);
+    } else {
+        q = (u32)x / (u32)L;
+        r = (u32)x - (u32)q * (u32)L;
+    }
+    u32 j = piece_of(tab, np, r);
+    u32 cb = (u32)(sp[0] + (sp[2] + q) * sp[1]);  // the chunk byte of the period's first byte
+    const u64 in = r - tab[2 * j + 1], rest = tab[2 * j + 3] - r;  // bytes of piece j before and from the lane's first byte
+    u32 c = cb + (u32)(tab[2 * j] + in);
+    u32 left = rest < 0x7fffffffu ? (u32)rest : 0x7fffffffu;  // (beyond the chunk's 2^31 bytes: no source byte lies behind it)
+    if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
+        u32 w[4 * K], p[K][4];
+        load_elems16<K>((u64)src + u0, w);
+        if (D) {
+            u32 b[4 * K];
+            load_elems16<K>((u64)base + u0, b);
+#pragma unroll
+            for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
+        }
+        if constexpr (K == 1) {
+#pragma unroll
+            for (int n = 0; n < 4; n++) p[0][n] = w[n];
+        } else {
+            deinterleave<K>(w, p);
+        }
+#pragma unroll
+        for (int i = 0; i < K; i++) {  // plane i: the lane's 16 bytes, one granule where they are one
+            const u64 a = (u64)dst + (u64)i * m + c / K;
+            if ((a & 15) == 0) {
+                *(uint4 *)a = make_uint4(p[i][0], p[i][1], p[i][2], p[i][3]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < 16; t++) *(u8 *)(a + t) = (u8)(p[i][t / 4] >> (8 * (t % 4)));
+            }
+        }
+    } else {
+        const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
+        for (u32 u = u0; u < u1; u++) {
+            dst[c < m * K ? (c % K) * m + c / K : c] = D ? (u8)(src[u] - base[u]) : src[u];
+            c++;
+            if (--left == 0 && u + 1 < u1) {  // the next piece that is not empty (there is one: L > 0), in the next period behind the last
+                u64 l;
+                do {
+                    if (++j == np) {
+                        j = 0;
+                        cb += stride;
+                    }
+                    l = tab[2 * j + 3] - tab[2 * j + 1];
+                } while (l == 0);
+                c = cb + (u32)tab[2 * j];
+                left = l < 0x7fffffffu ? (u32)l : 0x7fffffffu;
+            }
+        }
+    }
+}
+
+// One workgroup of an update's patch launch: a select split (SELECT alone compiles it), a clipped split, whose [a, b) are clips[2 i],
+// clips[2 i + 1], or a segment that is moved whole.
+template <bool SELECT>
+__device__ __forceinline__ void patch_segments_tile(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg, const u64 * __restrict__ clips,
+                                                    const u64 * __restrict__ selects, u8 * lds) {
     const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
     const CopySeg sg = segs[lo];
     const u32 tile = blockIdx.x - tile_start[lo];
-    if (!(sg.mode & PLANES_CLIP)) return whole_segment_tile(sg, tile, (u8 *)lds);
     const u8 * src = (const u8 *)sg.src;
     const u8 * base = (const u8 *)sg.base;
     u8 * dst = (u8 *)sg.dst;
+    if (SELECT && (sg.mode & PLANES_SELECT)) {
+        const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
+        const u32 len = (u32)sg.len;
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+            case 1: select_split_tile<1, false>(src, base, dst, len, sp, tile); break;
+            case 2: select_split_tile<2, false>(src, base, dst, len, sp, tile); break;
+            case 4: select_split_tile<4, false>(src, base, dst, len, sp, tile); break;
+            case 8: select_split_tile<8, false>(src, base, dst, len, sp, tile); break;
+            case 1 | 16: select_split_tile<1, true>(src, base, dst, len, sp, tile); break;
+            case 2 | 16: select_split_tile<2, true>(src, base, dst, len, sp, tile); break;
+            case 4 | 16: select_split_tile<4, true>(src, base, dst, len, sp, tile); break;
+            case 8 | 16: select_split_tile<8, true>(src, base, dst, len, sp, tile); break;
+            default: break;
+        }
+        return;
+    }
+    if (!(sg.mode & PLANES_CLIP)) return whole_segment_tile(sg, tile, lds);
     const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
     switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-        case 2: clip_split_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-        case 4: clip_split_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-        case 8: clip_split_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-        case 2 | 16: clip_split_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-        case 4 | 16: clip_split_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
-        case 8 | 16: clip_split_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, (u8 *)lds); break;
+        case 2: clip_split_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+        case 4: clip_split_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+        case 8: clip_split_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+        case 2 | 16: clip_split_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+        case 4 | 16: clip_split_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
+        case 8 | 16: clip_split_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
         default: break;
     }
+}
+
+// The kernel of an update's patch launch (bz3_hip_update_device_range, api_frames.hip): clipped splits beside segments that are moved whole.  It
+// holds no merge that is clipped, strided or selected, and the kernels above hold no clipped split: a launch has segments of one family
+// (copy_segments sees to it).
+__global__ void __launch_bounds__(COPY_THREADS) k_patch_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                 const u64 * __restrict__ clips) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    patch_segments_tile<false>(segs, tile_start, nseg, clips, nullptr, (u8 *)lds);
+}
+
+// The same for a patch launch that holds a select split (bz3_hip_update_device_select, api_frames.hip), whose SELECT_PARAMS are selects[7 i .. 7 i + 6].
+// A kernel of its own, as every kind's is, so that a patch launch without one keeps k_patch_segments.
+__global__ void __launch_bounds__(COPY_THREADS) k_patch_select_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                        const u64 * __restrict__ clips, const u64 * __restrict__ selects) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    patch_segments_tile<true>(segs, tile_start, nseg, clips, selects, (u8 *)lds);
 }
 
 

@@ -399,6 +399,61 @@ BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_si
  * is written.  One launch takes mixed elem_size.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
 
+/* Index update: the write mirror of index decode.  Chosen rows, columns or experts of what a frame decodes to are replaced in one call, and of the
+ * frame only the chunks that hold them are coded again.  phi, L, W = count * L, P_j, `pieces` (a HOST array of 2 m u64) and the piece index j are
+ * exactly those of the index-decode contract above; X, p_j, o_j, c_j and T those of the range-update contract.  A strided update (a slice along an
+ * inner dimension) is the m == 1 case.
+ *   Result.  X' is X with X'[phi(t)] = data[t] for every t < W -- with a base, X'[phi(t)] = (data[t] - base[t]) mod 256.  `base` holds the base's
+ *   bytes OF THE INDEX SET in output order, as in index decode: base[t] pairs with data[t]; NULL means none.  On BZ3_OK, out[0, *out_size) is a
+ *   frame f' with f's 13 header bytes and f's number of chunks.  An untouched chunk is copied verbatim and never decoded.  A touched chunk is
+ *   exactly what bz3_hip_compress_device_delta writes for a block with the content X'[p_j, p_j + o_j), as in the range update.  Consequence: if
+ *   f == bz3_compress(bs, S(x)), then f' == bz3_compress(bs, S(x')) byte for byte.
+ *   Touched, cut and covered chunks.  Chunk j is TOUCHED iff o_j > 0 and [p_j, p_j + o_j) holds phi(t) for some t < W.  It is COVERED iff every
+ *   one of its o_j bytes is such a phi(t): a covered chunk is rebuilt from `data` alone, and its old payload is not looked at.  Otherwise it is
+ *   CUT.  A cut chunk is decoded first, whole and ONCE, however many pieces and periods it holds.  A frame may have any number of cut chunks: a
+ *   column update cuts all of them.
+ *   Validity (a violation is BZ3_ERR_INIT for the whole call before any write).  Every validity rule of bz3_hip_decompress_device_select[_many]
+ *   applies to offset, stride, count, m and pieces.  w != W is invalid: an update names all its bytes.  The bad-elem_size, pointer and device checks
+ *   are those of the range update.  out[0, cap) must not overlap in[0, in_size), data[0, W) or base[0, W) (cap: *out_size on entry).
+ *   Range and capacity.  If W > 0 and phi(W - 1) + 1 > T, the call returns BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor.
+ *   W == 0 (m == 0, L == 0 or count == 0; nothing else of such a request is looked at) gives the verbatim copy of the frame, with the headers
+ *   still checked.  need = 13 + sum over j of (8 + (touched_j ? bz3_bound(o_j) : c_j)), and cap < need is BZ3_ERR_DATA_TOO_BIG before any write: the
+ *   range update's formula, unchanged.
+ *   Order of work and failure are the range update's: the frame header and EVERY chunk header are walked and checked first (the plain walk); then
+ *   every cut chunk of the call is decoded; only then is anything written to `out`.  A frame that fails in either step has its code,
+ *   *out_size = 0 and an untouched `out`; on an encode error afterwards (not expected) *out_size = 0 and out[0, cap) is unspecified.  `in`, `data`,
+ *   `base` and `pieces` are never written; nothing outside out[0, cap) is ever written.
+ *   Normal form and equivalence.  The request is normalised as index decode normalises: empty pieces are dropped and pieces with
+ *   s_j + l_j == s_{j+1} are joined.  A request left in range form -- one piece with count == 1 or stride == L -- returns byte for byte what
+ *   bz3_hip_update_device_range returns for (offset + s_0, data, W), with the same return code and *out_size, through the same launches.
+ * Every other request patches its chunks with its piece table in device memory (16 bytes per piece, uploaded once per call beside the walk's
+ * arguments).  Within a touched chunk the new bytes are one contiguous piece of `data`, scattered into the chunk's byte planes by one launch per
+ * window (planes.hpp k_patch_select_segments), a chunk being one segment however many pieces and periods it holds.  Lanes whose 16 elements are
+ * whole elements of the chunk inside one piece move 16 elements at once; the others byte by byte: pieces shorter than 16 elements are correct
+ * and slow.
+ * _many: the whole-call checks, rcs[] and the independence of frames follow bz3_hip_update_device_range_many; params holds four u64 per frame:
+ * offset, stride, count, m; pieces[i] is frame i's host array of 2 m_i u64; ws[i] must be W_i.  NULL params, or NULL pieces or pieces[i] where
+ * m_i > 0, is BZ3_ERR_INIT.  The touched chunks of all frames share windows in frame order, and the states are sized from the touched list, never
+ * from n_blocks.  A call whose touched chunks exceed one window decodes its cut chunks twice, as the range update does: once to check them before
+ * the first write, once in the window that codes them.  (Parking the decoded chunks instead is open.)  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_update_device_select(uint32_t elem_size, const void * in, size_t in_size, uint64_t offset, uint64_t stride, uint64_t count,
+                                           uint64_t m, const uint64_t * pieces, const void * data, size_t w, const void * base, void * out,
+                                           size_t * out_size);
+BZIP3_API int bz3_hip_update_device_select_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                                const uint64_t params[], const uint64_t * const pieces[], const void * const datas[],
+                                                const size_t ws[], const void * const bases[], void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: bz3_hip_debug_select in the forward direction, one launch of the patch of an index update: n tuples of 12 u64 (src_off, base_off,
+ * dst_off, len, elem_size, rel, stride, q0, r0, nbytes, first_piece, m) relative to `src` / `base` / `dst`, and one host array `pieces` of
+ * 2 n_pieces u64 (s, l) of which a tuple takes the m pieces from first_piece on.  The `len` bytes at dst_off are a slot that holds split_k of a
+ * chunk; for u < nbytes the chunk's byte c(u) -- the formula of bz3_hip_debug_select -- gets the value of byte u at src_off, less byte u at
+ * base_off unless base_off is UINT64_MAX.  Chunk byte c lives at slot[(c % k) * (len / k) + c / k] below (len / k) * k and at slot[c] in the tail.
+ * No other byte of the slot, and nothing of `src` or `base`, is written.  The pieces are NOT normalised, so a uniform list reaches the select
+ * split; a tuple whose bytes lie within one piece becomes the clipped or whole segment of bz3_hip_debug_patch.  BZ3_ERR_INIT for what
+ * bz3_hip_debug_select refuses, and for any bit above the element size in the fifth field (the inverse bit among them).  Returns 0, or
+ * BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_patch_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n,
+                                             const uint64_t * pieces, uint64_t n_pieces);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
