@@ -648,6 +648,75 @@ def decompress_tensor_range(frame, offset, nbytes, out=None, planes=1, base=None
         raise Bz3Error(e.code, "bz3_hip_decompress_device_range", e.outs[0]) from None
 
 
+def _index_set_arg(name, n, offsets, strides, counts, pieces, datas=None):
+    """The index sets of the n frames of decompress_tensors_select and update_tensors_select, validated: (the bytes every set names, the
+    (offset, stride, count) of every frame, its pieces, the C call's `params` and `pieces` arrays).  datas: an update's data tensors, each of which
+    must hold all the bytes of its set."""
+    cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
+    lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
+    if any(len(col) != n for col in cols) or len(lists) != n or (datas is not None and len(datas) != n):
+        raise ValueError(f"{name}: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists" +
+                         ("" if datas is None else f", {len(datas)} data tensors"))
+    params = list(zip(*cols))
+    nbytes = []
+    for i, ((o, s, c), pl) in enumerate(zip(params, lists)):
+        if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
+            raise ValueError(f"{name}: offsets, strides, counts and pieces must not be negative")
+        if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
+            raise ValueError(f"{name}: the pieces of frame {i} do not ascend")
+        L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
+        if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
+            raise ValueError(f"{name}: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
+        if datas is not None and datas[i].numel() != c * L:
+            raise ValueError(f"{name}: datas[{i}] holds {datas[i].numel()} bytes, the index set of frame {i} {c * L}")
+        nbytes.append(c * L)
+    arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
+    ptrs = (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs])
+    ptrs.arrays = arrs  # alive as long as their pointers
+    return nbytes, params, lists, [(C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]), ptrs]
+
+
+def _update_partial(name, frames, datas, request, planes, bases, lib, block_sizes):
+    """The body of update_tensors_range and _select.  request(n, datas) validates the caller's request for the n frames and returns (the C entry
+    point's name, its parameter arrays between in_sizes and datas, whether the 13 header bytes of the frames must be read whatever block_sizes is,
+    recoded(i, block size, chunks): a bound on the chunks of frame i that are coded again; chunks: every frame's count of them, or None where the
+    headers were not read)."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
+    entry, params, heads_needed, recoded = request(n, datas)
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
+    dev = _same_device(frames + datas, name)
+    L = lib or load()
+    chunks = None
+    if heads_needed:
+        heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
+        chunks = [int.from_bytes(bytes(h[9:13]), "little") for h in heads]
+        if block_sizes is None:
+            block_sizes = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
+    bss = [min(max(int(b), _KiB65), _MiB511) for b in block_sizes]  # (a header that lies: the call refuses it, or finds the output too small)
+    if len(bss) != n:
+        raise ValueError(f"{name}: {n} frames and {len(bss)} block sizes")
+    caps = [f.numel() + recoded(i, bs, chunks) * L.bz3_bound(bs) for i, (f, bs) in enumerate(zip(frames, bss))]
+    outs = _carve(sum(caps), caps, dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    torch.cuda.synchronize(dev)
+    rc = getattr(L, entry)(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), *params, _ptrs(datas),
+                           (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(codes[idx], entry, index=idx, codes=codes, outs=res)
+    return res
+
+
 def update_tensors_range(frames, offsets, datas, planes=1, bases=None, lib=None, block_sizes=None):
     """New frames in which the bytes [offsets[i], offsets[i] + datas[i].numel()) of what frames[i] decodes to are replaced by datas[i], for many
     frames in ONE call (bz3_hip_update_device_range_many) and one synchronisation: only the chunks that hold bytes of a range are coded again, of
@@ -660,41 +729,15 @@ def update_tensors_range(frames, offsets, datas, planes=1, bases=None, lib=None,
     They only size the outputs, which are views of one allocation of frames[i].numel() + (datas[i].numel() // block size + 2) *
     bz3_bound(block size) bytes each (.clone() one to drop the rest).  The inputs are never written.  Raises Bz3Error with .index / .codes / .outs
     as compress_tensors does; a frame that fails has no output.  [] returns []."""
-    import torch
+    def request(n, datas):
+        offs = [int(o) for o in offsets]
+        if len(offs) != n or len(datas) != n:
+            raise ValueError(f"update_tensors_range: {n} frames, {len(offs)} offsets and {len(datas)} data tensors")
+        if any(o < 0 for o in offs):
+            raise ValueError("update_tensors_range: offsets must not be negative")
+        return "bz3_hip_update_device_range_many", [(C.c_uint64 * n)(*offs)], block_sizes is None, lambda i, bs, chunks: datas[i].numel() // bs + 2
 
-    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
-    n = len(frames)
-    offs = [int(o) for o in offsets]
-    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
-    if len(offs) != n or len(datas) != n:
-        raise ValueError(f"update_tensors_range: {n} frames, {len(offs)} offsets and {len(datas)} data tensors")
-    if any(o < 0 for o in offs):
-        raise ValueError("update_tensors_range: offsets must not be negative")
-    if not frames:
-        return []
-    ks = _planes_arg(planes, n)
-    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
-    dev = _same_device(frames + datas, "update_tensors_range")
-    L = lib or load()
-    if block_sizes is None:
-        heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
-        block_sizes = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
-    bss = [min(max(int(b), _KiB65), _MiB511) for b in block_sizes]  # (a header that lies: the call refuses it, or finds the output too small)
-    if len(bss) != n:
-        raise ValueError(f"update_tensors_range: {n} frames and {len(bss)} block sizes")
-    caps = [f.numel() + (d.numel() // bs + 2) * L.bz3_bound(bs) for f, d, bs in zip(frames, datas, bss)]
-    outs = _carve(sum(caps), caps, dev)
-    out_sizes = (C.c_size_t * n)(*caps)
-    rcs = (C.c_int * n)()
-    torch.cuda.synchronize(dev)
-    rc = L.bz3_hip_update_device_range_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]), (C.c_uint64 * n)(*offs), _ptrs(datas),
-                                            (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
-    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
-        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(codes[idx], "bz3_hip_update_device_range_many", index=idx, codes=codes, outs=res)
-    return res
+    return _update_partial("update_tensors_range", frames, datas, request, planes, bases, lib, block_sizes)
 
 
 def update_tensor_range(frame, offset, data, planes=1, base=None, lib=None, block_size=None):
@@ -731,56 +774,12 @@ def update_tensors_select(frames, offsets, strides, counts, pieces, datas, plane
     size the outputs, views of one allocation of frames[i].numel() + min(chunks, W // bs + 2 * pieces * counts[i]) * bz3_bound(bs) bytes each
     (pieces: after joining neighbours that touch; .clone() a result to drop the rest).  The inputs are never written.  Raises Bz3Error with
     .index / .codes / .outs as update_tensors_range does; a frame that fails has no output.  [] returns []."""
-    import torch
+    def request(n, datas):
+        _, params, lists, args = _index_set_arg("update_tensors_select", n, offsets, strides, counts, pieces, datas)
+        joined = [_joined_pieces(pl) for pl in lists]
+        return "bz3_hip_update_device_select_many", args, True, lambda i, bs, chunks: min(chunks[i], datas[i].numel() // bs + 2 * joined[i] * params[i][2])
 
-    name = "update_tensors_select"
-    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
-    n = len(frames)
-    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
-    cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
-    lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
-    if any(len(col) != n for col in cols) or len(lists) != n or len(datas) != n:
-        raise ValueError(f"{name}: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists, {len(datas)} data tensors")
-    params = list(zip(*cols)) if n else []
-    for i, ((o, s, c), pl, d) in enumerate(zip(params, lists, datas)):
-        if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
-            raise ValueError(f"{name}: offsets, strides, counts and pieces must not be negative")
-        if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
-            raise ValueError(f"{name}: the pieces of frame {i} do not ascend")
-        L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
-        if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
-            raise ValueError(f"{name}: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
-        if d.numel() != c * L:
-            raise ValueError(f"{name}: datas[{i}] holds {d.numel()} bytes, the index set of frame {i} {c * L}")
-    if not frames:
-        return []
-    ks = _planes_arg(planes, n)
-    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
-    dev = _same_device(frames + datas, name)
-    L = lib or load()
-    heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
-    if block_sizes is None:
-        block_sizes = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
-    bss = [min(max(int(b), _KiB65), _MiB511) for b in block_sizes]  # (a header that lies: the call refuses it, or finds the output too small)
-    if len(bss) != n:
-        raise ValueError(f"{name}: {n} frames and {len(bss)} block sizes")
-    chunks = [int.from_bytes(bytes(h[9:13]), "little") for h in heads]
-    caps = [f.numel() + min(nb, d.numel() // bs + 2 * _joined_pieces(pl) * c) * L.bz3_bound(bs) for f, d, bs, nb, pl, (_, _, c) in zip(frames, datas, bss, chunks, lists, params)]
-    outs = _carve(sum(caps), caps, dev)
-    out_sizes = (C.c_size_t * n)(*caps)
-    rcs = (C.c_int * n)()
-    arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
-    ptrs = (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs])
-    torch.cuda.synchronize(dev)
-    rc = L.bz3_hip_update_device_select_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
-                                             (C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]), ptrs, _ptrs(datas),
-                                             (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
-    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
-    if rc != BZ3_OK:
-        codes = list(rcs)
-        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
-        raise Bz3Error(codes[idx], "bz3_hip_update_device_select_many", index=idx, codes=codes, outs=res)
-    return res
+    return _update_partial("update_tensors_select", frames, datas, request, planes, bases, lib, block_sizes)
 
 
 def update_tensor_select(frame, offset, stride, count, pieces, data, planes=1, base=None, lib=None, block_size=None):
@@ -842,25 +841,8 @@ def decompress_tensors_select(frames, offsets, strides, counts, pieces, outs=Non
     counts[i] > 1, and for a set that does not fit 64 bits.  The same frame may appear more than once.  Raises Bz3Error with .index /
     .codes / .outs (per frame the bytes committed before its error) as decompress_tensors does.  [] returns []."""
     def request(n):
-        cols = [[int(v) for v in col] for col in (offsets, strides, counts)]
-        lists = [[(int(a), int(l)) for a, l in pl] for pl in pieces]
-        if any(len(col) != n for col in cols) or len(lists) != n:
-            raise ValueError(f"decompress_tensors_select: {n} frames and {[len(col) for col in cols]} offsets, strides and counts, {len(lists)} piece lists")
-        params = list(zip(*cols))
-        nbytes = []
-        for i, ((o, s, c), pl) in enumerate(zip(params, lists)):
-            if min(o, s, c) < 0 or any(a < 0 or l < 0 for a, l in pl):
-                raise ValueError("decompress_tensors_select: offsets, strides, counts and pieces must not be negative")
-            if any(a + l >= 1 << 64 for a, l in pl) or any(a + l > b for (a, l), (b, _) in zip(pl, pl[1:])):
-                raise ValueError(f"decompress_tensors_select: the pieces of frame {i} do not ascend")
-            L, end = sum(l for _, l in pl), pl[-1][0] + pl[-1][1] if pl else 0
-            if L and c and ((c > 1 and s < end) or c * L >= 1 << 64 or o + (c - 1) * s + end >= 1 << 64):
-                raise ValueError(f"decompress_tensors_select: ({o}, {s}, {c}) and the pieces of frame {i} are no index set")
-            nbytes.append(c * L)
-        arrs = [(C.c_uint64 * max(1, 2 * len(pl)))(*[v for p in pl for v in p]) for pl in lists]
-        ptrs = (C.POINTER(C.c_uint64) * n)(*[C.cast(a, C.POINTER(C.c_uint64)) for a in arrs])
-        ptrs.arrays = arrs  # alive as long as their pointers
-        return nbytes, "bz3_hip_decompress_device_select_many", [(C.c_uint64 * (4 * n))(*[v for p, pl in zip(params, lists) for v in (*p, len(pl))]), ptrs]
+        nbytes, _, _, args = _index_set_arg("decompress_tensors_select", n, offsets, strides, counts, pieces)
+        return nbytes, "bz3_hip_decompress_device_select_many", args
 
     return _decompress_partial("decompress_tensors_select", frames, request, outs, planes, bases, lib)
 
@@ -1184,8 +1166,8 @@ def _update_rows_many(ps, rows, bases, lib):
     bz3_hip_update_device_range_many call.  bases[i]: the same rows of the base.  Every argument is checked before any GPU work."""
     import torch
 
-    offs, raws, braws = [], [], []
-    for i, (p, (start, values), b) in enumerate(zip(ps, rows, _bases_arg(bases, len(ps)))):
+    offs = []
+    for i, (p, (start, values)) in enumerate(zip(ps, rows)):
         rb = _row_bytes(p, f"tensor {i}")
         start = int(start)
         if not isinstance(values, torch.Tensor) or values.device.type != "cuda":
@@ -1194,18 +1176,10 @@ def _update_rows_many(ps, rows, bases, lib):
             raise TypeError(f"update: the rows of tensor {i} must be {p.dtype} of shape (rows, {', '.join(map(str, p.shape[1:]))})")
         if not 0 <= start <= start + values.shape[0] <= p.shape[0]:
             raise ValueError(f"update: rows ({start}, {start + values.shape[0]}) of a tensor of {p.shape[0]} rows")
-        if p.delta and b is None:
-            raise ValueError(f"update: tensor {i} was packed against a base, whose rows are needed to code the new ones")
-        if not p.delta:
-            b = None
-        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != tuple(values.shape):
-            raise ValueError(f"update: base {i} must hold the same rows of the base: {p.dtype} {tuple(values.shape)}")
-        raw = _as_bytes(values, f"rows {i}")
         offs.append(start * rb)
-        raws.append(raw)
-        braws.append(_base_bytes(b, raw.numel(), p.frame.device, f"base {i}"))
-    frames = update_tensors_range([p.frame for p in ps], offs, raws, planes=[p.planes for p in ps], bases=braws, lib=lib, block_sizes=[p.block_size for p in ps])
-    return [PackedTensor(f, p.dtype, p.shape, p.planes, p.block_size, p.nbytes, p.delta, p.base_crc, None) for f, p in zip(frames, ps)]
+    return _update_parts_many(ps, [tuple(v.shape) for _, v in rows], [v for _, v in rows], bases, lib, "rows",
+                              lambda i: (f"tensor {i}", f"the rows of tensor {i}", f"base {i}"),
+                              lambda frames, raws, braws, **kw: update_tensors_range(frames, offs, raws, bases=braws, **kw))
 
 
 def update_tensor_rows(p, start, values, base=None, lib=None):
@@ -1415,32 +1389,44 @@ def unpack_tensor_index(p, dim, index, out=None, base=None, lib=None):
     return out
 
 
-def _update_parts_many(ps, sels, values, bases, lib, names=None):
-    """For every PackedTensor sels[i] = (dim, index) (strictly increasing) or a slice (dim, start, stop): the PackedTensors with that part replaced
-    by values[i], a tensor of the part's shape, through ONE bz3_hip_update_device_select_many call.  bases[i]: the same part of the base.  Every
-    argument is checked before any GPU work."""
+def _update_parts_many(ps, shapes, values, bases, lib, what, words, update):
+    """What the partial update calls share: the PackedTensors with a part of shapes[i] replaced by values[i], a tensor of that shape, through the
+    ONE call update(frames, the values' bytes, the bases' bytes, planes=, lib=, block_sizes=), which returns the new frames.  bases[i]: the same part
+    of the base, `what` its name in messages ("rows", "part"); words(i): tensor i's name, that of its values and that of its base.  Every argument
+    is checked before any GPU work."""
     import torch
 
-    reqs, raws, braws = [], [], []
-    for i, (p, sel, v, b) in enumerate(zip(ps, sels, values, _bases_arg(bases, len(ps)))):
-        what = f"tensor {i}" if names is None else repr(names[i])
-        shape, q, _ = _index_of(p, sel, f"update: {what}")
+    raws, braws = [], []
+    for i, (p, shape, v, b) in enumerate(zip(ps, shapes, values, _bases_arg(bases, len(ps)))):
+        name, vname, bname = words(i)
         if not isinstance(v, torch.Tensor) or v.device.type != "cuda":
-            raise TypeError(f"update: the values of {what} must be a torch tensor on a GPU")
+            raise TypeError(f"update: {vname} must be a torch tensor on a GPU")
         if v.dtype != p.dtype or tuple(v.shape) != tuple(shape):
-            raise TypeError(f"update: the values of {what} must be {p.dtype} of shape {tuple(shape)}")
+            raise TypeError(f"update: {vname} must be {p.dtype} of shape {tuple(shape)}")
         if p.delta and b is None:
-            raise ValueError(f"update: {what} was packed against a base, whose part is needed to code the new one")
+            raise ValueError(f"update: {name} was packed against a base, whose {'rows are needed to code the new ones' if what == 'rows' else what + ' is needed to code the new one'}")
         if not p.delta:
             b = None
         elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != tuple(shape):
-            raise ValueError(f"update: the base of {what} must hold the same part of the base: {p.dtype} {tuple(shape)}")
-        raw = _as_bytes(v, f"the values of {what}")
-        reqs.append(q)
+            raise ValueError(f"update: {bname} must hold the same {what} of the base: {p.dtype} {tuple(shape)}")
+        raw = _as_bytes(v, vname)
         raws.append(raw)
-        braws.append(_base_bytes(b, raw.numel(), p.frame.device, f"the base of {what}"))
-    frames = update_tensors_select([p.frame for p in ps], *zip(*reqs), raws, planes=[p.planes for p in ps], bases=braws, lib=lib, block_sizes=[p.block_size for p in ps])
+        braws.append(_base_bytes(b, raw.numel(), p.frame.device, bname))
+    frames = update([p.frame for p in ps], raws, braws, planes=[p.planes for p in ps], lib=lib, block_sizes=[p.block_size for p in ps])
     return [PackedTensor(f, p.dtype, p.shape, p.planes, p.block_size, p.nbytes, p.delta, p.base_crc, None) for f, p in zip(frames, ps)]
+
+
+def _update_index_many(ps, sels, values, bases, lib, names=None):
+    """For every PackedTensor sels[i] = (dim, index) (strictly increasing) or a slice (dim, start, stop): the PackedTensors with that part replaced
+    by values[i], through ONE bz3_hip_update_device_select_many call.  bases[i]: the same part of the base."""
+    whats = [f"tensor {i}" if names is None else repr(names[i]) for i in range(len(ps))]
+    shapes, reqs = [], []
+    for p, sel, what in zip(ps, sels, whats):
+        shape, q, _ = _index_of(p, sel, f"update: {what}")
+        shapes.append(shape)
+        reqs.append(q)
+    return _update_parts_many(ps, shapes, values, bases, lib, "part", lambda i: (whats[i], f"the values of {whats[i]}", f"the base of {whats[i]}"),
+                              lambda frames, raws, braws, **kw: update_tensors_select(frames, *zip(*reqs), raws, bases=braws, **kw))
 
 
 def update_tensor_slice(p, dim, start, stop, values, base=None, lib=None):
@@ -1453,7 +1439,7 @@ def update_tensor_slice(p, dim, start, stop, values, base=None, lib=None):
     slice's shape (TypeError otherwise; any strides); ValueError for a 0-d tensor, a bad `dim` and unless 0 <= start <= stop <= p.shape[dim].  All
     of that is checked before any GPU work.  A tensor packed against a base needs `base`: THE SAME SLICE of the base.  Everything but `crc`,
     which is None as after update_tensor_rows, is carried over; `p` is unchanged."""
-    return _update_parts_many([p], [(dim, start, stop)], [values], [base], lib)[0]
+    return _update_index_many([p], [(dim, start, stop)], [values], [base], lib)[0]
 
 
 def _update_index_arg(p, dim, index, values, has_base, what):
@@ -1494,7 +1480,7 @@ def update_tensor_index(p, dim, index, values, base=None, lib=None):
     if not isinstance(p, PackedTensor):
         raise TypeError("update: a PackedTensor is expected")
     sel, values = _update_index_arg(p, dim, index, values, p.delta, "update_tensor_index")
-    return _update_parts_many([p], [sel], [values], [base], lib)[0]
+    return _update_index_many([p], [sel], [values], [base], lib)[0]
 
 
 def update_state_dict(packed, rows=None, slices=None, index=None, base=None, lib=None):
@@ -1538,7 +1524,7 @@ def update_state_dict(packed, rows=None, slices=None, index=None, base=None, lib
             sel, vals = _update_index_arg(p, dim, idx, vals, p.delta, f"update_state_dict: {k!r}")
             sels.append(sel)
         values.append(vals)
-    out.update(zip(names, _update_parts_many([packed[k] for k in names], sels, values, [None if base is None else base.get(k) for k in names], lib, names)))
+    out.update(zip(names, _update_index_many([packed[k] for k in names], sels, values, [None if base is None else base.get(k) for k in names], lib, names)))
     return out
 
 

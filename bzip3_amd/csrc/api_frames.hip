@@ -1,7 +1,8 @@
 // api_frames.hip -- the device-resident frame API of include/bz3_hip.h (plain, byte planes, delta, decoded sizes, and the partial decode calls:
 // range, strided, select), its debug entry points and the batched CRC.  The only unit that includes frame.hpp and planes.hpp: their kernels are
 // ordinary definitions.  The partial decode calls share one request form (Request), one list of gather segments with their side tables
-// (GatherList) and one body (decompress_frames); what differs between them is how an entry point reads its parameters.
+// (GatherList) and one body (decompress_frames); what differs between them is how an entry point reads its parameters.  The two update calls
+// share the same request form and front (request_front) and one body (update_frames).
 #include <functional>
 
 #include "api_internal.hpp"
@@ -344,6 +345,14 @@ struct DeviceFrames {
         if (h.size() > lay.tab - lay.hdr) throw std::length_error("staged header overflow");
         if (!h.empty()) HIP_CHECK(hipMemcpyAsync(meta + lay.hdr, h.data(), h.size(), hipMemcpyHostToDevice, s));
     }
+    // The piece tables of a call, one after the other: one upload per call.  Returns the device address of the first.
+    u64 upload_pieces(const std::vector<u64> & tables) {
+        if (!tables.empty()) {
+            HIP_CHECK(hipMemcpyAsync(meta + lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+        return (u64)(meta + lay.pieces);
+    }
     // One launch of k_frame_walk_many over args.size() frames and one read-back: tails[q] is frame q's resume state, its
     // records are rec[args[q].rec_base ..].
     void walk(const std::vector<WalkArg> & args, std::vector<WalkChunk> & rec, std::vector<WalkTail> & tails) {
@@ -409,6 +418,34 @@ void walk_frame_headers(DeviceFrames & f, s32 n, const u8 * const * ins, const s
         }
     }
 }
+
+// The buffers of a call's walks over its chunk headers, and one round of plain walks: args[q] walks frame who[q], whose records are
+// rec[args[q].rec_base ..] and whose resume state is tails[q].
+struct WalkRound {
+    std::vector<WalkArg> args;
+    std::vector<s32> who;
+    std::vector<WalkChunk> rec;
+    std::vector<WalkTail> tails;
+    // Plans and runs a round over the frames i of [from, n) with want(i) that have a chunk left, in order: a frame's limit is what is left of it or
+    // of the `budget` of records, its capacity buf_max(i).  One launch and one read-back; false, and neither, where no such frame is left.
+    bool plain(DeviceFrames & f, const std::vector<WalkPos> & pos, const u8 * const * ins, const size_t * in_sizes, s32 from, s32 n, u32 budget,
+               const std::function<bool(s32)> & want, const std::function<size_t(s32)> & buf_max) {
+        args.clear();
+        who.clear();
+        u32 base = 0;
+        for (s32 i = from; i < n && budget; i++) {
+            if (!want(i) || pos[i].done == pos[i].n_blocks) continue;
+            const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
+            args.push_back(pos[i].arg(ins[i], in_sizes[i], buf_max(i), lim, base));
+            who.push_back(i);
+            base += lim;
+            budget -= lim;
+        }
+        if (args.empty()) return false;
+        f.walk(args, rec, tails);
+        return true;
+    }
+};
 
 // ---- compress: n frames whose buffers passed the pointer checks, on device dev --------------------------------------------
 // Blocks go through windows in frame order, across frame boundaries: scatter (one copy launch), run_encode (one CM launch
@@ -684,10 +721,11 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     if (!any) return;
     DeviceFrames f;
     std::vector<Chunk> win;
-    std::vector<WalkArg> args;
-    std::vector<s32> who;
-    std::vector<WalkChunk> rec;
-    std::vector<WalkTail> tails;
+    WalkRound round;
+    auto & args = round.args;
+    auto & who = round.who;
+    auto & rec = round.rec;
+    auto & tails = round.tails;
     s32 cur = 0;  // frames before it are finished
     // The next chunks of the live frames from `cur` on, W at most in all, into `win` (frame order).  A frame's limit is what
     // is left of it or of the window; only a frame that stops at a header error walks fewer, and then the frames behind
@@ -695,19 +733,7 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     auto collect = [&](size_t W) {
         win.clear();
         while (win.size() < W) {
-            args.clear();
-            who.clear();
-            u32 budget = (u32)(W - win.size()), base = 0;
-            for (s32 i = cur; i < n && budget; i++) {
-                if (!live[i] || fr[i].pending != BZ3_OK || pos[i].done == pos[i].n_blocks) continue;
-                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
-                args.push_back(pos[i].arg(ins[i], in_sizes[i], fr[i].buf_max, lim, base));
-                who.push_back(i);
-                base += lim;
-                budget -= lim;
-            }
-            if (args.empty()) return;
-            f.walk(args, rec, tails);
+            if (!round.plain(f, pos, ins, in_sizes, cur, n, (u32)(W - win.size()), [&](s32 i) { return live[i] && fr[i].pending == BZ3_OK; }, [&](s32 i) { return fr[i].buf_max; })) return;
             bool stopped = false;
             for (size_t q = 0; q < who.size(); q++) {
                 const s32 i = who[q];
@@ -768,12 +794,9 @@ void decompress_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const 
     try {
         if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64))) throw std::runtime_error("no device");
         DeviceGuard g(dev);
-        if (!tables.empty()) {  // the piece tables: one upload per call
-            HIP_CHECK(hipMemcpyAsync(f.meta + f.lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, f.s));
-            HIP_CHECK(hipStreamSynchronize(f.s));
-            for (s32 i = 0; i < n; i++)
-                if (fr[i].sel) fr[i].d_tab += (u64)(f.meta + f.lay.pieces);
-        }
+        const u64 d_pieces = f.upload_pieces(tables);
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].sel) fr[i].d_tab += d_pieces;
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
         for (s32 i = 0; i < n; i++) {
             if (range && fr[i].buf_max == 0) live[i] = 0;  // nothing wanted: the frame header alone was checked
@@ -882,34 +905,18 @@ void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t *
         if (!f.open(dev, (size_t)n)) throw std::runtime_error("no device");
         DeviceGuard g(dev);
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // a block size bz3_new refuses: BZ3_ERR_INIT, what bz3_decompress reports for it
-        std::vector<WalkArg> args;
-        std::vector<s32> who;
-        std::vector<WalkChunk> rec;
-        std::vector<WalkTail> tails;
-        for (;;) {
-            args.clear();
-            who.clear();
-            u32 budget = (u32)WALK_RECORDS, base = 0;
-            for (s32 i = 0; i < n && budget; i++) {
-                if (!live[i]) continue;
-                if (pos[i].done == pos[i].n_blocks) {
-                    live[i] = 0;
-                    continue;
-                }
-                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
-                args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, lim, base));
-                who.push_back(i);
-                base += lim;
-                budget -= lim;
-            }
-            if (args.empty()) break;
-            f.walk(args, rec, tails);
-            for (size_t q = 0; q < who.size(); q++) {
-                const s32 i = who[q];
-                pos[i].take(tails[q]);
+        WalkRound round;
+        auto unfinished = [&](s32 i) {  // (a frame whose walk is over is done with: no later failure touches its code)
+            if (pos[i].done == pos[i].n_blocks) live[i] = 0;
+            return live[i] != 0;
+        };
+        while (round.plain(f, pos, ins, in_sizes, 0, n, (u32)WALK_RECORDS, unfinished, [](s32) { return (size_t)SIZE_MAX; })) {
+            for (size_t q = 0; q < round.who.size(); q++) {
+                const s32 i = round.who[q];
+                pos[i].take(round.tails[q]);
                 decoded[i] = pos[i].planned;
-                if (tails[q].err != BZ3_OK) {
-                    rcs[i] = tails[q].err;
+                if (round.tails[q].err != BZ3_OK) {
+                    rcs[i] = round.tails[q].err;
                     live[i] = 0;
                 }
             }
@@ -988,36 +995,19 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     try {
         if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64), 2)) throw std::runtime_error("no device");
         DeviceGuard g(dev);
-        if (!tables.empty()) {  // the piece tables: one upload per call
-            HIP_CHECK(hipMemcpyAsync(f.meta + f.lay.pieces, tables.data(), tables.size() * sizeof(u64), hipMemcpyHostToDevice, f.s));
-            HIP_CHECK(hipStreamSynchronize(f.s));
-            for (s32 i = 0; i < n; i++)
-                if (fr[i].sel) fr[i].d_tab += (u64)(f.meta + f.lay.pieces);
-        }
+        const u64 d_pieces = f.upload_pieces(tables);
+        for (s32 i = 0; i < n; i++)
+            if (fr[i].sel) fr[i].d_tab += d_pieces;
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
-        std::vector<WalkArg> args;
-        std::vector<s32> who;
-        std::vector<WalkChunk> rec;
-        std::vector<WalkTail> tails;
-        for (;;) {  // every chunk header of every live frame
-            args.clear();
-            who.clear();
-            u32 budget = (u32)WALK_RECORDS, base = 0;
-            for (s32 i = 0; i < n && budget; i++) {
-                if (!live[i] || pos[i].done == pos[i].n_blocks) continue;
-                const u32 lim = std::min(pos[i].n_blocks - pos[i].done, budget);
-                args.push_back(pos[i].arg(ins[i], in_sizes[i], SIZE_MAX, lim, base));
-                who.push_back(i);
-                base += lim;
-                budget -= lim;
-            }
-            if (args.empty()) break;
-            f.walk(args, rec, tails);
-            for (size_t q = 0; q < who.size(); q++) {
-                const s32 i = who[q];
+        WalkRound round;
+        // every chunk header of every live frame
+        while (round.plain(f, pos, ins, in_sizes, 0, n, (u32)WALK_RECORDS, [&](s32 i) { return live[i] != 0; }, [](s32) { return (size_t)SIZE_MAX; })) {
+            for (size_t q = 0; q < round.who.size(); q++) {
+                const s32 i = round.who[q];
+                const WalkTail & tail = round.tails[q];
                 Frame & x = fr[i];
-                for (u32 r = 0; r < tails[q].count; r++) {
-                    const WalkChunk & c = rec[args[q].rec_base + r];
+                for (u32 r = 0; r < tail.count; r++) {
+                    const WalkChunk & c = round.rec[round.args[q].rec_base + r];
                     const u64 p = c.out_off, o = (u64)c.orig;
                     const u64 ta = o > 0 ? x.below(p) : 0, tb = o > 0 ? x.below(p + o) : 0;  // (touched iff the chunk holds phi(t) for some t < w)
                     const bool touched = tb > ta;
@@ -1026,8 +1016,8 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
                     touch.push_back({i, c, ta, tb});
                     x.chunks++;
                 }
-                pos[i].take(tails[q]);
-                if (tails[q].err != BZ3_OK) fail(i, tails[q].err);
+                pos[i].take(tail);
+                if (tail.err != BZ3_OK) fail(i, tail.err);
             }
         }
         for (s32 i = 0; i < n; i++) {
@@ -1217,6 +1207,33 @@ bool elem_sizes_ok(s32 n, const u32 * elem_sizes) {
 }
 
 
+// The front of the partial decode and the update calls over n > 0 frames: the whole-call checks they share (args_ok: the caller's own pointers and
+// parameters), frame i's request from make(i, request) (false: an invalid one), and in `dev` the call's device as frames_device names it, which the
+// caller judges by its own rule.  False: the call fails, before any write, with BZ3_ERR_INIT.
+bool request_front(s32 n, const u32 * elem_sizes, const void * const * ins, const size_t * in_sizes, bool args_ok, void * const * outs, size_t * out_sizes, int * rcs,
+                   const std::function<bool(s32, Request &)> & make, std::vector<Request> & reqs, int & dev) {
+    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !args_ok) return false;
+    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return false;
+    reqs.resize((size_t)n);
+    for (s32 i = 0; i < n; i++)
+        if (!make(i, reqs[(size_t)i])) return false;
+    dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    return true;
+}
+
+// Frame i's index set of a select call, params[4 i ..] = (offset, stride, count, m) and the m pairs (s_j, l_j) of pieces[i] in host memory, into t.
+// False for a set that bz3_hip.h calls invalid; else W = count L, the bytes it names (0: none, and offset and stride were not looked at).
+bool read_index_set(const u64 * params, const u64 * const * pieces, s32 i, PieceTable & t, u64 & W) {
+    const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
+    W = 0;
+    if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return false;
+    if (t.L == 0 || count == 0) return true;
+    const unsigned __int128 all = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
+    if ((count > 1 && stride < t.given_end) || all > UINT64_MAX || last > UINT64_MAX) return false;
+    W = (u64)all;
+    return true;
+}
+
 // The three partial decode calls: the whole-call checks they share, frame i's request from make(i, request) (false: an invalid one, which fails
 // the whole call before any write), then decompress_frames.  A base is device memory of the same GPU, and `out` is the base itself or does not
 // overlap it; the overlap is judged on the w = min(out_sizes[i], base_sizes[i], what the request names) bytes the call can touch of each: two
@@ -1225,13 +1242,10 @@ int decompress_requests(int32_t n, const uint32_t elem_sizes[], const void * con
                         const size_t base_sizes[], void * const outs[], size_t out_sizes[], int rcs[],
                         const std::function<bool(s32, Request &)> & make) {
     if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !outs || !out_sizes || !rcs || !params_ok || (bases && !base_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    std::vector<Request> reqs((size_t)n);
-    for (s32 i = 0; i < n; i++)
-        if (!make(i, reqs[(size_t)i])) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev == -2) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    std::vector<Request> reqs;
+    int dev = -2;
+    if (!request_front(n, elem_sizes, ins, in_sizes, params_ok && (!bases || base_sizes), outs, out_sizes, rcs, make, reqs, dev) || dev == -2)
+        return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
     for (s32 i = 0; bases && i < n; i++) {
         if (!bases[i] || !base_sizes[i]) continue;
         const u64 w = std::min<u64>({(u64)out_sizes[i], (u64)base_sizes[i], reqs[(size_t)i].wanted}), x = (u64)outs[i], y = (u64)bases[i];
@@ -1384,15 +1398,11 @@ BZIP3_API int bz3_hip_decompress_device_select_many(int32_t n, const uint32_t el
                                                     void * const outs[], size_t out_sizes[], int rcs[]) {
     std::vector<PieceTable> tables;  // (sized once the whole-call checks have passed)
     return decompress_requests(n, elem_sizes, ins, in_sizes, params != nullptr, bases, base_sizes, outs, out_sizes, rcs, [&](s32 i, Request & r) {
-        const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
         tables.resize((size_t)n);
         PieceTable & t = tables[(size_t)i];
-        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return false;
-        if (t.L && count) {  // (else W = 0)
-            const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
-            if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX) return false;
-        }
-        r = Request::select(offset, stride, count, t);
+        u64 W;
+        if (!read_index_set(params, pieces, i, t, W)) return false;
+        r = Request::select(params[4 * i], params[4 * i + 1], params[4 * i + 2], t);
         return true;
     });
 }
@@ -1425,13 +1435,10 @@ namespace {
 int update_requests(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], bool params_ok, const void * const datas[], const size_t ws[],
                     const void * const bases[], void * const outs[], size_t out_sizes[], int rcs[], const std::function<bool(s32, Request &)> & make) {
     if (n == 0) return BZ3_OK;
-    if (n < 0 || !ins || !in_sizes || !datas || !ws || !outs || !out_sizes || !rcs || !params_ok) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    if (elem_sizes && !elem_sizes_ok(n, elem_sizes)) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    std::vector<Request> reqs((size_t)n);
-    for (s32 i = 0; i < n; i++)
-        if (!make(i, reqs[(size_t)i])) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
-    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
-    if (dev < 0) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (every frame is empty and has no room: nothing to walk, nowhere to write)
+    std::vector<Request> reqs;
+    int dev = -2;
+    if (!request_front(n, elem_sizes, ins, in_sizes, params_ok && datas && ws, outs, out_sizes, rcs, make, reqs, dev) || dev < 0)
+        return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (dev == -1: every frame is empty and has no room: nothing to walk, nowhere to write)
     for (s32 i = 0; i < n; i++) {
         const void * base = bases ? bases[i] : nullptr;
         if (ws[i] && (device_of(datas[i]) != dev || (base && device_of(base) != dev))) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
@@ -1462,16 +1469,15 @@ BZIP3_API int bz3_hip_update_device_select_many(int32_t n, const uint32_t elem_s
                                                 void * const outs[], size_t out_sizes[], int rcs[]) {
     std::vector<PieceTable> tables;  // (sized once the whole-call checks have passed)
     return update_requests(n, elem_sizes, ins, in_sizes, params != nullptr, datas, ws, bases, outs, out_sizes, rcs, [&](s32 i, Request & r) {
-        const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2], m = params[4 * i + 3];
+        const u64 offset = params[4 * i], stride = params[4 * i + 1], count = params[4 * i + 2];
         tables.resize((size_t)n);
         PieceTable & t = tables[(size_t)i];
-        if (!t.take(m ? (pieces ? pieces[i] : nullptr) : nullptr, m)) return false;
-        if (t.L == 0 || count == 0) {  // W = 0: the verbatim copy
+        u64 W;
+        if (!read_index_set(params, pieces, i, t, W) || W != (u64)ws[i]) return false;
+        if (W == 0) {  // the verbatim copy
             r = Request::range(0);
-            return ws[i] == 0;
+            return true;
         }
-        const unsigned __int128 W = (unsigned __int128)count * t.L, last = (unsigned __int128)offset + (unsigned __int128)(count - 1) * stride + t.given_end;
-        if ((count > 1 && stride < t.given_end) || W > UINT64_MAX || last > UINT64_MAX || (u64)W != (u64)ws[i]) return false;
         if (t.m == 1 && (count == 1 || stride == t.L)) {
             r = Request::range(offset + t.s(0));
         } else {
@@ -1587,6 +1593,21 @@ int32_t debug_move_segments(const void * src, const void * base, void * dst, con
 
 // The base address of a debug tuple's segment: base_off == UINT64_MAX is no base.
 u64 debug_base(const void * base, u64 base_off) { return base_off == UINT64_MAX ? 0 : (u64)base + base_off; }
+
+// The body of bz3_hip_debug_range and bz3_hip_debug_patch: n septuples whose fifth field must be elem_size | mode_bits << 8 and whose [a, b) must lie
+// in their len bytes, one launch of the segments add(list, septuple) makes of them.
+int32_t debug_clips(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, u64 mode_bits, const std::function<void(GatherList &, const uint64_t *)> & add) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    bool any_base = false;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)7 * i;
+        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != mode_bits || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
+        any_base |= q[1] != UINT64_MAX;
+    }
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
+        for (s32 i = 0; i < n; i++) add(g, segs + (size_t)7 * i);
+    });
+}
 }  // namespace
 
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 3); }
@@ -1600,18 +1621,8 @@ BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void 
 // n septuples (src_off, base_off, dst_off, len, elem_size | 1 << 8, a, b): of the merge of the `len` bytes at src_off the bytes [a, b), to
 // dst_off (plus the bytes at base_off unless it is UINT64_MAX), one launch through the segments a range call's gather makes of them.
 BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
-    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
-    bool any_base = false;
-    for (s32 i = 0; i < n; i++) {
-        const uint64_t * q = segs + (size_t)7 * i;
-        if (!planes_elem_size_ok(q[4] & 0xff) || (q[4] >> 8) != 1 || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
-        any_base |= q[1] != UINT64_MAX;
-    }
-    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
-        for (s32 i = 0; i < n; i++) {
-            const uint64_t * q = segs + (size_t)7 * i;
-            g.range((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], debug_base(base, q[1]));
-        }
+    return debug_clips(src, base, dst, segs, n, 1, [&](GatherList & g, const uint64_t * q) {
+        g.range((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], (u64)dst + q[2], debug_base(base, q[1]));
     });
 }
 
@@ -1619,18 +1630,8 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
 // [a, b) get the values at src_off (less the bytes at base_off unless it is UINT64_MAX), one launch through the segments an update call's patch
 // makes of them.
 BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
-    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
-    bool any_base = false;
-    for (s32 i = 0; i < n; i++) {
-        const uint64_t * q = segs + (size_t)7 * i;
-        if (!planes_elem_size_ok(q[4]) || q[5] > q[6] || q[6] > q[3]) return BZ3_ERR_INIT;
-        any_base |= q[1] != UINT64_MAX;
-    }
-    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
-        for (s32 i = 0; i < n; i++) {
-            const uint64_t * q = segs + (size_t)7 * i;
-            g.patch((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6]);
-        }
+    return debug_clips(src, base, dst, segs, n, 0, [&](GatherList & g, const uint64_t * q) {
+        g.patch((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6]);
     });
 }
 
@@ -1682,6 +1683,25 @@ bool debug_select_tuples(const uint64_t * segs, int32_t n, const uint64_t * piec
     }
     return true;
 }
+
+// The body of the two select hooks: those checks, the tables uploaded behind the launch's own, and one launch of the segments that
+// add(list, tuple, its table, the table's device address) makes of the tuples that name a byte.
+int32_t debug_selects(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces, u64 mode_bits,
+                      const std::function<void(GatherList &, const uint64_t *, const PieceTable &, u64)> & add) {
+    bool any_base = false;
+    std::vector<PieceTable> tabs;
+    std::vector<u64> all;
+    if (!debug_select_tuples(segs, n, pieces, n_pieces, mode_bits, tabs, all, any_base)) return BZ3_ERR_INIT;
+    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
+        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+        size_t at = 0;
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)12 * i;
+            if (q[9]) add(g, q, tabs[(size_t)i], (u64)d_tabs + at * sizeof(u64));
+            at += tabs[(size_t)i].tab.size();
+        }
+    });
+}
 }  // namespace
 
 // n tuples of 12 u64 (src_off, base_off, dst_off, len, elem_size | 1 << 8, rel, stride, q0, r0, nbytes, first_piece, m): of the merge of the `len`
@@ -1689,19 +1709,8 @@ bool debug_select_tuples(const uint64_t * segs, int32_t n, const uint64_t * piec
 // bytes at base_off unless it is UINT64_MAX), one launch through the segments a select call's gather makes of them.  The pieces are taken as they
 // are, empty ones and neighbours that touch included.
 BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces) {
-    bool any_base = false;
-    std::vector<PieceTable> tabs;
-    std::vector<u64> all;
-    if (!debug_select_tuples(segs, n, pieces, n_pieces, 1, tabs, all, any_base)) return BZ3_ERR_INIT;
-    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
-        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
-        size_t at = 0;
-        for (s32 i = 0; i < n; i++) {
-            const uint64_t * q = segs + (size_t)12 * i;
-            const PieceTable & t = tabs[(size_t)i];
-            if (q[9]) g.select((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, (u64)d_tabs + at * sizeof(u64), q[7], q[8], q[9], (u64)dst + q[2], debug_base(base, q[1]));
-            at += t.tab.size();
-        }
+    return debug_selects(src, base, dst, segs, n, pieces, n_pieces, 1, [&](GatherList & g, const uint64_t * q, const PieceTable & t, u64 d_tab) {
+        g.select((u64)src + q[0], q[3], q[4] & 0xff, q[5], q[6], t, d_tab, q[7], q[8], q[9], (u64)dst + q[2], debug_base(base, q[1]));
     });
 }
 
@@ -1710,19 +1719,8 @@ BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void
 // from pieces[2 first_piece] on get the values at src_off (less the bytes at base_off unless it is UINT64_MAX), one launch through the segments an
 // update call's patch makes of them.  The pieces are taken as they are, empty ones and neighbours that touch included.
 BZIP3_API int32_t bz3_hip_debug_patch_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n, const uint64_t * pieces, uint64_t n_pieces) {
-    bool any_base = false;
-    std::vector<PieceTable> tabs;
-    std::vector<u64> all;
-    if (!debug_select_tuples(segs, n, pieces, n_pieces, 0, tabs, all, any_base)) return BZ3_ERR_INIT;
-    return debug_launch(src, base, any_base, dst, (size_t)n, SEG_SELECT, all.size() * sizeof(u64) + 16, [&](GatherList & g, u8 * d_tabs, hipStream_t s) {
-        if (!all.empty()) HIP_CHECK(hipMemcpyAsync(d_tabs, all.data(), all.size() * sizeof(u64), hipMemcpyHostToDevice, s));
-        size_t at = 0;
-        for (s32 i = 0; i < n; i++) {
-            const uint64_t * q = segs + (size_t)12 * i;
-            const PieceTable & t = tabs[(size_t)i];
-            if (q[9]) g.patch_select((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6], t, (u64)d_tabs + at * sizeof(u64), q[7], q[8], q[9]);
-            at += t.tab.size();
-        }
+    return debug_selects(src, base, dst, segs, n, pieces, n_pieces, 0, [&](GatherList & g, const uint64_t * q, const PieceTable & t, u64 d_tab) {
+        g.patch_select((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6], t, d_tab, q[7], q[8], q[9]);
     });
 }
 

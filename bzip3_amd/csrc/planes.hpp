@@ -75,22 +75,21 @@
 // k = 1 is a plain copy, or the delta1_tile copy with a base, at dst + a, and a == 0 && b == s the ordinary split segment (GatherList::patch,
 // api_frames.hip).  No scratch; the LDS of the other segment kernels.
 //
-// Strided merge (CopySeg::mode & PLANES_STRIDED; bz3_hip_decompress_device_strided, api_frames.hip).  A strided range wants of a chunk a
-// periodic set of its bytes: chunk byte c0, the `first` bytes from it on (the rest of the run c0 lies in), then runs of `run` bytes
-// whose starts lie `stride` bytes apart, nbytes in all.  In the output they are CONTIGUOUS, dst[0, nbytes), so the chunk is one segment
-// with one destination range, whatever the number of runs in it.  Destination byte u comes from chunk byte
-//     c(u) = c0 + u                                                    (u < first)
-//     c(u) = c0 + first + (stride - run) + (v / run) stride + v % run  (v = u - first)
-// and chunk byte c lives at slot[(c % k) m + c / k] for c < m k (m = len / k), at slot[c] in the tail: merge_k.  strided_tile tiles the
-// DESTINATION: a workgroup owns the destination bytes [4080 k t, 4080 k (t + 1)) cut at dst's 16-byte boundaries as merge_tile's are,
-// lane l fills LDS with the 16 k destination bytes from 4080 k t + 16 k l on, in destination order, and phase 2 is store_from_lds.  A
-// lane whose 16 k bytes are 16 whole elements of one run (they lie inside one run, inside [0, nbytes) and inside the element part of
-// the chunk, and the first of them is byte 0 of an element) takes k plane granules and interleave<K> (k = 1: one load16_any) and, with a base, load_elems16 of the
-// base and add_bytes; every other lane (one that crosses a run boundary, the chunk's tail or the segment's end, or whose bytes do not
-// start an element) moves its bytes one by one.  RUNS SHORTER THAN 16 ELEMENTS THEREFORE GO WHOLLY THROUGH THE BYTE PATH: correct and
-// slow ("Strided range decode").  A lane divides once (32 bits: every quantity is below the chunk's 2^31 bytes; a run
-// longer than that is clamped, which changes no c(u)) and then steps.  Every granule loaded from the slot holds a byte of the chunk, every
-// granule loaded from the base a byte of base[0, nbytes) -- the byte path loads bytes -- and nothing outside dst[0, nbytes) is written.
+// Gather merges (CopySeg::mode & (PLANES_STRIDED | PLANES_SELECT); gather_tile).  A strided and a select merge want of a chunk a set of its bytes
+// that a formula c(u), increasing in u, names (the two paragraphs below).  In the output they are CONTIGUOUS, dst[0, nbytes), so the chunk is one
+// segment with one destination range, whatever the number of runs or pieces in it.  Chunk byte c lives at slot[(c % k) m + c / k] for c < m k
+// (m = len / k), at slot[c] in the tail: merge_k.  gather_tile tiles the DESTINATION: a workgroup owns the destination bytes
+// [4080 k t, 4080 k (t + 1)) cut at dst's 16-byte boundaries as merge_tile's are, lane l fills LDS with the 16 k destination bytes from
+// u0 = 4080 k t + 16 k l on, in destination order, and phase 2 is store_from_lds.  The two merges differ in one thing, the cursor a lane walks the
+// chunk with (StridedCursor, SelectCursor): it locates c(u0) and what is left of the run or piece there with one division, and then steps.  A lane
+// whose 16 k bytes are 16 whole elements of one run or piece (they lie inside it, inside [0, nbytes) and inside the element part of the chunk, and
+// the first of them is byte 0 of an element) takes k plane granules and interleave<K> (k = 1: one load16_any) and, with a base, load_elems16 of
+// the base and add_bytes (merged_elems16); every other lane (one that crosses a run's or a piece's boundary, the chunk's tail or the segment's end,
+// or whose bytes do not start an element) moves its bytes one by one.  RUNS AND PIECES SHORTER THAN 16 ELEMENTS THEREFORE GO WHOLLY THROUGH THE
+// BYTE PATH: correct and slow ("Strided range decode").  Every granule loaded from the slot holds a byte of the chunk (16-byte path:
+// c + 16 k <= m k, and plane granule q covers slot[q m + c / k, + 16)); every granule loaded from the base holds a byte of base[0, nbytes)
+// (16-byte path: u0 + 16 k <= nbytes, and load_elems16 takes the aligned granules around exactly those bytes; byte path: bytes u < nbytes); and
+// nothing outside dst[0, nbytes) is written (phase 2 is store_from_lds over the tile's share of [dst, dst + nbytes)).  No scratch.
 // In place (dst == base): dst and base share the segment's coordinates, so dst == base pairs every byte with itself.  The bytes a tile
 // stores, [s0, s1), are its own (the tiles' store ranges partition dst[0, nbytes), the segments' destinations are disjoint); they lie
 // within the destination bytes of its 256 lanes, [4080 k t, 4080 k t + 4096 k) (s1 <= dst + 4080 k (t + 1) + 15), so every one of
@@ -98,34 +97,34 @@
 // path: the byte does), before the barrier, and is stored in phase 2, after it.  load_elems16 keeps of the aligned granules it reads
 // only the lane's own 16 k bytes, so what else phase 1 takes from the base are the 256th lane's bytes and the bytes below s0, which
 // belong to other tiles, may have been overwritten already and land in LDS outside [s0 - origin, s1 - origin), where phase 2 never
-// reads.
+// reads.  The argument speaks of the tiling, the lanes' destination bytes and phase 2 alone: which SOURCE byte a cursor gives a destination byte
+// does not enter it.
 //
-// Select merge (CopySeg::mode & PLANES_SELECT; bz3_hip_decompress_device_select, api_frames.hip).  An index request wants of a chunk the bytes
-// of a LIST of pieces per period: the periods start `stride` bytes apart, piece j of a period is its bytes [s_j, s_j + l_j), the pieces
-// ascend and are disjoint, P_j = l_0 + ... + l_{j-1}, L = P_m.  The table of the m + 1 pairs (s_j, P_j) -- the last one closes it with
-// P_m -- lies in device memory and is only ever read.  In the output the chunk's share is CONTIGUOUS, dst[0, nbytes): one segment.  With
-// x = r0 + u, destination byte u comes from chunk byte
+// Strided merge (PLANES_STRIDED; bz3_hip_decompress_device_strided, api_frames.hip).  A strided range wants of a chunk a periodic set of its
+// bytes: chunk byte c0, the `first` bytes from it on (the rest of the run c0 lies in), then runs of `run` bytes whose starts lie `stride` bytes
+// apart, nbytes in all.  Destination byte u comes from chunk byte
+//     c(u) = c0 + u                                                    (u < first)
+//     c(u) = c0 + first + (stride - run) + (v / run) stride + v % run  (v = u - first)
+// StridedCursor divides in 32 bits: every quantity is below the chunk's 2^31 bytes; a run longer than that is clamped (segments_tile), which
+// changes no c(u).
+//
+// Select merge (PLANES_SELECT; bz3_hip_decompress_device_select, api_frames.hip).  An index request wants of a chunk the bytes of a LIST of
+// pieces per period: the periods start `stride` bytes apart, piece j of a period is its bytes [s_j, s_j + l_j), the pieces ascend and are
+// disjoint, P_j = l_0 + ... + l_{j-1}, L = P_m.  The table of the m + 1 pairs (s_j, P_j) -- the last one closes it with P_m -- lies in device
+// memory and is only ever read.  With x = r0 + u, destination byte u comes from chunk byte
 //     c(u) = rel + (q0 + x / L) stride + s_j + (x % L - P_j),     j the piece with P_j <= x % L < P_{j+1}
-// (rel = the request's offset less the chunk's, mod 2^64; q0, r0: the period and the place in it of destination byte 0) and chunk byte c
-// lives where merge_k puts it, as above.  The host has checked that c(0) and c(nbytes - 1) lie in [0, len); c increases, so every c(u) does.
-// select_tile tiles the DESTINATION exactly as strided_tile does and differs in phase 1 alone: a lane locates its first byte with one
-// division (32 bits where L < 2^31, else a comparison: x < L + 2^31 then) and one binary search over P, and from there steps through the
-// pieces linearly, skipping empty ones, with the chunk byte of the period's start in hand.  The 16-byte path is strided_tile's under
-// strided_tile's conditions with "piece" for "run"; every other lane moves its bytes one by one.  So, as there: every granule loaded from the
-// slot holds a byte of the chunk (16-byte path: c + 16 k <= m k, and plane granule q covers slot[q m + c / k, + 16)); every granule loaded
-// from the base holds a byte of base[0, nbytes) (16-byte path: u0 + 16 k <= nbytes, and load_elems16 takes the aligned granules around
-// exactly those bytes; byte path: bytes u < nbytes); nothing outside dst[0, nbytes) is written (phase 2 is store_from_lds over the tile's
-// share of [dst, dst + nbytes)).  In place (dst == base): the tile argument of the strided merge holds word for word, because the tiling, the
-// lanes' destination bytes and phase 2 are the same and only the SOURCE byte of a destination byte differs.  No scratch, and the LDS of
-// k_strided_segments.
+// (rel = the request's offset less the chunk's, mod 2^64; q0, r0: the period and the place in it of destination byte 0).  The host has checked
+// that c(0) and c(nbytes - 1) lie in [0, len); c increases, so every c(u) does.  SelectCursor locates its first byte with one division (32 bits
+// where L < 2^31, else a comparison: x < L + 2^31 then) and one binary search over P, and from there steps through the pieces linearly,
+// skipping empty ones, with the chunk byte of the period's start in hand.  The LDS is that of k_strided_segments.
 //
 // Select split (CopySeg::mode & PLANES_SELECT without PLANES_INVERSE; bz3_hip_update_device_select, api_frames.hip).  The write mirror of the select
 // merge: dst is a slot that holds split_k of a chunk of len bytes, and the chunk bytes c(u) of the formula above, u < nbytes, get the new values
 // src[u] (less base[u] where there is a base): src and base are the CONTIGUOUS side and address the segment's first byte.  Chunk byte c is stored
 // where split_k keeps it, dst[(c % k) m + c / k] below m k and dst[c] in the tail, and NO OTHER BYTE OF THE SLOT is: the rest is the old chunk,
-// which the encode that follows reads.  select_split_tile tiles the SOURCE as select_tile tiles its destination, and a lane finds its piece the
-// same way.  A lane whose 16 k bytes are 16 whole elements of the chunk inside one piece (select_tile's condition) takes load_elems16, sub_bytes
-// and deinterleave, the fast path of clip_split_tile; every other lane moves its bytes one by one, so PIECES SHORTER THAN 16 ELEMENTS GO WHOLLY
+// which the encode that follows reads.  select_split_tile tiles the SOURCE as gather_tile tiles its destination, and a lane walks the chunk
+// with the same SelectCursor.  A lane whose 16 k bytes are 16 whole elements of the chunk inside one piece (gather_tile's condition) takes load_elems16,
+// sub_bytes and deinterleave, the fast path of clip_split_tile (split_elems16); every other lane moves its bytes one by one, so PIECES SHORTER THAN 16 ELEMENTS GO WHOLLY
 // THROUGH THE BYTE PATH: correct and slow.  Every granule loaded from src or base holds a byte of the lane's own 16 k bytes of src[0, nbytes) or
 // base[0, nbytes).  The stores leave the lane directly, without the LDS stage of the other tiles: the wanted bytes of different lanes are disjoint
 // but a tile's share of a plane is no contiguous range (neighbouring lanes may lie in different pieces and periods), and the bytes between two
@@ -133,6 +132,8 @@
 // bytes a lane has for one plane are ONE 16-byte store where they are an aligned granule, and 16 byte stores otherwise; never a read-modify-write.
 // No scratch; the kernel's LDS is that of the clipped and whole splits beside it.
 #pragma once
+#include <type_traits>
+
 #include "frame.hpp"
 
 namespace bz3 {
@@ -307,6 +308,72 @@ __device__ __forceinline__ u64 align16_up_to(u64 a, u64 end) {
     return a < end ? a : end;
 }
 
+// ---- a lane's 16 elements --------------------------------------------------------------------------------------------------------------
+// The 16-byte paths of phase 1.  Merge side: the 16 elements from element index e on of the K planes at `src`, m bytes apart (K == 1: the 16
+// bytes at src + e), interleaved into 4 K words; with D, plus the 16 K bytes at address `base`.  The caller has checked that e + 16 <= m and,
+// with D, that the 16 K base bytes are the lane's own.
+template <int K, bool D>
+__device__ __forceinline__ void merged_elems16(const u8 * src, u64 m, u64 e, u64 base, u32 (&w)[4 * K]) {
+    if constexpr (K == 1) {
+        const uint4 v = load16_any((u64)src + e);
+        w[0] = v.x;
+        w[1] = v.y;
+        w[2] = v.z;
+        w[3] = v.w;
+    } else {
+        u32 p[K][4];
+#pragma unroll
+        for (int q = 0; q < K; q++) {
+            const uint4 v = load16_any((u64)src + q * m + e);
+            p[q][0] = v.x;
+            p[q][1] = v.y;
+            p[q][2] = v.z;
+            p[q][3] = v.w;
+        }
+        interleave<K>(p, w);
+    }
+    if (D) {
+        u32 b[4 * K];
+        load_elems16<K>(base, b);
+#pragma unroll
+        for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
+    }
+}
+
+// Those 4 K words as the lane's K rows of the merge layout of LDS (16 K bytes per lane, in destination order).
+template <int K>
+__device__ __forceinline__ void rows_to_lds(u8 * lds, const u32 (&w)[4 * K]) {
+#pragma unroll
+    for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+}
+
+// The mirror, split side: the 16 elements of K bytes at address `src`, less with D the 16 K bytes at address `base`, deinterleaved: p[q] is byte q
+// of the 16 elements.
+template <int K, bool D>
+__device__ __forceinline__ void split_elems16(u64 src, u64 base, u32 (&p)[K][4]) {
+    u32 w[4 * K];
+    load_elems16<K>(src, w);
+    if (D) {
+        u32 b[4 * K];
+        load_elems16<K>(base, b);
+#pragma unroll
+        for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
+    }
+    if constexpr (K == 1) {
+#pragma unroll
+        for (int n = 0; n < 4; n++) p[0][n] = w[n];
+    } else {
+        deinterleave<K>(w, p);
+    }
+}
+
+// Those K granules as the lane's granule of every plane of the split layout of LDS (PLANE_STRIDE bytes per plane).
+template <int K>
+__device__ __forceinline__ void planes_to_lds(u8 * lds, const u32 (&p)[K][4]) {
+#pragma unroll
+    for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
+}
+
 // Tile `tile` of a split: elements [ea, ea + PLANES_TILE_ELEMS) of the block at `src` into the planes at `dst`; with D, of the
 // block's byte-wise difference from the bytes at `base`.
 template <int K, bool D>
@@ -314,17 +381,9 @@ __device__ __forceinline__ void split_tile(const u8 * src, const u8 * base, u8 *
     const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
     const u64 e = ea + 16 * (u64)threadIdx.x;
     if (e + 16 <= m) {
-        u32 w[4 * K], p[K][4];
-        load_elems16<K>((u64)src + e * K, w);
-        if (D) {
-            u32 b[4 * K];
-            load_elems16<K>((u64)base + e * K, b);
-#pragma unroll
-            for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
-        }
-        deinterleave<K>(w, p);
-#pragma unroll
-        for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
+        u32 p[K][4];
+        split_elems16<K, D>((u64)src + e * K, (u64)base + e * K, p);
+        planes_to_lds<K>(lds, p);
     } else {
         for (u64 i = e; i < m; i++)
             for (int q = 0; q < K; q++) lds[q * PLANE_STRIDE + (i - ea)] = D ? (u8)(src[i * K + q] - base[i * K + q]) : src[i * K + q];
@@ -351,24 +410,9 @@ __device__ __forceinline__ void merge_tile(const u8 * src, const u8 * base, u8 *
     const u64 m = len / K, ea = tile * PLANES_TILE_ELEMS;
     const u64 e = ea + 16 * (u64)threadIdx.x;
     if (e + 16 <= m) {
-        u32 w[4 * K], p[K][4];
-#pragma unroll
-        for (int q = 0; q < K; q++) {
-            const uint4 v = load16_any((u64)src + q * m + e);
-            p[q][0] = v.x;
-            p[q][1] = v.y;
-            p[q][2] = v.z;
-            p[q][3] = v.w;
-        }
-        interleave<K>(p, w);
-        if (D) {
-            u32 b[4 * K];
-            load_elems16<K>((u64)base + e * K, b);
-#pragma unroll
-            for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+        u32 w[4 * K];
+        merged_elems16<K, D>(src, m, e, (u64)base + e * K, w);
+        rows_to_lds<K>(lds, w);
     } else {
         for (u64 i = e; i < m; i++)
             for (int q = 0; q < K; q++) lds[(i - ea) * K + q] = D ? (u8)(src[q * m + i] + base[i * K + q]) : src[q * m + i];
@@ -480,24 +524,9 @@ __device__ __forceinline__ void clip_merge_tile(const u8 * src, const u8 * base,
     const u64 l0 = e * K, l1 = (e + 16) * K;  // the chunk bytes of the lane's elements
     if (l0 < bm && l1 > ca) {
         if (e + 16 <= m && (!D || (l0 >= ca && l1 <= cb))) {
-            u32 w[4 * K], p[K][4];
-#pragma unroll
-            for (int q = 0; q < K; q++) {
-                const uint4 v = load16_any((u64)src + q * m + e);
-                p[q][0] = v.x;
-                p[q][1] = v.y;
-                p[q][2] = v.z;
-                p[q][3] = v.w;
-            }
-            interleave<K>(p, w);
-            if (D) {
-                u32 b[4 * K];
-                load_elems16<K>((u64)base + (l0 - ca), b);
-#pragma unroll
-                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+            u32 w[4 * K];
+            merged_elems16<K, D>(src, m, e, (u64)base + (l0 - ca), w);
+            rows_to_lds<K>(lds, w);
         } else {
             for (u64 i = e; i < m && i < e + 16; i++)
                 for (int q = 0; q < K; q++) {
@@ -531,17 +560,9 @@ __device__ __forceinline__ void clip_split_tile(const u8 * src, const u8 * base,
     const u64 l0 = e * K, l1 = (e + 16) * K;  // the chunk bytes of the lane's elements
     if (l0 < bm && l1 > ca) {
         if (l0 >= ca && l1 <= bm) {  // (l1 <= bm <= m K: the lane's 16 elements are whole elements of the chunk)
-            u32 w[4 * K], p[K][4];
-            load_elems16<K>((u64)src + (l0 - ca), w);
-            if (D) {
-                u32 b[4 * K];
-                load_elems16<K>((u64)base + (l0 - ca), b);
-#pragma unroll
-                for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
-            }
-            deinterleave<K>(w, p);
-#pragma unroll
-            for (int q = 0; q < K; q++) *(uint4 *)(lds + q * PLANE_STRIDE + 16 * threadIdx.x) = make_uint4(p[q][0], p[q][1], p[q][2], p[q][3]);
+            u32 p[K][4];
+            split_elems16<K, D>((u64)src + (l0 - ca), (u64)base + (l0 - ca), p);
+            planes_to_lds<K>(lds, p);
         } else {
             for (u64 i = e; i < m && i < e + 16; i++)
                 for (int q = 0; q < K; q++) {
@@ -569,75 +590,41 @@ __device__ __forceinline__ void clip_split_tile(const u8 * src, const u8 * base,
     }
 }
 
-// ---- strided merge ------------------------------------------------------------------------------------------------------------------
-// Workgroups of a strided merge of nbytes destination bytes: one per PLANES_TILE_ELEMS k of them.
+// ---- gather merges: strided and select ---------------------------------------------------------------------------------------------------
+// Workgroups of a gather merge (or of a select split) of nbytes contiguous bytes: one per PLANES_TILE_ELEMS k of them.
 __host__ __device__ inline u64 strided_tiles(u64 nbytes, u64 k) { return (nbytes + k * PLANES_TILE_ELEMS - 1) / (k * PLANES_TILE_ELEMS); }
 
-// Tile `tile` of a strided merge of the `len` < 2^31 bytes at `src`: destination bytes [0, nbytes) from the chunk bytes c(u) (the head of
-// this file; gap = stride - run), to dst; with D, plus base[0, nbytes) (which may be `dst`).
-template <int K, bool D>
-__device__ __forceinline__ void strided_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, u32 c0, u32 first, u32 run, u32 gap, u32 nbytes, u32 tile, u8 * lds) {
-    const u32 m = len / K, ua = tile * (PLANES_TILE_ELEMS * K);
-    const u32 u0 = ua + 16 * K * threadIdx.x;
-    if (u0 < nbytes) {
-        u32 c, left;  // the chunk byte of destination byte u0, and what is left of its run
-        if (u0 < first) {
-            c = c0 + u0;
-            left = first - u0;
+// A cursor walks the chunk bytes c(u) of a segment's contiguous side from a lane's first byte u0 on (the head of this file): `c` is the chunk
+// byte of the lane's current byte, `left` what is left of its run or piece from there, step(more) goes on one byte (more: the lane has another
+// byte to move).  Chunk bytes are taken mod 2^32: every c(u) that is read or written lies below the chunk's 2^31 bytes.
+
+// The strided walk: chunk byte c0, `first` bytes from it on, then runs of `run` bytes with `gap` = stride - run bytes between them.
+struct StridedRuns {
+    u32 c0, first, run, gap;
+};
+struct StridedCursor {
+    using Walk = StridedRuns;
+    u32 c, left;
+    const u32 run, gap;
+    __device__ __forceinline__ StridedCursor(const StridedRuns & r, u32 u0) : run(r.run), gap(r.gap) {  // one division
+        if (u0 < r.first) {
+            c = r.c0 + u0;
+            left = r.first - u0;
         } else {
-            const u32 v = u0 - first, q = v / run;
-            c = c0 + u0 + (q + 1) * gap;
+            const u32 v = u0 - r.first, q = v / run;
+            c = r.c0 + u0 + (q + 1) * gap;
             left = run - (v - q * run);
         }
-        if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
-            u32 w[4 * K];
-            if constexpr (K == 1) {
-                const uint4 v = load16_any((u64)src + c);
-                w[0] = v.x;
-                w[1] = v.y;
-                w[2] = v.z;
-                w[3] = v.w;
-            } else {
-                u32 p[K][4];
-#pragma unroll
-                for (int q = 0; q < K; q++) {
-                    const uint4 v = load16_any((u64)src + (u64)q * m + c / K);
-                    p[q][0] = v.x;
-                    p[q][1] = v.y;
-                    p[q][2] = v.z;
-                    p[q][3] = v.w;
-                }
-                interleave<K>(p, w);
-            }
-            if (D) {
-                u32 b[4 * K];
-                load_elems16<K>((u64)base + u0, b);
-#pragma unroll
-                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-        } else {
-            const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
-            for (u32 u = u0; u < u1; u++) {
-                const u8 x = src[c < m * K ? (c % K) * m + c / K : c];
-                lds[u - ua] = D ? (u8)(x + base[u]) : x;
-                c++;
-                if (--left == 0) {
-                    c += gap;
-                    left = run;
-                }
-            }
+    }
+    __device__ __forceinline__ void step(bool) {
+        c++;
+        if (--left == 0) {
+            c += gap;
+            left = run;
         }
     }
-    __syncthreads();
-    const u64 d0 = (u64)dst, dend = d0 + nbytes;
-    const u64 s0 = tile == 0 ? d0 : align16_up_to(d0 + ua, dend);
-    const u64 s1 = ua + PLANES_TILE_ELEMS * K >= nbytes ? dend : align16_up_to(d0 + ua + PLANES_TILE_ELEMS * K, dend);
-    store_from_lds<K>(lds, d0 + ua, s0, s1);  // at most 255 K + 1 granules
-}
+};
 
-// ---- select merge --------------------------------------------------------------------------------------------------------------------
 // The piece of a table of m (pairs (s_j, P_j), closed by P_m) that holds byte r < P_m of the period's wanted bytes: P_j <= r < P_{j+1}.
 __host__ __device__ inline u32 piece_of(const u64 * tab, u32 m, u64 r) {
     u32 lo = 0, hi = m;  // invariant: P_lo <= r < P_hi
@@ -649,15 +636,15 @@ __host__ __device__ inline u32 piece_of(const u64 * tab, u32 m, u64 r) {
     return lo;
 }
 
-// Tile `tile` of a select merge of the `len` < 2^31 bytes at `src`: destination bytes [0, nbytes) from the chunk bytes c(u) (the head of this
-// file; sp: the segment's SELECT_PARAMS), to dst; with D, plus base[0, nbytes) (which may be `dst`).  Workgroups: strided_tiles(nbytes, k).
-template <int K, bool D>
-__device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, const u64 * __restrict__ sp, u32 tile, u8 * lds) {
-    const u32 m = len / K, ua = tile * (PLANES_TILE_ELEMS * K), nbytes = (u32)sp[4];
-    const u32 u0 = ua + 16 * K * threadIdx.x;
-    if (u0 < nbytes) {
-        const u64 * __restrict__ tab = (const u64 *)sp[5];
-        const u32 np = (u32)sp[6], stride = (u32)sp[1];  // (chunk bytes are taken mod 2^32: every c(u) that is read lies below 2^31)
+// The select walk over a segment's SELECT_PARAMS sp: one division (32 bits where L < 2^31, else a comparison: x < L + 2^31 then) and one binary
+// search over P locate the lane's first byte; from there it steps through the pieces linearly, skipping empty ones, with the chunk byte of the
+// period's start in hand.
+struct SelectCursor {
+    using Walk = const u64 *;
+    const u64 * __restrict__ tab;
+    const u32 np, stride;
+    u32 j, cb, c, left;  // the piece, the chunk byte of its period's first byte
+    __device__ __forceinline__ SelectCursor(const u64 * __restrict__ sp, u32 u0) : tab((const u64 *)sp[5]), np((u32)sp[6]), stride((u32)sp[1]) {
         const u64 L = tab[2 * np + 1], x = sp[3] + u0;
         u64 q, r;  // x = q L + r
         if (L >> 31) {
@@ -667,57 +654,48 @@ __device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 
             q = (u32)x / (u32)L;
             r = (u32)x - (u32)q * (u32)L;
         }
-        u32 j = piece_of(tab, np, r);
-        u32 cb = (u32)(sp[0] + (sp[2] + q) * sp[1]);  // the chunk byte of the period's first byte
+        j = piece_of(tab, np, r);
+        cb = (u32)(sp[0] + (sp[2] + q) * sp[1]);
         const u64 in = r - tab[2 * j + 1], rest = tab[2 * j + 3] - r;  // bytes of piece j before and from the lane's first byte
-        u32 c = cb + (u32)(tab[2 * j] + in);
-        u32 left = rest < 0x7fffffffu ? (u32)rest : 0x7fffffffu;  // (beyond the chunk's 2^31 bytes: no destination byte lies behind it)
-        if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
-            u32 w[4 * K];
-            if constexpr (K == 1) {
-                const uint4 v = load16_any((u64)src + c);
-                w[0] = v.x;
-                w[1] = v.y;
-                w[2] = v.z;
-                w[3] = v.w;
-            } else {
-                u32 p[K][4];
-#pragma unroll
-                for (int i = 0; i < K; i++) {
-                    const uint4 v = load16_any((u64)src + (u64)i * m + c / K);
-                    p[i][0] = v.x;
-                    p[i][1] = v.y;
-                    p[i][2] = v.z;
-                    p[i][3] = v.w;
+        c = cb + (u32)(tab[2 * j] + in);
+        left = rest < 0x7fffffffu ? (u32)rest : 0x7fffffffu;  // (beyond the chunk's 2^31 bytes: no byte of the segment lies behind it)
+    }
+    __device__ __forceinline__ void step(bool more) {
+        c++;
+        if (--left == 0 && more) {  // the next piece that is not empty (there is one: L > 0), in the next period behind the last
+            u64 l;
+            do {
+                if (++j == np) {
+                    j = 0;
+                    cb += stride;
                 }
-                interleave<K>(p, w);
-            }
-            if (D) {
-                u32 b[4 * K];
-                load_elems16<K>((u64)base + u0, b);
-#pragma unroll
-                for (int i = 0; i < 4 * K; i++) w[i] = add_bytes(w[i], b[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < K; i++) *(uint4 *)(lds + 16 * (K * threadIdx.x + i)) = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+                l = tab[2 * j + 3] - tab[2 * j + 1];
+            } while (l == 0);
+            c = cb + (u32)tab[2 * j];
+            left = l < 0x7fffffffu ? (u32)l : 0x7fffffffu;
+        }
+    }
+};
+
+// Tile `tile` of a gather merge of the `len` < 2^31 bytes at `src`: destination bytes [0, nbytes) from the chunk bytes c(u) that a Cursor over
+// `walk` names (the head of this file, "Gather merges"), to dst; with D, plus base[0, nbytes) (which may be `dst`).  Workgroups:
+// strided_tiles(nbytes, k).
+template <int K, bool D, class Cursor>
+__device__ __forceinline__ void gather_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, u32 nbytes, const typename Cursor::Walk & walk, u32 tile, u8 * lds) {
+    const u32 m = len / K, ua = tile * (PLANES_TILE_ELEMS * K);
+    const u32 u0 = ua + 16 * K * threadIdx.x;
+    if (u0 < nbytes) {
+        Cursor cur(walk, u0);
+        if (cur.left >= 16 * K && u0 + 16 * K <= nbytes && cur.c % K == 0 && cur.c + 16 * K <= m * K) {
+            u32 w[4 * K];
+            merged_elems16<K, D>(src, m, cur.c / K, (u64)base + u0, w);
+            rows_to_lds<K>(lds, w);
         } else {
             const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
             for (u32 u = u0; u < u1; u++) {
-                const u8 v = src[c < m * K ? (c % K) * m + c / K : c];
-                lds[u - ua] = D ? (u8)(v + base[u]) : v;
-                c++;
-                if (--left == 0 && u + 1 < u1) {  // the next piece that is not empty (there is one: L > 0), in the next period behind the last
-                    u64 l;
-                    do {
-                        if (++j == np) {
-                            j = 0;
-                            cb += stride;
-                        }
-                        l = tab[2 * j + 3] - tab[2 * j + 1];
-                    } while (l == 0);
-                    c = cb + (u32)tab[2 * j];
-                    left = l < 0x7fffffffu ? (u32)l : 0x7fffffffu;
-                }
+                const u8 x = src[cur.c < m * K ? (cur.c % K) * m + cur.c / K : cur.c];
+                lds[u - ua] = D ? (u8)(x + base[u]) : x;
+                cur.step(u + 1 < u1);
             }
         }
     }
@@ -731,6 +709,25 @@ __device__ __forceinline__ void select_tile(const u8 * src, const u8 * base, u8 
 // ---- the segment kernels -------------------------------------------------------------------------------------------------------------
 // The kinds of segment a launch may hold, in the order they were added: every kind's kernel handles the kinds below it as well.
 enum SegLevel : int { SEG_DELTA = 0, SEG_CLIP = 1, SEG_STRIDED = 2, SEG_SELECT = 3 };
+
+// f(K, D) with the segment's element size and whether it has a base as constants (K() and D() are constant expressions): the one switch of every
+// partial tile.  It is written into every branch that calls it: its value computed once above the branches costs four to six SGPRs.
+template <int K>
+using ElemSize = std::integral_constant<int, K>;
+template <class F>
+__device__ __forceinline__ void with_elem_size_and_base(const CopySeg & sg, F && f) {
+    switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+        case 1: f(ElemSize<1>(), std::false_type()); break;
+        case 2: f(ElemSize<2>(), std::false_type()); break;
+        case 4: f(ElemSize<4>(), std::false_type()); break;
+        case 8: f(ElemSize<8>(), std::false_type()); break;
+        case 1 | 16: f(ElemSize<1>(), std::true_type()); break;
+        case 2 | 16: f(ElemSize<2>(), std::true_type()); break;
+        case 4 | 16: f(ElemSize<4>(), std::true_type()); break;
+        case 8 | 16: f(ElemSize<8>(), std::true_type()); break;
+        default: break;
+    }
+}
 
 // One tile of a segment that is moved whole: a copy, a split or a merge, with or without a base.
 __device__ __forceinline__ void whole_segment_tile(const CopySeg & sg, u32 tile, u8 * lds) {
@@ -751,8 +748,7 @@ __device__ __forceinline__ void whole_segment_tile(const CopySeg & sg, u32 tile,
 // are segment i's [a, b) (read for segments with PLANES_CLIP alone, LEVEL >= SEG_CLIP), periods[5 i .. 5 i + 4] its c0, first, run, stride and
 // nbytes (PLANES_STRIDED, LEVEL >= SEG_STRIDED), selects[7 i .. 7 i + 6] its SELECT_PARAMS (PLANES_SELECT, LEVEL == SEG_SELECT); tile_start counts
 // a segment's workgroups with strided_tiles, strided_tiles, clip_tiles and segment_tiles in that order.  A branch above LEVEL is not compiled,
-// so a kernel holds the code of its own kinds alone.  (The switch value is written out in every branch: computed once above them it costs
-// four to six SGPRs.)
+// so a kernel holds the code of its own kinds alone.
 template <int LEVEL>
 __device__ __forceinline__ void segments_tile(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg, const u64 * __restrict__ clips,
                                               const u64 * __restrict__ periods, const u64 * __restrict__ selects, u8 * lds) {
@@ -764,38 +760,16 @@ __device__ __forceinline__ void segments_tile(const CopySeg * __restrict__ segs,
     u8 * dst = (u8 *)sg.dst;
     if (LEVEL >= SEG_SELECT && (sg.mode & PLANES_SELECT)) {
         const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
-        const u32 len = (u32)sg.len;
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: select_tile<1, false>(src, base, dst, len, sp, tile, lds); break;
-            case 2: select_tile<2, false>(src, base, dst, len, sp, tile, lds); break;
-            case 4: select_tile<4, false>(src, base, dst, len, sp, tile, lds); break;
-            case 8: select_tile<8, false>(src, base, dst, len, sp, tile, lds); break;
-            case 1 | 16: select_tile<1, true>(src, base, dst, len, sp, tile, lds); break;
-            case 2 | 16: select_tile<2, true>(src, base, dst, len, sp, tile, lds); break;
-            case 4 | 16: select_tile<4, true>(src, base, dst, len, sp, tile, lds); break;
-            case 8 | 16: select_tile<8, true>(src, base, dst, len, sp, tile, lds); break;
-            default: break;
-        }
+        with_elem_size_and_base(sg, [&](auto K, auto D) { gather_tile<K(), D(), SelectCursor>(src, base, dst, (u32)sg.len, (u32)sp[4], sp, tile, lds); });
     } else if (LEVEL >= SEG_STRIDED && (sg.mode & PLANES_STRIDED)) {
         const u64 * pp = periods + (u64)STRIDED_PARAMS * lo;
         const u32 c0 = (u32)pp[0], first = (u32)pp[1], nbytes = (u32)pp[4];
         const u32 run = pp[2] < 0x7fffffffu ? (u32)pp[2] : 0x7fffffffu;  // (a run beyond the chunk's 2^31 bytes: no destination byte lies behind it)
         const u32 gap = nbytes > first ? (u32)(pp[3] - pp[2]) : 0;
-        const u32 len = (u32)sg.len;
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: strided_tile<1, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 2: strided_tile<2, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 4: strided_tile<4, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 8: strided_tile<8, false>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 1 | 16: strided_tile<1, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 2 | 16: strided_tile<2, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 4 | 16: strided_tile<4, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            case 8 | 16: strided_tile<8, true>(src, base, dst, len, c0, first, run, gap, nbytes, tile, lds); break;
-            default: break;
-        }
+        with_elem_size_and_base(sg, [&](auto K, auto D) { gather_tile<K(), D(), StridedCursor>(src, base, dst, (u32)sg.len, nbytes, {c0, first, run, gap}, tile, lds); });
     } else if (LEVEL >= SEG_CLIP && (sg.mode & PLANES_CLIP)) {
         const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
+        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {  // (written out: through with_elem_size_and_base k_range_segments and k_strided_segments take two more SGPRs)
             case 2: clip_merge_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
             case 4: clip_merge_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
             case 8: clip_merge_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
@@ -838,47 +812,20 @@ __global__ void __launch_bounds__(COPY_THREADS) k_select_segments(const CopySeg 
 // ---- select split --------------------------------------------------------------------------------------------------------------------
 // Tile `tile` of a select split INTO the `len` < 2^31 bytes at `dst`, which hold split_k of a chunk: the chunk bytes c(u), u < nbytes (the head of
 // this file, "Select split"; sp: the segment's SELECT_PARAMS), get src[u]; with D, less base[u].  Workgroups: strided_tiles(nbytes, k); the first
-// 255 lanes of one own 16 k source bytes each (the tiling of the select merge's destination, which needs its 256th lane for the straddling
+// 255 lanes of one own 16 k source bytes each (the tiling of the gather merge's destination, which needs its 256th lane for the straddling
 // granule alone: here nothing straddles).  No LDS and no barrier: every store leaves the lane that loaded the byte.
 template <int K, bool D>
 __device__ __forceinline__ void select_split_tile(const u8 * src, const u8 * base, u8 * dst, u32 len, const u64 * __restrict__ sp, u32 tile) {
     const u32 m = len / K, nbytes = (u32)sp[4];
     const u32 u0 = tile * (PLANES_TILE_ELEMS * K) + 16 * K * threadIdx.x;
     if (threadIdx.x >= COPY_THREADS - 1 || u0 >= nbytes) return;
-    const u64 * __restrict__ tab = (const u64 *)sp[5];
-    const u32 np = (u32)sp[6], stride = (u32)sp[1];  // (chunk bytes are taken mod 2^32: every c(u) that is written lies below 2^31)
-    const u64 L = tab[2 * np + 1], x = sp[3] + u0;
-    u64 q, r;  // x = q L + r
-    if (L >> 31) {
-        q = x >= L ? 1 : 0;
-        r = x - (q ? L : 0);
-    } else {
-        q = (u32)x / (u32)L;
-        r = (u32)x - (u32)q * (u32)L;
-    }
-    u32 j = piece_of(tab, np, r);
-    u32 cb = (u32)(sp[0] + (sp[2] + q) * sp[1]);  // the chunk byte of the period's first byte
-    const u64 in = r - tab[2 * j + 1], rest = tab[2 * j + 3] - r;  // bytes of piece j before and from the lane's first byte
-    u32 c = cb + (u32)(tab[2 * j] + in);
-    u32 left = rest < 0x7fffffffu ? (u32)rest : 0x7fffffffu;  // (beyond the chunk's 2^31 bytes: no source byte lies behind it)
-    if (left >= 16 * K && u0 + 16 * K <= nbytes && c % K == 0 && c + 16 * K <= m * K) {
-        u32 w[4 * K], p[K][4];
-        load_elems16<K>((u64)src + u0, w);
-        if (D) {
-            u32 b[4 * K];
-            load_elems16<K>((u64)base + u0, b);
-#pragma unroll
-            for (int i = 0; i < 4 * K; i++) w[i] = sub_bytes(w[i], b[i]);
-        }
-        if constexpr (K == 1) {
-#pragma unroll
-            for (int n = 0; n < 4; n++) p[0][n] = w[n];
-        } else {
-            deinterleave<K>(w, p);
-        }
+    SelectCursor cur(sp, u0);
+    if (cur.left >= 16 * K && u0 + 16 * K <= nbytes && cur.c % K == 0 && cur.c + 16 * K <= m * K) {
+        u32 p[K][4];
+        split_elems16<K, D>((u64)src + u0, (u64)base + u0, p);
 #pragma unroll
         for (int i = 0; i < K; i++) {  // plane i: the lane's 16 bytes, one granule where they are one
-            const u64 a = (u64)dst + (u64)i * m + c / K;
+            const u64 a = (u64)dst + (u64)i * m + cur.c / K;
             if ((a & 15) == 0) {
                 *(uint4 *)a = make_uint4(p[i][0], p[i][1], p[i][2], p[i][3]);
             } else {
@@ -889,20 +836,8 @@ __device__ __forceinline__ void select_split_tile(const u8 * src, const u8 * bas
     } else {
         const u32 u1 = u0 + 16 * K < nbytes ? u0 + 16 * K : nbytes;
         for (u32 u = u0; u < u1; u++) {
-            dst[c < m * K ? (c % K) * m + c / K : c] = D ? (u8)(src[u] - base[u]) : src[u];
-            c++;
-            if (--left == 0 && u + 1 < u1) {  // the next piece that is not empty (there is one: L > 0), in the next period behind the last
-                u64 l;
-                do {
-                    if (++j == np) {
-                        j = 0;
-                        cb += stride;
-                    }
-                    l = tab[2 * j + 3] - tab[2 * j + 1];
-                } while (l == 0);
-                c = cb + (u32)tab[2 * j];
-                left = l < 0x7fffffffu ? (u32)l : 0x7fffffffu;
-            }
+            dst[cur.c < m * K ? (cur.c % K) * m + cur.c / K : cur.c] = D ? (u8)(src[u] - base[u]) : src[u];
+            cur.step(u + 1 < u1);
         }
     }
 }
@@ -920,31 +855,13 @@ __device__ __forceinline__ void patch_segments_tile(const CopySeg * __restrict__
     u8 * dst = (u8 *)sg.dst;
     if (SELECT && (sg.mode & PLANES_SELECT)) {
         const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
-        const u32 len = (u32)sg.len;
-        switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-            case 1: select_split_tile<1, false>(src, base, dst, len, sp, tile); break;
-            case 2: select_split_tile<2, false>(src, base, dst, len, sp, tile); break;
-            case 4: select_split_tile<4, false>(src, base, dst, len, sp, tile); break;
-            case 8: select_split_tile<8, false>(src, base, dst, len, sp, tile); break;
-            case 1 | 16: select_split_tile<1, true>(src, base, dst, len, sp, tile); break;
-            case 2 | 16: select_split_tile<2, true>(src, base, dst, len, sp, tile); break;
-            case 4 | 16: select_split_tile<4, true>(src, base, dst, len, sp, tile); break;
-            case 8 | 16: select_split_tile<8, true>(src, base, dst, len, sp, tile); break;
-            default: break;
-        }
-        return;
+        return with_elem_size_and_base(sg, [&](auto K, auto D) { select_split_tile<K(), D()>(src, base, dst, (u32)sg.len, sp, tile); });
     }
     if (!(sg.mode & PLANES_CLIP)) return whole_segment_tile(sg, tile, lds);
     const u64 ca = clips[2 * lo], cb = clips[2 * lo + 1];
-    switch ((u32)(sg.mode & 0xff) | (sg.base ? 16u : 0u)) {
-        case 2: clip_split_tile<2, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        case 4: clip_split_tile<4, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        case 8: clip_split_tile<8, false>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        case 2 | 16: clip_split_tile<2, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        case 4 | 16: clip_split_tile<4, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        case 8 | 16: clip_split_tile<8, true>(src, base, dst, sg.len, ca, cb, tile, lds); break;
-        default: break;
-    }
+    with_elem_size_and_base(sg, [&](auto K, auto D) {
+        if constexpr (K() > 1) clip_split_tile<K(), D()>(src, base, dst, sg.len, ca, cb, tile, lds);  // (a k = 1 clip is an ordinary segment)
+    });
 }
 
 // The kernel of an update's patch launch (bz3_hip_update_device_range, api_frames.hip): clipped splits beside segments that are moved whole.  It
@@ -963,6 +880,5 @@ __global__ void __launch_bounds__(COPY_THREADS) k_patch_select_segments(const Co
     __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
     patch_segments_tile<true>(segs, tile_start, nseg, clips, selects, (u8 *)lds);
 }
-
 
 }  // namespace bz3

@@ -478,6 +478,40 @@ def test_many_updates_equal_their_single_calls(emu, monkeypatch):
     many_equal_single_calls(emu, many_call, select_update_call)
 
 
+def every_request_form(case_for):
+    """(cases, params, lists) of five frames of element size 4 and six chunks, two of them with a base (case_for(with_base, seed) makes a case): a
+    one-run range, the whole tensor, a two-run request with one piece per period, a two-piece request, and a two-piece request of which every
+    chunk holds bytes of one piece alone.  Their patch segments are a clipped split, six whole splits, a select split over a one-piece table, a
+    select split, and two clipped splits that come from a piece table."""
+    plain, based = case_for(False, 61), case_for(True, 62)
+    s = plain.starts
+    assert plain.sizes == based.sizes == [BS] * 5 + [LAST]
+    plan = [(based, (s[2] + 100, 0, 1), [(0, 777)]),  # one run inside chunk 2
+            (plain, (0, 0, 1), [(0, plain.T)]),  # the whole tensor: every chunk covered
+            (plain, (s[1] + 5, 1000, 2), [(3, 401)]),  # two runs
+            (based, (s[3] + 100, 2000, 2), [(0, 300), (650, 130)]),  # two pieces
+            (plain, (s[4] + 9, 0, 1), [(4, 500), (BS + 20, 100)])]  # one piece in chunk 4, the other in chunk 5
+    return [c for c, _, _ in plan], [p for _, p, _ in plan], [l for *_, l in plan]
+
+
+@pytest.mark.parametrize("window", [2, 16])
+def test_one_call_holds_every_request_form(emu, window, monkeypatch):
+    """The write mirror of test_frame_select_emu's test of this name: the five requests of every_request_form in one _many call.  Windows of two
+    chunks patch the eleven touched chunks in six launches; a window of sixteen patches them in ONE launch, which then holds whole, clipped and
+    select splits side by side, each with the parameters of its own kind.  Every resulting frame is the reference's frame of the updated bytes."""
+    monkeypatch.setenv("BZ3_HIP_FRAME_WINDOW", str(window))
+    ref = require_ref().lib
+    cases, params, lists = every_request_form(lambda wb, seed: Case(ref, 4, 6, wb, seed=seed))
+    ups = [index_update(c, *p, l) for c, p, l in zip(cases, params, lists)]
+    assert sorted(len(touched_chunks(c, u[3])) for c, u in zip(cases, ups)) == [1, 1, 1, 2, 6]
+    rc, got = many_call(emu, [4] * 5, [c.frame for c in cases], params, lists, [u[0] for u in ups], [u[1] for u in ups])
+    assert rc == 0
+    for i, ((code, size, out), (_, _, expect, _)) in enumerate(zip(got, ups)):
+        assert (code, size) == (0, len(expect)), (i, code, size, len(expect))
+        assert out[:size] == expect, ("frames differ", i)
+        assert out[size:] == bytes([FILL]) * (len(out) - size), ("wrote beyond the frame", i)
+
+
 def test_many_whole_call_errors(emu):
     case = Case(require_ref().lib, 1, 1)
     data = pattern(40, 9)

@@ -12,9 +12,9 @@ import bzip3_amd
 from oracle_lib import require_ref
 from test_frame_delta_emu import D
 from test_frame_planes_emu import BS, S, _ref_compress
-from test_frame_select_emu import _pieces_arg, _seg, piece_list
-from test_frame_update_emu import FILL, INIT
-from test_frame_update_select_emu import (covered_and_corrupt_chunks, debug_patch_select_rejects, decode_once, default_cap, delta_frames_match_reference, frames_match_reference,
+from test_frame_select_emu import _pieces_arg, _seg, phi, piece_list, total
+from test_frame_update_emu import FILL, INIT, LAST
+from test_frame_update_select_emu import (covered_and_corrupt_chunks, debug_patch_select_rejects, decode_once, default_cap, delta_frames_match_reference, every_request_form, frames_match_reference,
                                           many_equal_single_calls, mixed_spec_patch_select, normal_forms_are_the_range_update, patch_select_case, periods_spec_patch_select,
                                           sweep_specs_patch_select, update_refusals)
 from test_gpu_frame_delta import _gpu_alloc
@@ -147,6 +147,42 @@ def test_many_updates_equal_their_single_calls_across_windows(gpu_lib, monkeypat
     many = gpu_lib.bz3_hip_update_device_select_many
     assert many(0, None, None, None, None, None, None, None, None, None, None, None) == 0
     assert many(2, None, None, None, None, None, None, None, None, None, None, None) == INIT
+
+
+class _PackedBytes:
+    """A uint8 tensor of five chunks of 65 KiB and a short one, packed with element size 4 (with_base: against a base).  Tensor and base are bytes
+    of few values, so that every chunk codes to less than the block size: the format has no chunk that does not."""
+
+    def __init__(self, lib, with_base, seed):
+        import torch
+
+        self.sizes = [BS] * 5 + [LAST]
+        self.starts, self.T = [j * BS for j in range(6)], 5 * BS + LAST
+        g = torch.Generator().manual_seed(seed)
+        self.x = torch.randint(0, 7, (self.T,), generator=g, dtype=torch.uint8).to("cuda:0")
+        self.base = torch.randint(0, 5, (self.T,), generator=g, dtype=torch.uint8).to("cuda:0") if with_base else None
+        self.p = bzip3_amd.pack_tensor(self.x, BS, planes=4, base=self.base, lib=lib)
+        assert self.p.block_size == BS and self.p.delta == with_base
+
+
+@pytest.mark.parametrize("window", [2, 16])
+def test_one_call_holds_every_request_form(gpu_lib, window, monkeypatch):
+    """The device twin of test_frame_update_select_emu's test of this name, through update_tensors_select: the five request forms in ONE call, in
+    windows of two chunks and in one window, whose patch launch then holds whole, clipped and select splits.  Every frame is the one pack_tensor
+    gives for the updated tensor."""
+    import torch
+
+    monkeypatch.setenv("BZ3_HIP_FRAME_WINDOW", str(window))
+    cases, params, lists = every_request_form(lambda wb, seed: _PackedBytes(gpu_lib, wb, seed))
+    datas, bases, wants = [], [], []
+    for i, (c, (offset, stride, count), pieces) in enumerate(zip(cases, params, lists)):
+        idx = torch.from_numpy(phi(offset, stride, pieces, count * total(pieces))).to("cuda:0")
+        datas.append(torch.randint(0, 9, (idx.numel(),), generator=torch.Generator().manual_seed(70 + i), dtype=torch.uint8).to("cuda:0"))
+        bases.append(None if c.base is None else c.base[idx])
+        wants.append(c.x.index_copy(0, idx, datas[-1]))
+    got = bzip3_amd.update_tensors_select([c.p.frame for c in cases], *zip(*params), lists, datas, planes=4, bases=bases, lib=gpu_lib, block_sizes=[BS] * 5)
+    for i, (c, f, want) in enumerate(zip(cases, got, wants)):
+        assert torch.equal(f, bzip3_amd.pack_tensor(want, BS, planes=4, base=c.base, lib=gpu_lib).frame), ("frames differ", i)
 
 
 # ---- the Python layer ---------------------------------------------------------------------------------------------------------
