@@ -1,4 +1,4 @@
-"""Differential fuzzer (CPU, emulator): every CM kernel variant (whole model, row caches of 96 / 44 / 56 / 40 slots) against the oracle on random sources (Zipf alphabets of 2-255 symbols, BWT output of text, runs, noise),
+"""Differential fuzzer (CPU, emulator): every CM kernel variant (whole model, row caches of 96 / 44 / 56 / 40 slots) against the oracle on random sources (Zipf alphabets of 2-255 symbols, BWT output of text, runs, noise, straddle blocks of tests/cm_cases.py),
 truncated streams included, plus block round trips with classic and lean states.  Not collected by pytest:
     python tests/fuzz_cm_variants.py <seed> <seconds>
 Round 1: seeds 1-3 x 2400 s = 2,389 stage iterations + 341 block round trips, 0 mismatches.
@@ -8,6 +8,7 @@ import sys, os, time, ctypes as C
 HERE = os.path.dirname(os.path.abspath(__file__)); sys.path[:0] = [os.path.dirname(HERE), HERE, os.path.join(HERE, 'emu')]
 import numpy as np
 import bzip3_amd, datagen
+import cm_cases
 from build_emu import build
 from oracle_lib import Oracle
 lib = bzip3_amd._declare(C.CDLL(build()))
@@ -18,7 +19,7 @@ t0 = time.time(); it = 0; bad = 0
 text = datagen.shakespeare()
 while time.time() - t0 < budget:
     it += 1
-    kind = rng.integers(0, 4)
+    kind = rng.integers(0, 5)
     n = int(rng.integers(1, 3500))
     if kind == 0:
         nsym = int(rng.integers(2, 256)); a = float(rng.uniform(0.2, 3.0))
@@ -30,8 +31,10 @@ while time.time() - t0 < budget:
     elif kind == 2:  # runs
         vals = rng.integers(0, 256, size=max(1, n // 20), dtype=np.uint8); lens = rng.integers(1, 60, size=len(vals))
         d = bytes(np.repeat(vals, lens)[:n])
-    else:
+    elif kind == 3:
         d = bytes(rng.integers(0, 256, size=n, dtype=np.uint8))
+    else:  # the interval keeps straddling a multiple of 2^24: ranges 0 and 1, four bytes at one bit (shorter than 1024 bytes: no row cache gives it up)
+        d = cm_cases.straddle(seed * 100003 + it, min(n, 1000), force_one=bool(it & 1))[0]
     if not d: continue
     mode = int(rng.choice([9, 9, 9, 0, 1, 2]))  # tiny cache (recycles slots all the time), whole model, the shipped caches
     lib.bz3_hip_set_cm_mode(mode)
