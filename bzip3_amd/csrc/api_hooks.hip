@@ -405,16 +405,17 @@ BZIP3_API void bz3_hip_stage_cm_decode(const uint8_t * in, int32_t in_size, uint
 // variant the current mode selects (no hand-back of given-up blocks: this measures the variant itself).  Returns the launch
 // time in ms (HIP events).  out receives the n decoded bytes of copy 0.  With BZ3_CM_DEBUG=3 the guess-ahead decoder leaves
 // cycle counters instead of the first output bytes (walker: wait, walk, slow-path bytes, wrong guesses at u64[0..3]; model
-// wave 1: speculate, wait, redo, wrong guesses at u64[8..11]); `counters`, if not NULL, receives u64[16] per copy.
+// wave 1: speculate, wait, redo at u64[8..10]; the walker's wait behind wrong guesses and its right guesses at u64[4..5]); `counters`, if not
+// NULL, receives u64[16] per copy.  The counters need a block of 256 bytes or more.
 BZIP3_API float bz3_hip_stage_cm_decode_many(const uint8_t * in, int32_t in_size, uint8_t * out, int32_t n, int32_t copies, uint64_t * counters) {
     return stage_guard([&]() -> float {
         StageEnv e;
-        if (copies < 1 || n < 256) return -1.f;
+        const char * dbg = getenv("BZ3_CM_DEBUG");
+        const u32 debug = dbg ? (u32)atoi(dbg) : 0u;
+        if (copies < 1 || n < 1 || ((debug || counters) && n < 256)) return -1.f;
         u8 * d = e.dev((size_t)in_size + 64, in, (size_t)in_size);
         const size_t stride = ((size_t)n + 64 + 255) & ~(size_t)255;
         u8 * o = e.dev(stride * (size_t)copies);
-        const char * dbg = getenv("BZ3_CM_DEBUG");
-        const u32 debug = dbg ? (u32)atoi(dbg) : 0u;
         const int variant = cm_variant_for(e.ctx, (size_t)copies, false);
         u8 * spill = cm_variant_has_rows(variant) ? e.dev(CM_SPILL_BYTES * (size_t)copies) : nullptr;
         u32 * status = (u32 *)e.dev(4 * (size_t)copies + 64);

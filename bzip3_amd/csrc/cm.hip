@@ -279,12 +279,7 @@ __device__ __forceinline__ void cm_pair_store(u16 * p, u32 w) {
         reinterpret_cast<PackedU32 *>(p)->v = w;
     }
 }
-#ifndef BZ3_EMU  // the same through 32-bit LDS pointers (the decoder's model waves); the emulator's LDS is ordinary memory
-template <bool HALVES>
-__device__ __forceinline__ u32 cm_pair_load(const __attribute__((address_space(3))) u16 * p) {
-    if (HALVES) return (u32)p[0] | ((u32)p[1] << 16);
-    return reinterpret_cast<const __attribute__((address_space(3))) PackedU32 *>(p)->v;
-}
+#ifndef BZ3_EMU  // the store through 32-bit LDS pointers (the decoder's model waves); the emulator's LDS is ordinary memory
 template <bool HALVES>
 __device__ __forceinline__ void cm_pair_store(__attribute__((address_space(3))) u16 * p, u32 w) {
     if (HALVES) {
@@ -756,6 +751,16 @@ __device__ __forceinline__ u32 cm_xad(u32 a, u32 b, u32 c) {
     return r;
 #endif
 }
+// the same with a wave-uniform c taken straight from its scalar register (as a "v" operand it costs a v_mov first)
+__device__ __forceinline__ u32 cm_xad_uniform(u32 a, u32 b, u32 c) {
+#ifdef BZ3_EMU
+    return (a ^ b) + c;
+#else
+    u32 r;
+    asm("v_xad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(c));
+    return r;
+#endif
+}
 // acc = 2 * acc + bit, the bit given as a wave-wide vote mask (v_addc_co_u32 with the mask as carry-in)
 __device__ __forceinline__ u32 cm_shift_in(u32 acc, u64 vote, bool bit) {
 #ifdef BZ3_EMU
@@ -766,6 +771,31 @@ __device__ __forceinline__ u32 cm_shift_in(u32 acc, u64 vote, bool bit) {
     u64 carry_out;
     asm("v_addc_co_u32 %0, %1, %0, %0, %2" : "+v"(acc), "=s"(carry_out) : "s"(vote));
     return acc;
+#endif
+}
+
+// the first bit: acc = bit (no register to clear first)
+__device__ __forceinline__ u32 cm_shift_in_first(u64 vote, bool bit) {
+#ifdef BZ3_EMU
+    (void)vote;
+    return bit ? 1u : 0u;
+#else
+    (void)bit;
+    u32 acc;
+    u64 carry_out;
+    asm("v_addc_co_u32 %0, %1, 0, 0, %2" : "=v"(acc), "=s"(carry_out) : "s"(vote));
+    return acc;
+#endif
+}
+// Index of the lowest set bit, -1 when there is none: the scalar find-first-one as the hardware defines it (`__ffsll(mask) - 1` costs a compare and a
+// select for the empty mask, and `__builtin_ctzll` leaves that case undefined).  A readlane with -1 reads lane 63; the callers discard that byte's values.
+__device__ __forceinline__ int cm_lowest_lane(u64 mask) {
+#ifdef BZ3_EMU
+    return mask ? __builtin_ctzll(mask) : 63;  // (the lane a readlane with -1 reads)
+#else
+    int w;
+    asm("s_ff1_i32_b64 %0, %1" : "=s"(w) : "s"(mask));
+    return w;
 #endif
 }
 
@@ -867,12 +897,49 @@ __device__ __forceinline__ u64 cm_clock() {
 #else
 #define CM_LDS __attribute__((address_space(3)))
 #endif
-struct CmEvalP {              // CmEval with the cells remembered by address
-    CM_LDS u16 * a1;          // C1[c1][node]
-    u32 p1;                   // its value
+struct CmEvalP {              // what an evaluation leaves for the update of its byte: the two C2 cells, remembered by address
     CM_LDS u16 * ci;          // the first of the two C2 cells
-    u32 w;                    // both cells, x1 | x2 << 16
+    u32 x1, x2;               // their values (packed into one word, x1 | x2 << 16, only where an update or the repair needs it: one wave in four)
 };
+__device__ __forceinline__ u32 cm_pair_word(const CmEvalP & e) { return e.x1 | (e.x2 << 16); }
+// a * b + c for a, b below 2^24 (cm_mad24) left to the compiler: it knows the instruction's latency, where the inline-assembly form is followed by an s_nop
+__device__ __forceinline__ u32 cm_dec_mad24(u32 a, u32 b, u32 c) {
+#ifdef BZ3_EMU
+    return a * b + c;
+#else
+    return __umul24(a, b) + c;
+#endif
+}
+// One 16-bit LDS read that stays one: two plain reads of neighbouring cells are merged into a 32-bit read off its alignment (see cm_pair_load).
+__device__ __forceinline__ u32 cm_lds_u16(const CM_LDS u16 * p) {
+#ifdef BZ3_EMU
+    return *p;
+#else
+    return *reinterpret_cast<const volatile CM_LDS u16 *>(p);
+#endif
+}
+// v, kept in a 32-bit register of its own (no instruction): left alone, the compiler packs two 16-bit values that travel together into one
+// register on one path of the loop and takes them apart again on the next.
+__device__ __forceinline__ u32 cm_whole_register(u32 v) {
+#ifndef BZ3_EMU
+    asm("" : "+v"(v));
+#endif
+    return v;
+}
+// dst = src as an instruction of its own, placed where it is written: the value in `src` can then be updated in place.
+__device__ __forceinline__ void cm_copy(u32 & dst, u32 src) {
+#ifdef BZ3_EMU
+    dst = src;
+#else
+    asm("v_mov_b32 %0, %1" : "=v"(dst) : "v"(src));
+#endif
+}
+// Keeps a rarely taken, wave-uniform `if` a branch: without it the compiler turns the assignment inside into a select that every byte pays for.
+__device__ __forceinline__ void cm_keep_branch() {
+#ifndef BZ3_EMU
+    asm volatile("");
+#endif
+}
 
 template <int R, bool PROF>  // PROF: cycle counters instead of the first output bytes (profiling only, BZ3_CM_DEBUG=3)
 __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restrict__ jobs, CmLdsT<R> & m) {
@@ -901,7 +968,7 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
     if (role != 0) {
         // ---- model waves ------------------------------------------------------------------------------------
         // These four waves are three quarters of the workgroup's instructions, and at three blocks per CU the waves of a SIMD take turns:
-        // a model wave's instruction costs ~8 cycles, so the ~50 instructions of a byte with a right guess are what the walker (80) has to
+        // a model wave's instruction costs ~8 cycles, so the 37 instructions of a byte with a right guess (tools/cm_isa_count.py) are what the walker (107) has to
         // hide.  Hence: LDS cells are remembered as address-space-3 POINTERS (the address that read a cell also writes it back: no index
         // arithmetic), the two C2 rows of the node (run flag 0 / 1) are pointers that only change when the flag does, both order-1
         // counters of the speculative table are the same cell (7 c0 + 9 cell), and two bytes are unrolled per loop trip.
@@ -932,10 +999,8 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         CM_LDS u32 * const ptab0 = (CM_LDS u32 *)&ptab[0][node];
         CM_LDS u32 * const ptab1 = (CM_LDS u32 *)&ptab[1][node];
         // Probability of the node (:377-388) into *pt, given 16 p = (c0 + p1) * 7 + 2 * p2 and the node's C2 row for the run flag.
-        auto evaluate = [&](CM_LDS u32 * pt, CM_LDS u16 * a1, u32 p1, u32 p16, CM_LDS u16 * c2row) __attribute__((always_inline)) -> CmEvalP {
+        auto evaluate = [&](CM_LDS u32 * pt, u32 p16, CM_LDS u16 * c2row) __attribute__((always_inline)) -> CmEvalP {
             CmEvalP e;
-            e.a1 = a1;
-            e.p1 = p1;
 #ifdef BZ3_EMU
             e.ci = c2row + cm_bfe(p16, 16, 4);  // cell p >> 12 of the row
 #else
@@ -946,19 +1011,23 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
                 e.ci = (CM_LDS u16 *)(__UINTPTR_TYPE__)a;
             }
 #endif
-            e.w = cm_pair_load<CM_DEC_PAIR_HALVES>(e.ci);       // x1 | x2 << 16 (cells j, j + 1)
+            const u32 x1 = cm_lds_u16(e.ci), x2 = cm_lds_u16(e.ci + 1);  // cells j, j + 1 (two aligned 16-bit reads, see cm_pair_load)
+            e.x1 = cm_whole_register(x1);
+            e.x2 = cm_whole_register(x2);
             const int p = (int)(p16 >> 4);
-            const int x1 = (int)(e.w & 0xFFFFu), x2 = (int)(e.w >> 16);
-            const int ssep = x1 + (((x2 - x1) * (p & 4095)) >> 12);
-            *pt = cm_mad24((u32)ssep, 3u, (u32)p) << 14;       // (ssep < 2^16)
+            const int ssep = (int)x1 + ((((int)x2 - (int)x1) * (p & 4095)) >> 12);
+            *pt = cm_dec_mad24((u32)ssep, 3u, (u32)p) << 14;       // (ssep < 2^16)
             return e;
         };
         // byte 0: nothing to guess (c1 = c2 = 0, run = 1, :367-372)
-        const u32 first = *c1col;
-        CmEvalP prev = evaluate(ptab0, c1col, first, cm_mad24(c0 + first, 7u, 2u * first), c2row0);
+        CM_LDS u16 * a1 = c1col;  // the order-1 cell of the node in the row of the newest confirmed byte; it changes on a wrong guess only
+        u32 p1 = *a1;             // its value
+        u32 c0_old = c0, p1_old = p1;  // what a speculative update overwrote, in the lanes it ran in (the repair puts them back)
+        CmEvalP prev = evaluate(ptab0, cm_dec_mad24(c0 + p1, 7u, 2u * p1), c2row0);
         u32 k1 = 0;        // newest confirmed byte (byte i-2 inside the loop; the initial c1 = 0 before the block starts)
-        u32 run_prev = 1;  // run counter the evaluation of byte i-1 was made with
-        CM_LDS u16 * c2row = c2row0;  // the C2 row for the run flag of the NEXT speculative evaluation (flag = run_prev + 1 > 2)
+        u32 i_switch = 2;  // the byte whose speculative evaluation switches the run flag: the reference's run counter (1 at the start of a block) reaches 3 there
+        u32 n_live = n;    // the loop's bound; 0 once the block was given up
+        CM_LDS u16 * c2row = c2row0;  // the C2 row for the run flag of the NEXT speculative evaluation (row 1 from byte i_switch on)
         CmRowCache<R> & rc = rcs[R ? role - 1 : 0];
         CmRowState rs;
         u16 * __restrict__ spill = global_ptr<u16>(jobs[blockIdx.x].spill);
@@ -973,28 +1042,31 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         // One byte: `prev` = what the evaluation of byte i-1 left, `cur` receives that of byte i.  Two bytes per loop trip with the two
         // records swapping roles, so that neither they nor the table buffer / the s_done word of a byte cost a move or an address
         // computation (BUF = i & 1 is a compile-time constant).  Returns false when the block was given up.
-        auto step = [&](const u32 i, auto buf_tag, const CmEvalP & prev, CmEvalP & cur) __attribute__((always_inline)) -> bool {
+        auto step = [&](const u32 i, auto buf_tag, const CmEvalP & prev, CmEvalP & cur) __attribute__((always_inline)) {
             constexpr u32 BUF = decltype(buf_tag)::value;
             CM_LDS u32 * const pt = BUF ? ptab1 : ptab0;
-            bool give_up = false;
             u64 m0 = 0, m1 = 0, m2 = 0;
             if (PROF) m0 = cm_clock();
-            // -- speculate: byte i-1 == k1.  Update of byte i-1 (:396-399, :411-414; branch-free, see cm_upd) ...
+            // -- speculate: byte i-1 == k1.  Update of byte i-1 (:396-399, :411-414; branch-free, see cm_upd), IN PLACE: c0 and p1 (= C1[k1][node]:
+            // byte i-1 was evaluated with c1 = k1, so this is the cell its update moves) are overwritten, and only the lanes that do so keep
+            // the old values for the repair -- the waves without a lane on the path (three of four) copy nothing ...
             const u32 g = k1;
             const bool on_g = (g >> shr) == nodelow;
-            const u32 c0_old = c0;
-            u32 cell = prev.p1;  // C1[k1][node]: byte i-1 was evaluated with c1 = k1, so this is the cell its update moves
             if (on_g) {
                 const u32 mk = 0u - ((g >> bitpos) & 1u);
+                cm_copy(c0_old, c0);
+                cm_copy(p1_old, p1);
                 c0 = cm_upd(c0, 2, mk & 16383u);
-                cell = cm_upd(prev.p1, 4, mk & 4095u);
-                *prev.a1 = (u16)cell;
-                cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, cm_upd_pair6(prev.w, mk & 0x03FF03FFu));
+                p1 = cm_upd(p1, 4, mk & 4095u);
+                *a1 = (u16)p1;
+                cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, cm_upd_pair6(cm_pair_word(prev), mk & 0x03FF03FFu));
             }
-            // ... and the table of byte i with c1 = g, c2 = k1: both order-1 counters are `cell`, the run counter goes up
-            run_prev++;
-            if (__builtin_expect(run_prev == 3u, 0)) c2row = c2row1;
-            cur = evaluate(pt, prev.a1, cell, cm_mad24(cell, 9u, cm_mad24(c0, 7u, 0u)), c2row);
+            // ... and the table of byte i with c1 = g, c2 = k1: both order-1 counters are p1, the run counter goes up
+            if (__builtin_expect(i == i_switch, 0)) {
+                c2row = c2row1;
+                cm_keep_branch();
+            }
+            cur = evaluate(pt, cm_dec_mad24(p1, 9u, cm_dec_mad24(c0, 7u, 0u)), c2row);
             u32 early = 0;       // CM_EXP_EARLY_ROW: C1[mru][node], asked for while the walker still walks
             bool early_ok = false;
             if (CM_EXP_EARLY_ROW && mru < 0x100u) {
@@ -1013,63 +1085,65 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
             }
             k1 = c;
             if (c != g) {
-                // wrong guess: put the old counters back (the old values are still in `prev`), apply the real update
-                // and evaluate again.  The new c1 row differs from the row being repaired, so its read goes first.
+                // wrong guess: put the old counters back, apply the real update and evaluate again.  The new c1 row differs from the
+                // row being repaired, so its read goes first.
                 // (Issue priority for these waves during the repair -- the walker waits for it -- was measured in round 3: 804 -> 800 ns per
                 // byte at three per CU, nothing.)
                 u32 row = c;
                 if (R) {
                     row = (cm_readlane(rowreg, (int)(c >> 2)) >> (8u * (c & 3u))) & 0xFFu;
                     if (__builtin_expect(row >= CM_ROW_SPILLED, 0)) {
-                        // the only row still needed is the one of byte i-2 (prev.a1 points into it): pin it
+                        // the only row still needed is the one of byte i-2 (a1 points into it): pin it
                         rs.tick++;
-                        if (lane == 0) rc.stamp[cm_uniform((u32)(prev.a1 - c1col) >> 8)] = rs.tick;
+                        if (lane == 0) rc.stamp[cm_uniform((u32)(a1 - c1col) >> 8)] = rs.tick;
                         wave_sync();
                         row = cm_rows_fetch<R, 1>(m, rc, rs, spill, c, row, node);
                         rowreg = reinterpret_cast<const u32 *>(rc.row_of)[lane];
                         if (__builtin_expect(rs.misses > miss_base + (i >> miss_shift), 0)) {
                             // the working set does not fit (every model wave gets here at the same byte): the block is given up.  The repair
                             // below still runs -- no second way out of this branch, the compiler pays for one with moves on every path --
-                            // and the walker reads s_abort behind barrier 2
-                            give_up = true;
+                            // and the loop ends at its next test; the walker reads s_abort behind barrier 2
+                            n_live = 0;
                             if (threadIdx.x == 64) *global_ptr<u32>(jobs[blockIdx.x].status) = 1u;
                             LDS_POKE(s_abort, 1u);
                         }
                     }
                 }
-                CM_LDS u16 * const a1 = c1col + row * 256u;
-                u32 p1;
-                if (CM_EXP_EARLY_ROW && early_ok && c == mru) p1 = early;  // (wave-uniform branch)
-                else p1 = *a1;
+                CM_LDS u16 * const a1n = c1col + row * 256u;
+                u32 p1n;
+                if (CM_EXP_EARLY_ROW && early_ok && c == mru) p1n = early;  // (wave-uniform branch)
+                else p1n = *a1n;
                 if (CM_EXP_EARLY_ROW) mru = g;  // the run of g's ends here: g is what a later wrong guess most likely returns to
-                u32 cell2 = prev.p1;
                 if (on_g) {
                     c0 = c0_old;
-                    cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, prev.w);
+                    p1 = p1_old;
+                    cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, cm_pair_word(prev));
                 }
                 if ((c >> shr) == nodelow) {
                     const u32 mk = 0u - ((c >> bitpos) & 1u);
                     c0 = cm_upd(c0, 2, mk & 16383u);
-                    cell2 = cm_upd(prev.p1, 4, mk & 4095u);
-                    cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, cm_upd_pair6(prev.w, mk & 0x03FF03FFu));
+                    p1 = cm_upd(p1, 4, mk & 4095u);
+                    cm_pair_store<CM_DEC_PAIR_HALVES>(prev.ci, cm_upd_pair6(cm_pair_word(prev), mk & 0x03FF03FFu));
                 }
-                *prev.a1 = (u16)cell2;  // (unconditionally: storing the value that is there already costs less than finding out)
+                *a1 = (u16)p1;  // (unconditionally: storing the value that is there already costs less than finding out)
                 c2row = c2row0;  // c != k1: the run counter restarts
-                cur = evaluate(pt, a1, p1, cm_mad24(c0 + p1, 7u, 2u * cell2), c2row0);
+                cur = evaluate(pt, cm_dec_mad24(c0 + p1n, 7u, 2u * p1), c2row0);
+                a1 = a1n;
+                p1 = p1n;
                 if (R) wave_sync();  // (test emulation: a row fetch de-synchronises the fibers of a wave; no instruction on the GPU)
                 if (PROF) mprof_redo += cm_clock() - m2;  // up to the arrival at barrier 2
                 __syncthreads();  // barrier 2: the corrected table of byte i is there
-                run_prev = 0;
+                i_switch = i + 3u;  // (the reference's run counter restarts at 0 and switches the flag when it reaches 3)
             }
-            return !give_up;
         };
         CmEvalP other = prev;
-        for (u32 i = 1; i < n;) {
-            if (!step(i, CmConst<1>{}, prev, other)) return;
-            if (++i >= n) break;
-            if (!step(i, CmConst<0>{}, other, prev)) return;
+        for (u32 i = 1; i < n_live;) {
+            step(i, CmConst<1>{}, prev, other);
+            if (++i >= n_live) break;
+            step(i, CmConst<0>{}, other, prev);
             ++i;
         }
+        if (R && n_live == 0) return;  // given up
         if (PROF && n >= 256 && threadIdx.x == 64) {  // profiling only: model wave 1's phases (cycles) at u64[8..10] of the output
             u64 * o = reinterpret_cast<u64 *>(out) + 8;
             o[0] = mprof_spec;
@@ -1116,7 +1190,7 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         CM_NEXT_BYTE(b);
         code = (code << 8) + b;
     }
-    u64 prof_wait = 0, prof_walk = 0, prof_slow = 0, prof_miss = 0, prof_wait_miss = 0;  // PROF
+    u64 prof_wait = 0, prof_walk = 0, prof_slow = 0, prof_miss = 0, prof_hit = 0, prof_wait_miss = 0;  // PROF
     u64 t0 = 0, t1 = 0;
     u32 P0, P1, P2, P3, P4, P5, P6, P7a, P7b;  // this lane's slice of the table of the byte being decoded
     u32 vi = cm_opaque_zero();                 // the byte index as a vector register: the offset of the byte's store
@@ -1134,21 +1208,30 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         range = cm_xad(t_, (NB), keep_);                           /* t  |  range - t - 1 */          \
         d = cm_xad(t_ | ~(NB), 0xFFFFFFFFu, d);                    /* d  |  d - t - 1     */          \
     } while (0)
+// the first level: range and d are still the wave-uniform coder state (D0 = code - low)
+#define CM_WALK_SPEC_FIRST(P, NB, D0)                                                                 \
+    do {                                                                                              \
+        const u32 keep_ = range & (NB);                                                               \
+        const u32 t_ = (u32)(((u64)range * (P)) >> 32);                                               \
+        range = cm_xad(t_, (NB), keep_);                                                              \
+        d = cm_xad_uniform(t_ | ~(NB), 0xFFFFFFFFu, (D0));                                            \
+    } while (0)
 // one decoded level: the lane takes the bit it decodes and shifts it into cb
-#define CM_WALK_REAL(P, BIT)                                                                          \
+#define CM_WALK_REAL(P, BIT, FIRST)                                                                   \
     do {                                                                                              \
         const u32 t_ = (u32)(((u64)range * (P)) >> 32);                                               \
         BIT = d <= t_;                                                                                \
-        cb = cm_shift_in(cb, __ballot(BIT), BIT);                                                     \
+        cb = (FIRST) ? cm_shift_in_first(__ballot(BIT), BIT) : cm_shift_in(cb, __ballot(BIT), BIT);   \
         range = BIT ? t_ : range + ~t_;                            /* t  |  range - t - 1 */          \
         d = BIT ? d : d + ~t_;                                                                        \
     } while (0)
     // Decodes byte i from the table in P0..P7b; returns it.
     auto walk = [&]() __attribute__((always_inline)) -> u32 {
         u32 range = range_u, low;  // per-lane copies of the wave-uniform coder state
-        u32 d = code - low_u;
-        const bool inside = d <= range_u;  // low <= code <= high: always, unless a truncated stream fed -1 bytes (:345)
-        CM_WALK_SPEC(P0, nb0);  // :453-489
+        const u32 d0 = code - low_u;
+        u32 d;
+        const bool inside = d0 <= range_u;  // low <= code <= high: always, unless a truncated stream fed -1 bytes (:345)
+        CM_WALK_SPEC_FIRST(P0, nb0, d0);  // :453-489
         CM_WALK_SPEC(P1, nb1);
         const u64 ok1 = __ballot(d <= range);
         CM_WALK_SPEC(P2, nb2);
@@ -1162,10 +1245,10 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         const u64 ok = ok1 & ok3 & __ballot(d <= range);
         u32 cb = 0;
         bool bit6, bit7;
-        CM_WALK_REAL(P6, bit6);
+        CM_WALK_REAL(P6, bit6, true);
         const u32 P7f = bit6 ? P7b : P7a;
-        CM_WALK_REAL(P7f, bit7);
-        const int w = __ffsll((unsigned long long)ok) - 1;
+        CM_WALK_REAL(P7f, bit7, false);
+        const int w = cm_lowest_lane(ok);  // (no survivor: the byte goes to the checked walk and what is read here is dropped)
         const u32 low_f = code - cm_readlane(d, w), range_f = cm_readlane(range, w);
         // The fast result is committed unconditionally and the checked walk is a plain `if` without an `else`: with two arms the
         // compiler routes every loop-carried value (code, the input window, ...) through copies on BOTH arms.
@@ -1173,7 +1256,9 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         u32 c = ((u32)w << 2) | cm_readlane(cb, w);
         low_u = low_f;
         range_u = range_f;
-        const bool good = inside & ((ok & (ok - 1ull)) == 0ull) & (ok != 0ull) & ((low_f ^ (low_f + range_f)) >= (1u << 24));
+        // exactly one survivor, inside the interval, no renormalisation due: one number and one comparison (three flags cost a mask and an AND each)
+        const u32 verdict = (u32)__popcll(ok) | (inside ? 0u : 128u) | ((low_f ^ (low_f + range_f)) >= (1u << 24) ? 0u : 128u);
+        const bool good = verdict == 1u;
         if (__builtin_expect(!good, 0)) {  // a renormalisation was due on the true path: decode this byte again, checking every level
             if (PROF) prof_slow++;
             low = low_old;
@@ -1207,6 +1292,7 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         c1 = c;
         if (i + 1u == n) return false;
         __syncthreads();  // barrier 1: the speculative table of byte i+1 is complete, the models read byte i
+        if (PROF && hit) prof_hit++;
         if (!hit) {
             if (PROF) prof_miss++;
             __syncthreads();  // barrier 2: the corrected table
@@ -1241,11 +1327,13 @@ __device__ __forceinline__ void cm_decode_block_sync(const CmDecodeJob * __restr
         o[2] = prof_slow;
         o[3] = prof_miss;
         o[4] = prof_wait_miss;  // the part of prof_wait spent behind wrong guesses
+        o[5] = prof_hit;        // right guesses (with o[3]: every byte but the last)
         reinterpret_cast<u32 *>(out)[22] = hw_id;
         reinterpret_cast<u32 *>(out)[23] = xcc_id;
     }
 #undef CM_SYNC_FETCH
 #undef CM_WALK_SPEC
+#undef CM_WALK_SPEC_FIRST
 #undef CM_WALK_REAL
 }
 
