@@ -112,6 +112,10 @@ def _declare(L, strict=True):
         "bz3_hip_update_device_select_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint64)),
                                                         C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_patch_select": (i32, [vp, vp, vp, C.POINTER(C.c_uint64), i32, C.POINTER(C.c_uint64), C.c_uint64]),
+        "bz3_hip_resize_device": (C.c_int, [u32, u32, vp, sz, C.c_uint64, vp, sz, vp, vp, C.POINTER(sz)]),
+        "bz3_hip_resize_device_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
+                                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_replane": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -1193,6 +1197,172 @@ def update_tensor_rows(p, start, values, base=None, lib=None):
     carried over; `crc` of the result is None, because the checksum of the whole tensor cannot be had without the bytes of the chunks that were
     only copied (verify=True skips such a tensor; pack it anew, or unpack and checksum it, where a checksum is wanted).  `p` is unchanged."""
     return _update_rows_many([p], [(start, values)], [base], lib)[0]
+
+
+def _effective_block_size(block_size, nbytes):
+    """The block size bz3_compress codes `nbytes` bytes with under `block_size` (src/libbz3.c:877-878)."""
+    return max(_KiB65, block_size if block_size <= nbytes else nbytes + nbytes // 50 + 32)
+
+
+def resize_tensors(frames, keeps, datas, planes=1, bases=None, block_sizes=None, lib=None):
+    """New frames that decode to the first keeps[i] bytes of what frames[i] decodes to followed by datas[i], for many frames in ONE call
+    (bz3_hip_resize_device_many) and one synchronisation: the chunks that lie wholly inside the kept bytes are copied as they are, undecoded; of
+    the others at most one per frame is decoded first, the one the kept bytes end in ("Resize").  Result i is byte for byte the frame
+    compress_tensor gives for the new bytes at block_sizes[i].  frames and datas: contiguous uint8 tensors on one GPU (an empty datas[i]
+    truncates).  `block_sizes` is required: the block sizes the frames were made with (PackedTensor.block_size), which the header of a frame of
+    one block does not tell.  `planes` as in decompress_tensors.  `bases[i]`: None, or for a frame made against a base the base's bytes OF THE
+    APPENDED RANGE, as many as datas[i].  A new size that is a non-zero multiple of its block size would lose a block and is refused
+    (BZ3_ERR_INIT), as is a frame that bz3_compress would not have written.  The outputs are views of one allocation (.clone() one to drop the
+    rest).  The inputs are never written.  Raises Bz3Error with .index / .codes / .outs as compress_tensors does.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
+    keeps = [int(k) for k in keeps]
+    if block_sizes is None:
+        raise ValueError("resize_tensors: block_sizes is required")
+    bss = [int(b) for b in block_sizes]
+    if len(keeps) != n or len(datas) != n or len(bss) != n:
+        raise ValueError(f"resize_tensors: {n} frames, {len(keeps)} sizes to keep, {len(datas)} data tensors and {len(bss)} block sizes")
+    if any(k < 0 for k in keeps) or any(not 0 < b < 1 << 32 for b in bss):
+        raise ValueError("resize_tensors: sizes to keep must not be negative, block sizes must be positive")
+    if not frames:
+        return []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
+    dev = _same_device(frames + datas, "resize_tensors")
+    L = lib or load()
+    caps = []
+    for f, keep, d, bs in zip(frames, keeps, datas, bss):
+        total = keep + d.numel()
+        eff = _effective_block_size(bs, total)
+        rebuilt = -(-total // eff) - keep // eff  # the chunks from the one the kept bytes end in on
+        caps.append(13 + f.numel() + rebuilt * (8 + L.bz3_bound(min(eff, total))))
+    outs = _carve(sum(caps), caps, dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    rcs = (C.c_int * n)()
+    torch.cuda.synchronize(dev)
+    rc = L.bz3_hip_resize_device_many(n, (C.c_uint32 * n)(*bss), (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                      (C.c_uint64 * n)(*keeps), (C.c_void_p * n)(*[d.data_ptr() if d.numel() else None for d in datas]),
+                                      (C.c_size_t * n)(*[d.numel() for d in datas]), _ptrs_or_null(bases), _ptrs(outs), out_sizes, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(codes[idx], "bz3_hip_resize_device_many", index=idx, codes=codes, outs=res)
+    return res
+
+
+def _resize_rows_many(ps, specs, bases, lib):
+    """specs[i] = (keep_rows, values or None): the PackedTensors that hold the first keep_rows rows of dimension 0 followed by the rows of
+    `values`.  bases[i]: the rows of the base that pair with `values`.  Every argument is checked before any GPU work; then one
+    bz3_hip_resize_device_many call per distinct block size, the tensors whose new size is not lossless at their block size apart (repacked),
+    and one batched checksum call."""
+    import math
+
+    import torch
+
+    L = lib or load()
+    plan = []
+    for i, (p, (keep_rows, values), b) in enumerate(zip(ps, specs, _bases_arg(bases, len(ps)))):
+        _row_bytes(p, f"tensor {i}")
+        keep_rows = int(keep_rows)
+        if not 0 <= keep_rows <= p.shape[0]:
+            raise ValueError(f"resize: {keep_rows} rows to keep of a tensor of {p.shape[0]} rows")
+        if values is not None:
+            if not isinstance(values, torch.Tensor) or values.device.type != "cuda":
+                raise TypeError(f"resize: the rows of tensor {i} must be a torch tensor on a GPU")
+            if values.dtype != p.dtype or values.dim() != len(p.shape) or tuple(values.shape[1:]) != tuple(p.shape[1:]):
+                raise TypeError(f"resize: the rows of tensor {i} must be {p.dtype} of shape (rows, {', '.join(map(str, p.shape[1:]))})")
+            if values.device != p.frame.device:
+                raise ValueError(f"resize: the rows of tensor {i} are on {values.device}, the frame on {p.frame.device}")
+        added = 0 if values is None else values.shape[0]
+        if not (p.delta and added):
+            b = None  # (a base beside a tensor that was packed without one, or beside no new rows, is not used)
+        elif b is None:
+            raise ValueError(f"resize: tensor {i} was packed against a base, whose rows are needed to code the new ones")
+        elif not isinstance(b, torch.Tensor) or b.dtype != p.dtype or tuple(b.shape) != tuple(values.shape):
+            raise ValueError(f"resize: base {i} must hold the same rows of the base: {p.dtype} {tuple(values.shape)}")
+        rb = math.prod(p.shape[1:]) * torch.empty(0, dtype=p.dtype).element_size()
+        raw = _as_bytes(values, f"the rows of tensor {i}") if added else torch.empty(0, dtype=torch.uint8, device=p.frame.device)
+        braw = _base_bytes(b, raw.numel(), p.frame.device, f"base {i}")
+        shape = (keep_rows + added, *p.shape[1:])
+        plan.append((keep_rows * rb, raw, braw, shape, (keep_rows + added) * rb, keep_rows == p.shape[0]))
+    frames, sizes = [None] * len(ps), [p.block_size for p in ps]
+    groups = {}
+    for i, (p, (keep, raw, braw, shape, nbytes, _)) in enumerate(zip(ps, plan)):
+        if _lossless_block_size(nbytes, p.block_size, p.planes) == p.block_size:
+            groups.setdefault(p.block_size, []).append(i)
+            continue
+        # the new size would lose a block at p.block_size: the bytes the frame codes (the difference from the base for a delta tensor) are
+        # decoded, cut, joined with the new ones and coded again at the nearest lossless block size
+        old = decompress_tensors([p.frame], planes=[p.planes], lib=L)[0]
+        new = torch.cat([old[:keep], raw if braw is None else raw - braw])
+        sizes[i] = _lossless_block_size(nbytes, p.block_size, p.planes)
+        frames[i] = _compress_many(L, [new], [sizes[i]], [p.planes], new.device, slack=True)[0]
+    for bs, idx in groups.items():
+        got = resize_tensors([ps[i].frame for i in idx], [plan[i][0] for i in idx], [plan[i][1] for i in idx], planes=[ps[i].planes for i in idx],
+                             bases=[plan[i][2] for i in idx], block_sizes=[bs] * len(idx), lib=L)
+        for i, f in zip(idx, got):
+            frames[i] = f
+    # the codec's checksum has no final xor, so it chains: the checksum of an appended tensor is that of the new rows started from the old one
+    chain = [(i, which) for i, (p, pl) in enumerate(zip(ps, plan)) if pl[5]
+             for which in ("crc", "base_crc") if getattr(p, which) is not None and (which == "crc" or pl[2] is not None)]
+    sums = crc32c_tensors([plan[i][1] if which == "crc" else plan[i][2] for i, which in chain], inits=[getattr(ps[i], which) for i, which in chain], lib=L) if chain else []
+    out = []
+    for i, (p, pl) in enumerate(zip(ps, plan)):
+        out.append([p, pl, {"crc": p.crc if pl[5] else None, "base_crc": p.base_crc if pl[5] else None}])
+    for (i, which), c in zip(chain, sums):
+        out[i][2][which] = c
+    return [PackedTensor(frames[i], p.dtype, torch.Size(pl[3]), p.planes, sizes[i], pl[4], p.delta, crcs["base_crc"], crcs["crc"]) for i, (p, pl, crcs) in enumerate(out)]
+
+
+def resize_tensor_rows(p, keep_rows, values=None, base=None, lib=None):
+    """A new PackedTensor that holds the first keep_rows rows of dimension 0 of p's tensor followed by the rows of `values` (None: none), on the
+    frame's GPU, without the tensor ever being materialised (bz3_hip_resize_device): the chunks of the frame that lie wholly inside the kept rows
+    are copied undecoded, at most one chunk is decoded, and only the chunks from there on are coded.  Its frame is byte for byte the one
+    pack_tensor gives for the new tensor at p.block_size and p.planes.  `values`: a GPU tensor of p's dtype and trailing shape (TypeError
+    otherwise); 0 <= keep_rows <= p.shape[0] (ValueError; a 0-d tensor has no rows).  A tensor packed against a base needs `base` for the new
+    rows: the rows of the grown base that pair with `values`, of values' shape (ValueError without them).  All of that is checked before any GPU
+    work.  FALLBACK: where the new size is not lossless at p.block_size (a non-zero multiple of it: _lossless_block_size(new nbytes,
+    p.block_size, p.planes) != p.block_size), the tensor's bytes are decoded, joined and packed again as pack_tensor(block_size=p.block_size)
+    packs them, and the result's `block_size` DIFFERS from p's.  shape and nbytes are the new tensor's; planes, dtype and delta are carried over.
+    After a pure append (keep_rows == p.shape[0]) `crc` is the checksum of the grown tensor where p.crc is known, chained from it over the new
+    rows alone (crc32c_tensors with inits), and `base_crc` likewise that of the grown base; after a truncation both are None, as after an update
+    (check_chain reports such links as unchecked).  `p` is unchanged."""
+    return _resize_rows_many([p], [(keep_rows, values)], [base], lib)[0]
+
+
+def append_tensor_rows(p, values, base=None, lib=None):
+    """resize_tensor_rows(p, p.shape[0], values): p's tensor with the rows of `values` appended along dimension 0 -- a KV cache or a token buffer
+    that grows, an embedding table that gains vocabulary rows -- at the cost of the last chunk's decode and the new chunks' encode."""
+    _row_bytes(p, "append")
+    return _resize_rows_many([p], [(p.shape[0], values)], [base], lib)[0]
+
+
+def truncate_tensor_rows(p, rows, lib=None):
+    """resize_tensor_rows(p, rows): the first `rows` rows of dimension 0 of p's tensor."""
+    return _resize_rows_many([p], [(rows, None)], [None], lib)[0]
+
+
+def append_state_dict_rows(packed, rows, base=None, lib=None):
+    """append_tensor_rows for several tensors of a packed state dict: `rows` is {name: values}, and the result a new dict in which those names have
+    the grown PackedTensors and every other name the PackedTensor of `packed` itself.  One batched bz3_hip_resize_device_many call per distinct
+    block size among the named tensors, as pack_state_dict makes one compress call per block size.  `base`: {name: the rows of that tensor's
+    grown base that pair with its new rows}, needed for the named tensors that were packed against one.  A name that is not in `packed`:
+    ValueError.  Everything is checked before any GPU work; `packed` is unchanged."""
+    unknown = [k for k in rows if k not in packed]
+    if unknown:
+        raise ValueError(f"append_state_dict_rows: rows for {unknown[0]!r}, which is not in the dict")
+    names = list(rows)
+    out = dict(packed)
+    if names:
+        for k in names:
+            _row_bytes(packed[k], f"tensor {k!r}")
+        out.update(zip(names, _resize_rows_many([packed[k] for k in names], [(packed[k].shape[0], rows[k]) for k in names],
+                                                [None if base is None else base.get(k) for k in names], lib)))
+    return out
 
 
 def _slice_of(p, sl, what):

@@ -122,11 +122,12 @@ struct GatherList {
     int level = SEG_DELTA;
     bool patched = false;  // the list holds a clipped or a select split: the launch is k_patch_segments or k_patch_select_segments, and holds no partial merge
     bool merged = false;   // the list holds a partial merge
+    bool replaned = false;  // the list holds a replane segment: the launch is k_replane_segments, and holds no select split
     size_t size() const { return v.size(); }
     void clear() {
         v.clear();
         level = SEG_DELTA;
-        patched = merged = false;
+        patched = merged = replaned = false;
     }
     // A segment as it is: a copy, a split, a merge, with or without a base.
     void plain(const CopySeg & sg) { v.push_back({sg, {}}); }
@@ -146,6 +147,16 @@ struct GatherList {
         v.push_back({{src, slot, s, k | PLANES_CLIP, base}, {a, b}});
         level = std::max<int>(level, SEG_CLIP);
         patched = true;
+    }
+    // The kept head of a resized chunk: the chunk bytes [0, a) of the decoded chunk of s_old bytes that `src` holds in split form, to where `slot`,
+    // which is to hold the split form of a chunk of s_new bytes, keeps them (planes.hpp, "Replane"); a <= min(s_old, s_new).  k = 1 is a plain copy,
+    // and nothing where the chunk was decoded into `slot` itself.
+    void replane(u64 src, u64 slot, u64 s_old, u64 s_new, u64 k, u64 a) {
+        if (a == 0 || (k <= 1 && src == slot)) return;
+        if (k <= 1) return plain({src, slot, a, 0, 0});
+        v.push_back({{src, slot, s_new, k | PLANES_REPLANE, 0}, {s_old, a}});
+        level = std::max<int>(level, SEG_CLIP);
+        patched = replaned = true;
     }
     // The same for a chunk of which a strided range wants the nbytes bytes c(u) (planes.hpp, "Strided merge"; first in [1, run], stride >= run):
     // a share within one run (nbytes <= first) is the clipped or whole segment above, anything else a strided merge.
@@ -183,7 +194,7 @@ struct GatherList {
 };
 
 // Copies the segments of g (absolute device addresses) in one launch on stream s; d_tab holds table_bytes(g.size(), g.level) bytes.  The kernel
-// is k_patch_segments for a list with a clipped split (k_patch_select_segments where it holds a select split as well), else the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
+// is k_patch_segments for a list with a clipped split (k_patch_select_segments where it holds a select split as well, k_replane_segments where it holds a replane segment), else the one of g.level; at SEG_DELTA k_delta_segments where a segment has a base, else k_move_segments where one has an element size, else
 // k_copy_segments (planes.hpp).  The caller synchronises (the host tables are staged from pageable memory and must outlive the copy).
 void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, hipStream_t s) {
     const size_t n = g.size(), bytes = table_bytes(n, g.level), seg_bytes = align16(n * sizeof(CopySeg));
@@ -207,6 +218,9 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
         } else if (sg.mode & PLANES_CLIP) {
             memcpy(staging.data() + clip_off + i * 2 * sizeof(u64), row, 2 * sizeof(u64));
             tiles += clip_tiles(sg.len, k, row[0], row[1]);
+        } else if (sg.mode & PLANES_REPLANE) {  // (its row, len_old and a, lies in the clip table)
+            memcpy(staging.data() + clip_off + i * 2 * sizeof(u64), row, 2 * sizeof(u64));
+            tiles += replane_tiles(row[1], k);
         } else {
             tiles += segment_tiles(sg);
         }
@@ -214,6 +228,7 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
         delta |= sg.base != 0;
     }
     if (g.patched && g.merged) throw std::logic_error("patch segments and partial merges in one launch");
+    if (g.replaned && g.level == SEG_SELECT) throw std::logic_error("a replane segment and a select split in one launch");
     if (tiles >= ((u64)1 << 24)) throw std::length_error("segment copy larger than 256 GiB");
     starts[n] = (u32)tiles;
     if (!tiles) return;
@@ -224,7 +239,8 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
     const u64 * d_clips = (const u64 *)(d_tab + clip_off);
     const u64 * d_periods = (const u64 *)(d_tab + period_off);
     const u64 * d_selects = (const u64 *)(d_tab + select_off);
-    if (g.patched && g.level == SEG_SELECT) launch(k_patch_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_selects);
+    if (g.replaned) launch(k_replane_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
+    else if (g.patched && g.level == SEG_SELECT) launch(k_patch_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_selects);
     else if (g.patched) launch(k_patch_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips);
     else if (g.level == SEG_SELECT) launch(k_select_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods, d_selects);
     else if (g.level == SEG_STRIDED) launch(k_strided_segments, grid, block, 0, s, d_segs, d_starts, (u32)n, d_clips, d_periods);
@@ -1161,6 +1177,300 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     }
 }
 
+// ---- resize: n frames whose buffers passed the pointer checks, on device dev ------------------------------------------------------
+// The effective block size bz3_compress codes t bytes with under `block_size` (src/libbz3.c:877-878), in 64 bits.
+u64 effective_block_size(u32 block_size, u64 t) {
+    const u64 bs = (u64)block_size > t ? (u64)t + t / 50 + 32 : (u64)block_size;  // (bz3_bound, which may not fit size_t's callers' 32 bits)
+    return std::max<u64>(bs, (u64)KiB65);
+}
+
+// Frame i keeps the first keeps[i] bytes of what it decodes to, gets datas[i][0, ws[i]) behind them (less bases[i][0, ws[i]) where there is a base)
+// and the new frame goes to outs[i] (bz3_hip.h, "Resize").  T' = keep + w and B = eff(block_size, T') are known before the walk; new chunk c is
+// [c B, min((c + 1) B, T')).
+//   1. One walk reads every frame header, then plain walks read every chunk header of every frame, as the update's do.  They give T, tell a regular
+//      frame from any other, and give the copied prefix: with the header's block size equal to B, the old chunks that end at or below keep and
+//      have the extent of the new chunk of their number.  Everything behind them is rebuilt.  The first rebuilt chunk holds kept bytes iff it
+//      starts below keep; they are the first a = min(keep, its end) - its start bytes of it AND of the one old chunk that starts where it does
+//      (the same number under one block size; chunk 0 on both sides where the block size changes, which takes a frame of one chunk on one side).
+//      That old chunk is the frame's cut chunk; no other chunk of the frame is decoded.
+//   2. The rebuilt chunks of all frames form one list in frame order and go through windows of as many slots as the call has states.  Before
+//      anything is written to an `out`, every cut chunk of the call is decoded whole; where the list fits one window those decodes are the ones the
+//      window uses, a longer list decodes them once to check them and again in the window that codes them (one chunk per frame).
+//   3. Per window: the cut chunks into the parking slots (k = 1: into the chunk's own slot, which needs no move) and run_decode on them; ONE patch
+//      launch -- a replane segment from the parking slot for the kept head, a clipped or whole split from `data` for the rest --; run_encode; one
+//      pack launch: the new frame header and the new chunk headers from the staged buffer, the coded slots, and per frame one verbatim run, the
+//      copied chunks, which are a prefix.
+// A frame that fails in 1 or 2 has its code, size 0 and an untouched `out`; one that fails in 3 (not expected) its code and size 0.
+void resize_frames(int dev, s32 n, const u32 * block_sizes, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const u64 * keeps,
+                   const u8 * const * datas, const size_t * ws, const u8 * const * bases, u8 * const * outs, size_t * out_sizes, int * rcs) {
+    struct Frame {
+        u64 keep = 0, Tn = 0, B = 0;       // T' and the new block size
+        u64 need = 13, copy_end = 13;      // the capacity the frame needs; the end of its copied chunks in `in`
+        u32 ncopy = 0, chunks = 0, packed = 0;  // copied chunks; rebuilt chunks and those of them that are packed
+        u64 nb = 0;                        // new chunks
+        bool regular = true, has_cut = false, started = false;
+        WalkChunk cut{};                   // the old chunk that holds the kept bytes of the first rebuilt chunk
+        size_t cap = 0, pos = 0;
+    };
+    struct Rebuilt {
+        s32 frame;
+        u64 start, size, a;  // the new chunk's first byte and size; its kept bytes (those of the frame's cut chunk)
+    };
+    std::vector<Frame> fr((size_t)n);
+    std::vector<WalkPos> pos((size_t)n);
+    std::vector<char> live((size_t)n, 0);
+    std::vector<Rebuilt> list;
+    bool any = false;
+    for (s32 i = 0; i < n; i++) {
+        rcs[i] = BZ3_OK;
+        Frame & x = fr[i];
+        x.cap = out_sizes[i];
+        out_sizes[i] = 0;
+        x.keep = keeps ? keeps[i] : 0;
+        x.Tn = x.keep + (u64)ws[i];
+        if (x.Tn < x.keep) rcs[i] = BZ3_ERR_DATA_TOO_BIG;  // (keep + w does not fit 64 bits: keep > T whatever T is)
+        else if (in_sizes[i] < 13) rcs[i] = BZ3_ERR_MALFORMED_HEADER;  // :930
+        else live[i] = any = 1;
+        x.B = effective_block_size(block_sizes[i], x.Tn);
+        x.nb = (x.Tn + x.B - 1) / x.B;
+    }
+    if (!any) return;
+    auto fail = [&](s32 i, int rc) {
+        rcs[i] = rc;
+        out_sizes[i] = 0;
+        live[i] = 0;
+    };
+    auto new_size = [&](const Frame & x, u64 c) { return std::min(x.B, x.Tn - c * x.B); };  // of new chunk c < nb
+    DeviceFrames f;
+    u8 * park = nullptr;  // the slots the cut chunks with k > 1 are decoded into, one per such chunk of a window
+    u32 bs_max = 0;
+    try {
+        if (!f.open(dev, (size_t)n, 0, 2)) throw std::runtime_error("no device");
+        DeviceGuard g(dev);
+        walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
+        WalkRound round;
+        while (round.plain(f, pos, ins, in_sizes, 0, n, (u32)WALK_RECORDS, [&](s32 i) { return live[i] != 0; }, [](s32) { return (size_t)SIZE_MAX; })) {
+            for (size_t q = 0; q < round.who.size(); q++) {
+                const s32 i = round.who[q];
+                const WalkTail & tail = round.tails[q];
+                Frame & x = fr[i];
+                const u64 bs = pos[i].block_size;
+                for (u32 r = 0; r < tail.count; r++) {
+                    const WalkChunk & c = round.rec[round.args[q].rec_base + r];
+                    const u64 p = c.out_off, o = (u64)c.orig;
+                    const bool last = c.index + 1 == pos[i].n_blocks;
+                    if (p != (u64)c.index * bs || o == 0 || o > bs || (!last && o != bs)) x.regular = false;
+                    if (!x.regular) continue;
+                    if (bs == x.B && c.index == x.ncopy && p + o <= x.keep && (u64)c.index < x.nb && o == new_size(x, c.index)) {
+                        x.ncopy++;
+                        x.need += 8 + (u64)c.size;
+                        x.copy_end = c.in_off + 8 + (u64)c.size;
+                    } else if (x.keep > 0 && p <= x.keep - 1 && x.keep - 1 < p + o) {
+                        x.cut = c;
+                        x.has_cut = true;
+                    }
+                }
+                pos[i].take(tail);
+                if (tail.err != BZ3_OK) fail(i, tail.err);
+            }
+        }
+        size_t parked = 0;  // the cut chunks with k > 1 of the call: one per frame at most, and a window holds no more of them than it has slots
+        for (s32 i = 0; i < n; i++) {
+            if (!live[i]) continue;
+            Frame & x = fr[i];
+            const u64 T = pos[i].planned;
+            if (!x.regular || (u64)pos[i].block_size != effective_block_size(block_sizes[i], T) || (pos[i].n_blocks == 0) != (T == 0)) {
+                fail(i, BZ3_ERR_INIT);
+                continue;
+            }
+            if (x.keep > T) {
+                fail(i, BZ3_ERR_DATA_TOO_BIG);
+                continue;
+            }
+            if (x.B > (u64)MiB511 || (x.Tn >= x.B && x.Tn % x.B == 0)) {  // bz3_new's limit; the block src/libbz3.c:914 would drop
+                fail(i, BZ3_ERR_INIT);
+                continue;
+            }
+            for (u64 c = x.ncopy; c < x.nb; c++) x.need += 8 + (u64)bz3_bound((size_t)new_size(x, c));
+            if (x.cap < x.need) {
+                fail(i, BZ3_ERR_DATA_TOO_BIG);
+                continue;
+            }
+            for (u64 c = x.ncopy; c < x.nb; c++) {
+                const u64 start = c * x.B, size = new_size(x, c), a = start < x.keep ? std::min(x.keep, start + size) - start : 0;
+                if (a && (!x.has_cut || x.cut.out_off != start || c != x.ncopy || a > (u64)x.cut.orig)) throw std::logic_error("kept bytes without their chunk");
+                if (a && (elem_sizes ? elem_sizes[i] : 1) > 1) parked++;
+                list.push_back({i, start, size, a});
+                x.chunks++;
+                bs_max = std::max(bs_max, (u32)x.B);
+                if (a) bs_max = std::max(bs_max, pos[i].block_size);
+            }
+        }
+        if (bs_max && !f.init(bs_max, std::min(list.size(), FRAME_WINDOW_MAX))) throw std::runtime_error("no states");
+        if (parked) {
+            HIP_CHECK(hipSetDevice(dev));
+            HIP_CHECK(hipMalloc((void **)&park, std::min(parked, f.states.size()) * f.stride));
+        }
+    } catch (...) {
+        if (park) (void)hipFree(park);
+        for (s32 i = 0; i < n; i++)
+            if (live[i]) fail(i, BZ3_ERR_INIT);
+        return;
+    }
+    try {
+        DeviceGuard g(dev);
+        const size_t total = list.size(), W = std::max<size_t>(f.states.size(), 1);
+        const bool one_window = total <= W;
+        std::vector<bz3_state *> sts;
+        std::vector<void *> slots, where(W, nullptr);  // where[k]: the decoded cut chunk of the window's chunk k
+        std::vector<s32> sizes, orig, which;
+        std::vector<size_t> caps;
+        std::vector<u8> hdrs, hdr;
+        // Decodes the cut chunks of the frames of jobs[j] = (index into list, state, destination): one copy launch and one run_decode.  A chunk that
+        // fails ends its frame.
+        struct Job {
+            size_t t, k;
+            u8 * to;
+        };
+        auto decode = [&](const std::vector<Job> & jobs) {
+            if (jobs.empty()) return;
+            sts.clear(), slots.clear(), sizes.clear(), orig.clear(), caps.clear(), hdrs.clear();
+            for (const Job & j : jobs) {
+                const s32 i = list[j.t].frame;
+                const WalkChunk & c = fr[i].cut;
+                f.states[j.k]->block_size = (s32)pos[i].block_size;  // every check of the block is made against its own frame's block size
+                f.states[j.k]->last_error = BZ3_OK;
+                sts.push_back(f.states[j.k]);
+                slots.push_back(j.to);
+                sizes.push_back(c.size);
+                orig.push_back(c.orig);
+                caps.push_back(bz3_bound(pos[i].block_size));
+                hdrs.insert(hdrs.end(), c.hdr, c.hdr + 17);
+                f.gather.plain({(u64)(ins[i] + c.in_off + 8), (u64)j.to, (u64)c.size});
+                if (f.gather.size() == f.lay.segs) f.copy();
+            }
+            f.copy();
+            run_decode(sts.data(), slots.data(), caps.data(), sizes.data(), orig.data(), hdrs.data(), (s32)jobs.size(), false);
+            for (size_t j = 0; j < jobs.size(); j++)
+                if (live[list[jobs[j].t].frame] && bz3_last_error(sts[j]) != BZ3_OK) fail(list[jobs[j].t].frame, sts[j]->last_error);
+        };
+        // The jobs of the window [w0, w0 + cnt): a chunk with k > 1 is decoded into the next parking slot, one with k = 1 into its own slot.
+        std::vector<Job> jobs;
+        auto window_jobs = [&](size_t w0, size_t cnt) {
+            jobs.clear();
+            size_t p = 0;
+            for (size_t k = 0; k < cnt; k++) {
+                const Rebuilt & c = list[w0 + k];
+                where[k] = nullptr;
+                if (!c.a || !live[c.frame]) continue;
+                where[k] = (elem_sizes ? elem_sizes[c.frame] : 1) > 1 ? park + (p++) * f.stride : f.slot(k);
+                jobs.push_back({w0 + k, k, (u8 *)where[k]});
+            }
+        };
+        if (one_window) {
+            window_jobs(0, total);
+            decode(jobs);
+        } else {  // every cut chunk of the call, before any write to an `out`: into the slots, to be checked alone
+            jobs.clear();
+            for (size_t t = 0; t < total; t++) {
+                if (list[t].a) jobs.push_back({t, jobs.size(), f.slot(jobs.size())});
+                if (jobs.size() == W || t + 1 == total) {
+                    decode(jobs);
+                    jobs.clear();
+                }
+            }
+        }
+        auto flush = [&]() {  // the pack launch (a part of it, where its table is full)
+            f.stage_headers(hdr);
+            f.copy();
+            hdr.clear();
+        };
+        // The frame's 13 header bytes and its copied chunks, once, before its first rebuilt chunk (or alone).
+        auto start = [&](s32 i) {
+            Frame & x = fr[i];
+            if (x.started) return;
+            if (f.gather.size() + 4 > f.lay.segs || hdr.size() + 21 > f.lay.tab - f.lay.hdr) flush();
+            const size_t h = hdr.size();
+            hdr.insert(hdr.end(), {'B', 'Z', '3', 'v', '1'});
+            hdr.resize(h + 13);
+            wr_le32(hdr.data() + h + 5, (u32)x.B);
+            wr_le32(hdr.data() + h + 9, (u32)x.nb);
+            f.gather.plain({(u64)(f.meta + f.lay.hdr + h), (u64)outs[i], 13});
+            if (x.copy_end > 13) f.gather.plain({(u64)(ins[i] + 13), (u64)(outs[i] + 13), x.copy_end - 13});
+            x.pos = (size_t)x.copy_end;
+            x.started = true;
+        };
+        for (s32 i = 0; i < n; i++)  // a frame without a rebuilt chunk is its header and one run
+            if (live[i] && fr[i].chunks == 0) {
+                start(i);
+                out_sizes[i] = fr[i].pos;
+            }
+        for (size_t w0 = 0; w0 < total; w0 += W) {
+            const size_t cnt = std::min(W, total - w0);
+            if (!f.gather.v.empty()) flush();  // (the runs collected so far: the launches below are of other kinds)
+            if (!one_window) {
+                window_jobs(w0, cnt);
+                decode(jobs);
+            }
+            // patch: the kept head from where it was decoded, the new bytes from `data`, split
+            sts.clear(), slots.clear(), sizes.clear(), which.clear();
+            for (size_t k = 0; k < cnt; k++) {
+                const Rebuilt & c = list[w0 + k];
+                const s32 i = c.frame;
+                if (!live[i]) continue;
+                const Frame & x = fr[i];
+                const u64 es = elem_sizes ? (u64)elem_sizes[i] : 1, from = c.start + c.a - x.keep;  // the chunk's first new byte in data and base
+                if (c.a) f.gather.replane((u64)where[k], (u64)f.slot(k), (u64)x.cut.orig, c.size, es, c.a);
+                f.gather.patch((u64)(datas[i] + from), bases && bases[i] ? (u64)(bases[i] + from) : 0, (u64)f.slot(k), c.size, es, c.a, c.size);
+                f.states[k]->block_size = (s32)x.B;
+                f.states[k]->last_error = BZ3_OK;
+                sts.push_back(f.states[k]);
+                slots.push_back(f.slot(k));
+                sizes.push_back((s32)c.size);
+                which.push_back((s32)k);
+            }
+            if (sts.empty()) continue;
+            f.copy();
+            run_encode(sts.data(), slots.data(), sizes.data(), (s32)sts.size(), false);
+            // pack
+            for (size_t j = 0; j < which.size(); j++) {
+                const Rebuilt & c = list[w0 + (size_t)which[j]];
+                const s32 i = c.frame;
+                Frame & x = fr[i];
+                if (!live[i]) continue;  // an earlier block of its frame failed in this window
+                const s32 osz = sizes[j];
+                if (bz3_last_error(sts[j]) != BZ3_OK || osz < 0 || (size_t)osz > bz3_bound((size_t)c.size)) {
+                    fail(i, bz3_last_error(sts[j]) != BZ3_OK ? sts[j]->last_error : BZ3_ERR_DATA_TOO_BIG);
+                    continue;
+                }
+                start(i);
+                if (f.gather.size() + 2 > f.lay.segs || hdr.size() + 8 > f.lay.tab - f.lay.hdr) flush();
+                const size_t h = hdr.size();
+                hdr.resize(h + 8);
+                wr_le32(hdr.data() + h, (u32)osz);
+                wr_le32(hdr.data() + h + 4, (u32)c.size);
+                f.gather.plain({(u64)(f.meta + f.lay.hdr + h), (u64)(outs[i] + x.pos), 8});
+                f.gather.plain({(u64)slots[j], (u64)(outs[i] + x.pos + 8), (u64)osz});
+                x.pos += (size_t)osz + 8;
+                if (++x.packed == x.chunks) out_sizes[i] = x.pos;
+            }
+            flush();
+        }
+        if (!f.gather.v.empty()) flush();
+    } catch (const HipError & e) {
+        fprintf(stderr, "bzip3_amd: HIP failure '%s' at %s:%d\n", e.what, e.file, e.line);
+        for (s32 i = 0; i < n; i++)
+            if (live[i] && (fr[i].packed < fr[i].chunks || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+    } catch (...) {
+        for (s32 i = 0; i < n; i++)
+            if (live[i] && (fr[i].packed < fr[i].chunks || !out_sizes[i])) fail(i, BZ3_ERR_BWT);
+    }
+    if (park) {
+        (void)hipStreamSynchronize(f.s);
+        (void)hipFree(park);
+    }
+}
+
 // ---- the entry points' argument checks ------------------------------------------------------------------------------------
 // The GPU of a call: every non-empty buffer (a[i] with a_sizes[i] > 0, likewise b) must be device memory of the GPU the first
 // one lives on.  -1: no buffer is non-empty; -2: one is not.
@@ -1512,6 +1822,39 @@ BZIP3_API int bz3_hip_update_device_range(uint32_t elem_size, const void * in, s
     return bz3_hip_update_device_range_many(1, &elem_size, ins, &in_size, &offset, datas, &w, bases, outs, out_size, &rc);
 }
 
+// Resize (bz3_hip.h).  The whole-call checks of the update calls, the overlaps of a frame's out[0, cap) with its input, its data and its base, then
+// resize_frames.
+BZIP3_API int bz3_hip_resize_device_many(int32_t n, const uint32_t block_sizes[], const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                         const uint64_t keeps[], const void * const datas[], const size_t ws[], const void * const bases[], void * const outs[],
+                                         size_t out_sizes[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    if (n < 0 || !block_sizes || !ins || !in_sizes || !keeps || !datas || !ws || !outs || !out_sizes || !rcs || (elem_sizes && !elem_sizes_ok(n, elem_sizes)))
+        return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    const int dev = frames_device(n, ins, in_sizes, (const void * const *)outs, out_sizes);
+    if (dev < 0) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (dev == -1: every frame is empty and has no room: nothing to walk, nowhere to write)
+    for (s32 i = 0; i < n; i++) {
+        const void * base = bases ? bases[i] : nullptr;
+        if (ws[i] && (device_of(datas[i]) != dev || (base && device_of(base) != dev))) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+        if (ranges_overlap(outs[i], out_sizes[i], ins[i], in_sizes[i]) || ranges_overlap(outs[i], out_sizes[i], datas[i], ws[i]) ||
+            (base && ranges_overlap(outs[i], out_sizes[i], base, ws[i])))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    resize_frames(dev, n, block_sizes, elem_sizes, (const u8 * const *)ins, in_sizes, keeps, (const u8 * const *)datas, ws, (const u8 * const *)bases, (u8 * const *)outs,
+                  out_sizes, rcs);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_resize_device(uint32_t block_size, uint32_t elem_size, const void * in, size_t in_size, uint64_t keep, const void * data, size_t w,
+                                    const void * base, void * out, size_t * out_size) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * datas[1] = {data};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    int rc = BZ3_OK;
+    return bz3_hip_resize_device_many(1, &block_size, &elem_size, ins, &in_size, &keep, datas, &w, bases, outs, out_size, &rc);
+}
+
 BZIP3_API int bz3_hip_decompress_device_planes_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], void * const outs[],
                                                     size_t out_sizes[], int rcs[]) {
     return bz3_hip_decompress_device_delta_many(n, elem_sizes, ins, in_sizes, nullptr, nullptr, outs, out_sizes, rcs);
@@ -1632,6 +1975,22 @@ BZIP3_API int32_t bz3_hip_debug_range(const void * src, const void * base, void 
 BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
     return debug_clips(src, base, dst, segs, n, 0, [&](GatherList & g, const uint64_t * q) {
         g.patch((u64)src + q[0], debug_base(base, q[1]), (u64)dst + q[2], q[3], q[4], q[5], q[6]);
+    });
+}
+
+// n sextuples (src_off, dst_off, len_old, len_new, elem_size, a): the slot of len_old bytes at src_off holds a chunk in split form, whose bytes
+// [0, a) go to where the slot of len_new bytes at dst_off keeps them, one launch through the segments a resize call's patch makes of them.
+BZIP3_API int32_t bz3_hip_debug_replane(const void * src, void * dst, const uint64_t * segs, int32_t n) {
+    if (n < 0 || (n > 0 && !segs)) return BZ3_ERR_INIT;
+    for (s32 i = 0; i < n; i++) {
+        const uint64_t * q = segs + (size_t)6 * i;
+        if (!planes_elem_size_ok(q[4]) || q[5] > q[2] || q[5] > q[3]) return BZ3_ERR_INIT;
+    }
+    return debug_launch(src, nullptr, false, dst, (size_t)n, SEG_CLIP, 0, [&](GatherList & g, u8 *, hipStream_t) {
+        for (s32 i = 0; i < n; i++) {
+            const uint64_t * q = segs + (size_t)6 * i;
+            g.replane((u64)src + q[0], (u64)dst + q[1], q[2], q[3], q[4], q[5]);
+        }
     });
 }
 

@@ -131,6 +131,17 @@
 // lanes' shares are the old chunk's, so there is no granule a second phase could own without reading them back.  The rule is therefore: the 16
 // bytes a lane has for one plane are ONE 16-byte store where they are an aligned granule, and 16 byte stores otherwise; never a read-modify-write.
 // No scratch; the kernel's LDS is that of the clipped and whole splits beside it.
+//
+// Replane (CopySeg::mode & PLANES_REPLANE; bz3_hip_resize_device, api_frames.hip).  A resize keeps the first a bytes of a decoded chunk of o bytes in
+// a chunk of o' bytes, a <= min(o, o').  The decoded chunk sits in its slot as split_k over m = o / k, the chunk to be coded needs them as split_k
+// over m' = o' / k.  With pos(c; L) = (c % k) (L / k) + c / k below (L / k) k and pos(c; L) = c in the tail, the segment stores
+//     dst[pos(c; o')] = src[pos(c; o)]   for c < a,
+// and NO OTHER BYTE OF dst: the bytes from a on come from the clipped split of the same launch, which writes none below a.  Out of place, from
+// the slot the chunk was decoded into to the slot it is coded from: in place plane q would shift by q (m' - m) across workgroups.  The bulk is k
+// runs of a / k bytes, plane q of src to plane q of dst, at unrelated alignments: each goes through copy_tile (aligned granule loads,
+// v_alignbyte_b32, 16-byte stores, byte stores at the partial granules of a run's two ends), a tile index naming (plane, tile within plane).  What
+// is left is the partial element at a, fewer than k bytes, which may lie in the tail of either layout: single threads move them.  k = 1 is a
+// plain copy, and nothing at all where the two slots coincide (GatherList::replane, api_frames.hip).  No LDS of its own, no scratch.
 #pragma once
 #include <type_traits>
 
@@ -148,6 +159,7 @@ constexpr u64 PLANES_STRIDED = 0x400;                       // a merge of which 
 constexpr u32 STRIDED_PARAMS = 5;                           // u64 per segment in its side table: c0, first, run, stride, nbytes
 constexpr u64 PLANES_SELECT = 0x800;                        // a merge of which the bytes of a piece list per period are stored (k_select_segments alone); without PLANES_INVERSE a split that replaces only them (k_patch_select_segments)
 constexpr u32 SELECT_PARAMS = 7;                            // u64 per segment in its side table: rel, stride, q0, r0, nbytes, the piece table's address, m
+constexpr u64 PLANES_REPLANE = 0x1000;                      // a slot-to-slot move of a chunk's first a bytes from the planes of its old length to those of its new one (k_replane_segments alone); its row of the clip table holds len_old and a
 
 __host__ __device__ inline bool planes_elem_size_ok(u64 k) { return k == 1 || k == 2 || k == 4 || k == 8; }
 // Workgroups of a split / merge segment: one per PLANES_TILE_ELEMS elements; a block shorter than an element still has its tail.
@@ -842,9 +854,44 @@ __device__ __forceinline__ void select_split_tile(const u8 * src, const u8 * bas
     }
 }
 
-// One workgroup of an update's patch launch: a select split (SELECT alone compiles it), a clipped split, whose [a, b) are clips[2 i],
-// clips[2 i + 1], or a segment that is moved whole.
-template <bool SELECT>
+// ---- replane ---------------------------------------------------------------------------------------------------------------------------
+// Where split_k keeps byte c of a chunk of len bytes: pos(c; len) of the head of this file, "Replane".
+__host__ __device__ inline u64 plane_pos(u64 c, u64 len, u64 k) {
+    const u64 m = len / k;
+    return c < m * k ? (c % k) * m + c / k : c;
+}
+// Workgroups of a replane segment that keeps the chunk bytes [0, a): k plane runs of a / k bytes, each with the tiles a run of that length takes
+// at the worst destination alignment (a run touches at most (n + 30) / 16 granules), so that a tile index names its plane by one division; a
+// segment with nothing but stray bytes still has the tile that moves them.
+__host__ __device__ inline u64 replane_plane_tiles(u64 a, u64 k) { return a / k ? (((a / k + 30) >> 4) + COPY_TILE_GRANULES - 1) / COPY_TILE_GRANULES : 0; }
+__host__ __device__ inline u64 replane_tiles(u64 a, u64 k) {
+    const u64 t = k * replane_plane_tiles(a, k);
+    return a ? (t ? t : 1) : 0;
+}
+
+// Tile `tile` of a replane from the slot at `src`, which holds split_k of a chunk of len_old bytes, to the slot at `dst`, which is to hold split_k of
+// a chunk of len_new bytes with the same first a bytes, a <= min(len_old, len_new), k = 2, 4 or 8: plane q's first a / k bytes are one run from
+// src + q (len_old / k) to dst + q (len_new / k), moved by copy_tile, tile / per naming the plane and tile % per the tile within it; the bytes
+// of the partial element at a (fewer than k; they may lie in either chunk's tail) are moved one by one by the first threads of tile 0.  No
+// other byte of dst is written, and no granule is loaded that holds no byte of a run.
+__device__ __forceinline__ void replane_tile(const u8 * src, u8 * dst, u64 len_old, u64 len_new, u64 a, u32 k, u32 tile) {
+    const u32 sh = k == 2 ? 1 : k == 4 ? 2 : 3;
+    const u64 n = a >> sh;
+    const u32 per = (u32)replane_plane_tiles(a, k);
+    if (per) {
+        const u32 q = tile / per;
+        const CopySeg run = {(u64)src + q * (len_old >> sh), (u64)dst + q * (len_new >> sh), n, 0, 0};
+        if (q < k && (u64)(tile - q * per) < copy_tiles(run.dst, n)) copy_segment_tile(run, tile - q * per);
+    }
+    if (tile == 0 && threadIdx.x < a - (n << sh)) {
+        const u64 c = (n << sh) + threadIdx.x;
+        dst[plane_pos(c, len_new, k)] = src[plane_pos(c, len_old, k)];
+    }
+}
+
+// One workgroup of an update's patch launch: a select split (SELECT alone compiles it), a replane (REPLANE alone compiles it), whose len_old and a
+// are clips[2 i], clips[2 i + 1], a clipped split, whose [a, b) are clips[2 i], clips[2 i + 1], or a segment that is moved whole.
+template <bool SELECT, bool REPLANE = false>
 __device__ __forceinline__ void patch_segments_tile(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg, const u64 * __restrict__ clips,
                                                     const u64 * __restrict__ selects, u8 * lds) {
     const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
@@ -853,6 +900,7 @@ __device__ __forceinline__ void patch_segments_tile(const CopySeg * __restrict__
     const u8 * src = (const u8 *)sg.src;
     const u8 * base = (const u8 *)sg.base;
     u8 * dst = (u8 *)sg.dst;
+    if (REPLANE && (sg.mode & PLANES_REPLANE)) return replane_tile(src, dst, clips[2 * lo], sg.len, clips[2 * lo + 1], (u32)(sg.mode & 0xff), tile);
     if (SELECT && (sg.mode & PLANES_SELECT)) {
         const u64 * sp = selects + (u64)SELECT_PARAMS * lo;
         return with_elem_size_and_base(sg, [&](auto K, auto D) { select_split_tile<K(), D()>(src, base, dst, (u32)sg.len, sp, tile); });
@@ -879,6 +927,15 @@ __global__ void __launch_bounds__(COPY_THREADS) k_patch_select_segments(const Co
                                                                         const u64 * __restrict__ clips, const u64 * __restrict__ selects) {
     __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
     patch_segments_tile<true>(segs, tile_start, nseg, clips, selects, (u8 *)lds);
+}
+
+// The same for a patch launch that holds a replane segment (bz3_hip_resize_device, api_frames.hip), whose len_old and a are clips[2 i],
+// clips[2 i + 1]: the kept head of a decoded chunk moves to the byte planes of its new length while the clipped split beside it lays the new
+// bytes behind it.  A kernel of its own, so that a patch launch without one keeps k_patch_segments.
+__global__ void __launch_bounds__(COPY_THREADS) k_replane_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg,
+                                                                   const u64 * __restrict__ clips) {
+    __shared__ uint4 lds[PLANES_LDS_BYTES / 16];
+    patch_segments_tile<false, true>(segs, tile_start, nseg, clips, nullptr, (u8 *)lds);
 }
 
 }  // namespace bz3

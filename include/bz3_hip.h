@@ -376,7 +376,8 @@ BZIP3_API int32_t bz3_hip_debug_select(const void * src, const void * base, void
  *   a cut chunk that fails to decode, the call returns that code with *out_size = 0 and `out` untouched.  On an encode error afterwards (not
  *   expected) *out_size = 0 and out[0, cap) is unspecified.  `in`, `data` and `base` are never written; nothing outside out[0, cap) is ever
  *   written (cap: *out_size on entry).
- *   Range.  offset + w must not overflow and must be <= T, else BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor.  w == 0
+ *   Range.  offset + w must not overflow and must be <= T, else BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor
+ *   (bz3_hip_resize_device below appends and truncates).  w == 0
  *   gives a verbatim copy of the frame (its chunks, without anything that follows the last one in `in`); the headers are still checked.
  *   Capacity.  need = 13 + sum over j of (8 + (touched_j ? bz3_bound(o_j) : c_j)), known after the walk; cap < need is BZ3_ERR_DATA_TOO_BIG
  *   before any write.
@@ -399,6 +400,46 @@ BZIP3_API int bz3_hip_update_device_range_many(int32_t n, const uint32_t elem_si
  * is written.  One launch takes mixed elem_size.  Returns 0, or BZ3_ERR_INIT. */
 BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n);
 
+/* Resize: append to or truncate what a frame decodes to, coding again only its tail.  f, k, X, p_j, o_j, c_j and T are as in the range-update
+ * contract above.  X' = X[0, keep) ++ data[0, w) -- with a base the appended bytes are (data[i] - base[i]) mod 256; `base` holds the base's bytes OF
+ * THE APPENDED RANGE, as in the range update, NULL means none -- and T' = keep + w.  keep == T is an append, w == 0 a truncation, both together the
+ * verbatim copy.
+ *   Effective block size (src/libbz3.c:877-878): eff(bs, t) = max(65 KiB, bs > t ? bz3_bound(t) : bs).  B = eff(block_size, T').
+ *   Regular input.  f must be what bz3_compress(block_size, .) writes for T bytes: the header's block size equals eff(block_size, T), every chunk but
+ *   the last has o_j equal to it, the last has 0 < o_j <= it, and n_blocks == 0 iff T == 0.  Anything else is BZ3_ERR_INIT before any write; in
+ *   particular a frame that lost a block to the reference's in_size % block_size == 0 quirk (:914) is refused.
+ *   Lossless output.  If T' >= B and T' % B == 0 the reference would drop a block: the call returns BZ3_ERR_INIT before any write and never writes a
+ *   frame that loses bytes.  B > 511 MiB is BZ3_ERR_INIT, as in the compress call.
+ *   Result.  On BZ3_OK, out[0, *out_size) is exactly bz3_compress(block_size, S_k(X')): 13 header bytes with B and ceil(T' / B), then the chunks of
+ *   X' cut at multiples of B.  New chunk i is COPIED if the header block size of f equals B and old chunk i has the same extent and ends at or
+ *   below keep: its 8 + c_i bytes are copied verbatim, its payload is never decoded, and corruption in it is not noticed.  Every other new chunk is
+ *   REBUILT.  At most one rebuilt chunk per frame holds kept bytes, the one that holds X'[keep - 1]; only for it is an old chunk decoded, the single
+ *   old chunk that holds those bytes, whole and once, with the CRC and per-block checks of the full decode.  The other rebuilt chunks are built
+ *   from `data` alone.  A changed effective block size (a one-block frame of T < block_size that grows, a frame cut back below block_size) leaves
+ *   nothing to copy: that is the rule above at work, not a path of its own.
+ *   Order of work, failure and overlap follow the range update's.  All headers are walked and checked first; then the cut chunks of the whole call
+ *   are decoded; only then is anything written to any `out`.  A frame that fails in either step has its code, *out_size = 0 and an untouched `out`.
+ *   keep > T is BZ3_ERR_DATA_TOO_BIG.  need = 13 + sum over the new chunks of (8 + (copied ? c_i : bz3_bound(o'_i))), and cap < need (cap: *out_size
+ *   on entry) is BZ3_ERR_DATA_TOO_BIG before any write.  out[0, cap) must not overlap in[0, in_size), data[0, w) or base[0, w), else BZ3_ERR_INIT.
+ *   Nothing outside out[0, cap) is written; `in`, `data` and `base` are never written.
+ * _many: the whole-call checks, rcs[], the independence of frames and the headroom rule are those of bz3_hip_update_device_range_many; block_sizes
+ * and keeps are required, elem_sizes, bases and bases[i] may be NULL (1, none).  The rebuilt chunks of all frames share windows in frame order and
+ * the states are sized from that list: 256 frames that each append into their last chunk are at most one CM decode launch and one CM encode launch.
+ * A call whose rebuilt chunks exceed one window decodes its cut chunks twice, as the range update does.  The kept head of a cut chunk moves from the
+ * byte planes of its old length to those of its new one on the device (planes.hpp, "Replane"), from the slot it was decoded into to the slot it is
+ * coded from: one more slot per cut chunk with k > 1.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_resize_device(uint32_t block_size, uint32_t elem_size, const void * in, size_t in_size, uint64_t keep, const void * data, size_t w,
+                                    const void * base, void * out, size_t * out_size);
+BZIP3_API int bz3_hip_resize_device_many(int32_t n, const uint32_t block_sizes[], const uint32_t elem_sizes[], const void * const ins[],
+                                         const size_t in_sizes[], const uint64_t keeps[], const void * const datas[], const size_t ws[],
+                                         const void * const bases[], void * const outs[], size_t out_sizes[], int rcs[]);
+/* Test hook: one launch of the replane of a resize call: n (src_off, dst_off, len_old, len_new, elem_size, a) sextuples (host array of 6 n u64)
+ * relative to `src` / `dst`.  The len_old bytes at src_off are a slot that holds split_k of a chunk; the chunk's bytes [0, a), a <= min(len_old,
+ * len_new), are stored where a slot of len_new bytes at dst_off keeps them: chunk byte c lives at slot[(c % k) * (len / k) + c / k] below
+ * (len / k) * k and at slot[c] in the tail.  No other byte of `dst`, and nothing of `src`, is written.  One launch takes mixed elem_size.  Returns 0,
+ * or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_replane(const void * src, void * dst, const uint64_t * segs, int32_t n);
+
 /* Index update: the write mirror of index decode.  Chosen rows, columns or experts of what a frame decodes to are replaced in one call, and of the
  * frame only the chunks that hold them are coded again.  phi, L, W = count * L, P_j, `pieces` (a HOST array of 2 m u64) and the piece index j are
  * exactly those of the index-decode contract above; X, p_j, o_j, c_j and T those of the range-update contract.  A strided update (a slice along an
@@ -415,7 +456,8 @@ BZIP3_API int32_t bz3_hip_debug_patch(const void * src, const void * base, void 
  *   Validity (a violation is BZ3_ERR_INIT for the whole call before any write).  Every validity rule of bz3_hip_decompress_device_select[_many]
  *   applies to offset, stride, count, m and pieces.  w != W is invalid: an update names all its bytes.  The bad-elem_size, pointer and device checks
  *   are those of the range update.  out[0, cap) must not overlap in[0, in_size), data[0, W) or base[0, W) (cap: *out_size on entry).
- *   Range and capacity.  If W > 0 and phi(W - 1) + 1 > T, the call returns BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor.
+ *   Range and capacity.  If W > 0 and phi(W - 1) + 1 > T, the call returns BZ3_ERR_DATA_TOO_BIG before any write: an update never grows a tensor
+ *   (bz3_hip_resize_device does).
  *   W == 0 (m == 0, L == 0 or count == 0; nothing else of such a request is looked at) gives the verbatim copy of the frame, with the headers
  *   still checked.  need = 13 + sum over j of (8 + (touched_j ? bz3_bound(o_j) : c_j)), and cap < need is BZ3_ERR_DATA_TOO_BIG before any write: the
  *   range update's formula, unchanged.
