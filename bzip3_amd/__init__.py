@@ -252,7 +252,7 @@ class StageApi:
         return rc, C.string_at(out, len(data))
 
     def bwt_many(self, blocks):
-        """blocks: bytes objects, through the batched forward BWT in runs of at most four in the order given.  (rc, [(index, bytes), ...])."""
+        """blocks: bytes objects, through the batched forward BWT in runs of at most eight in the order given.  (rc, [(index, bytes), ...])."""
         k = len(blocks)
         ins = [_cbuf(d, len(d)) for d in blocks]
         outs = [(C.c_uint8 * max(1, len(d)))() for d in blocks]

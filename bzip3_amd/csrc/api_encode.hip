@@ -295,13 +295,16 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
     // The suffix sorter takes the blocks of a window in runs (bwt_forward_batch): the workspaces of a run's other blocks come on top of `need`,
     // only for block sizes at which bwt_batch_size grants a run at all, and only beside the ring: where memory is short enough for them to cost
     // an LZP context or the headroom, they are not taken, and bwt_batch_size finds room for one block at a time.
-    size_t bwt_extra = 0;
+    // Two candidates: the run the rule grants with memory to spare, and the run of BWT_BATCH_SHORT (four) where the longer one does not fit.
+    size_t bwt_extra = 0, bwt_extra_short = 0;
     if (n > 1) {
-        const u32 sz[BWT_MAX_BATCH] = {(u32)n_max, (u32)n_max, (u32)n_max, (u32)n_max};
+        u32 sz[BWT_MAX_BATCH];
+        for (u32 & x : sz) x = (u32)n_max;
         const u32 b = bwt_batch_size(sz, (u32)(n < (s32)BWT_MAX_BATCH ? n : (s32)BWT_MAX_BATCH), ~(size_t)0);
         bwt_extra = (size_t)(b - 1) * bwt_workspace_bytes(n_max + 64);
+        bwt_extra_short = (size_t)((b < BWT_BATCH_SHORT ? b : BWT_BATCH_SHORT) - 1) * bwt_workspace_bytes(n_max + 64);
     }
-    size_t contexts = ((size_t)32 << 30) / ctx_bytes, contexts_beside_runs = contexts;
+    size_t contexts = ((size_t)32 << 30) / ctx_bytes, contexts_beside_runs = contexts, contexts_beside_short_runs = contexts;
     {
         // Swap buffers the previous call left idle in the pool (a decode call's tail ring holds up to 4 x 16 of them, 17 GB at 256 MiB)
         // are memory this call's ring of LZP contexts cannot use: round 4's full-size run had a ring of 4 x 4 contexts and an encode
@@ -316,12 +319,13 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             contexts = ring_contexts_for(free_b, lead->ctx->ws_cap, need, fixed, ctx_bytes, lead->cap, lead->lean, headroom);
             contexts_beside_runs = ring_contexts_for(free_b, lead->ctx->ws_cap, need + bwt_extra, fixed, ctx_bytes, lead->cap, lead->lean, headroom);
+            contexts_beside_short_runs = ring_contexts_for(free_b, lead->ctx->ws_cap, need + bwt_extra_short, fixed, ctx_bytes, lead->cap, lead->lean, headroom);
         }
     }
     s32 window = 1, ns = 2;
     pipeline_shape((s32)(contexts < 1024 ? contexts : 1024), n, window, ns);
     // granted only where the ring as shaped above still fits beside them: then ring, runs and headroom all lie inside what ring_contexts_for counted
-    if (contexts_beside_runs < (size_t)ns * (size_t)window) bwt_extra = 0;
+    if (contexts_beside_runs < (size_t)ns * (size_t)window) bwt_extra = contexts_beside_short_runs < (size_t)ns * (size_t)window ? 0 : bwt_extra_short;
     lead->ctx->ensure_aux();
     hipStream_t s = lead->stream;
     DrainOnUnwind drain{s, lead->ctx->aux, DeviceCtx::AUX};
@@ -341,7 +345,8 @@ void encode_group(bz3_state ** sts, u8 ** bufs, const s32 * sizes, s32 n) {
         } catch (const HipError &) {  // out of memory, or whatever else the runtime answers to a size it does not like
             if (ns == 2 && window == 1 && bwt_extra == 0) throw;
             (void)hipGetLastError();
-            if (bwt_extra) bwt_extra = 0;  // the sorter's runs go first (bwt_batch_size then finds room for one block at a time): never an LZP context
+            if (bwt_extra > bwt_extra_short) bwt_extra = bwt_extra_short;  // the sorter's long runs go first, then its runs altogether
+            else if (bwt_extra) bwt_extra = 0;  // the sorter's runs go first (bwt_batch_size then finds room for one block at a time): never an LZP context
             else if (ns > 2) ns = 2;
             else window = (window + 1) / 2;
         }

@@ -1,4 +1,4 @@
-// bwt.hip -- forward Burrows-Wheeler transform on gfx950: one block, or up to BWT_MAX_BATCH blocks through one launch sequence (bwt_forward_batch).
+// bwt.hip -- forward Burrows-Wheeler transform on gfx950: one block, or up to BWT_MAX_BATCH (8) blocks through one launch sequence (bwt_forward_batch).
 // Replaces libsais_bwt (reference include/libsais.h:4095-4121, SA-IS: :3941-3983, :3740-3939), which is a sequential
 // induced-sorting algorithm whose inner scans carry a dependency through 256 bucket cursors.  This is NOT a port of it.
 //
@@ -59,11 +59,12 @@ constexpr u32 V_MASK = 0x3FFFFFFFu;  // suffix number (n < 2^30: bz3_bound(511 M
 // the fields under the names, types and qualifiers they had as kernel parameters.  Jobs never wait for each other.
 #define BWT_FIELD(T, name) T name;
 #define BWT_LOCAL(T, name) T const name = job_.name;
-#define BWT_JOB(NAME, ARGS) \
-    struct NAME {           \
-        u32 grid_;          \
-        ARGS(BWT_FIELD)     \
-    }
+#define BWT_JOB(NAME, ARGS)  \
+    struct NAME {            \
+        u32 grid_;           \
+        ARGS(BWT_FIELD)      \
+    };                       \
+    static_assert(sizeof(NAME) * BWT_MAX_BATCH <= KERNEL_TABLE_BYTES, "job table too large for a by-value kernel argument")
 #define BWT_ENTER(NAME, ARGS)                    \
     const NAME & job_ = jobs_.job[blockIdx.y];     \
     if (blockIdx.x >= job_.grid_) return;        \

@@ -47,6 +47,12 @@ inline void launch(void (*k)(KArgs...), dim3 grid, dim3 block, size_t shmem, hip
 #endif
 }
 
+// Job tables travel by value as kernel arguments (bwt.hip JobTab, sort.hip ScanBatch / RsBatch8 / RsBatchKV).  The kernel-argument segment holds
+// 4096 bytes, of which the hidden arguments take 256; a table may fill half of what is left, so that a table and the few scalars beside it never
+// come near the limit.  Every table type asserts it where it is defined.
+constexpr size_t KERNEL_ARG_BYTES = 4096, KERNEL_HIDDEN_ARG_BYTES = 256;
+constexpr size_t KERNEL_TABLE_BYTES = (KERNEL_ARG_BYTES - KERNEL_HIDDEN_ARG_BYTES) / 2;
+
 struct HipError {
     hipError_t code;
     const char * what;

@@ -193,6 +193,7 @@ struct ScanBatch {
         u64 n;        // >= 1
     } job[SORT_MAX_BATCH];
 };
+static_assert(sizeof(ScanBatch) <= KERNEL_TABLE_BYTES, "job table too large for a by-value kernel argument");
 __global__ void __launch_bounds__(SC_BLOCK) k_scan_reduce_many(ScanBatch b) {
     const ScanBatch::Job & j = b.job[blockIdx.y];
     if ((u64)blockIdx.x * SC_TILE >= j.n) return;
@@ -342,6 +343,7 @@ struct RsBatch8 {
         u32 tiles, iota_split;
     } job[SORT_MAX_BATCH];
 };
+static_assert(sizeof(RsBatch8) <= KERNEL_TABLE_BYTES, "job table too large for a by-value kernel argument");
 __global__ void __launch_bounds__(RS_BLOCK) k_rs_hist_many(RsBatch8 b, int shift, u32 xcd) {
     const RsBatch8::Job & j = b.job[blockIdx.y];
     if (blockIdx.x >= rs_grid(j.tiles, xcd != 0u)) return;
@@ -379,6 +381,7 @@ struct RsBatchKV {
         int shift;
     } job[SORT_MAX_BATCH];
 };
+static_assert(sizeof(RsBatchKV<u32>) <= KERNEL_TABLE_BYTES && sizeof(RsBatchKV<u64>) <= KERNEL_TABLE_BYTES, "job table too large for a by-value kernel argument");
 template <typename K>
 __global__ void __launch_bounds__(RS_BLOCK) k_rs_hist_kv_many(RsBatchKV<K> b, u32 xcd) {
     const typename RsBatchKV<K>::Job & j = b.job[blockIdx.y];

@@ -46,7 +46,7 @@ void exclusive_scan_u32(u32 * d_data, u64 n, u32 * d_total, Arena & tmp, hipStre
 
 // Batched forms (the inverse BWT of several blocks at once): up to SORT_MAX_BATCH independent jobs in one launch per step, the same kernel
 // bodies on a grid of (extent of the largest job, job).  The job table is a kernel argument: nothing of it has to outlive the call.
-constexpr u32 SORT_MAX_BATCH = 4;
+constexpr u32 SORT_MAX_BATCH = 8;  // (the forward suffix sorter's runs, stages.hpp BWT_MAX_BATCH; the inverse BWT sends up to UB_MAX_BATCH = 4)
 // The scan of `count` tables of n[k] >= 1 values each; d_totals (may be null, as may any entry) receives the grand totals.
 void exclusive_scan_u32_many(u32 * const * d_data, const u64 * n, u32 * const * d_totals, u32 count, Arena & tmp, hipStream_t s);
 // radix_pass<u8> with generated values and no keys out, shift 0, of `count` arrays: vout[out_base + stable rank of keys[i]] = i + (i >= iota_split).

@@ -105,7 +105,7 @@ void bwt_set_big_rounds(int k);  // tests only: more windows for the big groups 
 // never enter a batch), one read-back per pass for all of them, all scratch from `tmp`, job after job.  Every launch is built from the jobs that
 // need it (they diverge: done, one more window, rank doubling).  Output, primary index, d_outside and the statistics of a block are what the block
 // gets alone -- bwt_forward is a batch of one.  The call waits for the stream at the end only if a job has no d_idx; `idx` then holds its index.
-constexpr u32 BWT_MAX_BATCH = 4;
+constexpr u32 BWT_MAX_BATCH = 8;  // (a front-end window; every job table stays a by-value kernel argument: hipx.hpp KERNEL_TABLE_BYTES)
 struct BwtBatchItem {
     const u8 * in;
     u32 n;
@@ -117,9 +117,13 @@ struct BwtBatchItem {
 };
 void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t s);
 // How many of the first `count` blocks (sizes n[k]) one run takes, given the bytes the arena has free: 1 to BWT_MAX_BATCH.  Blocks above
-// BWT_BATCH_MAX_N bytes go alone: 64 MiB is the largest size at which a run has been measured (it still gains a quarter there, profiles/bwt_batch.txt),
+// BWT_BATCH_MAX_N bytes go alone: 64 MiB is the largest size at which a run has been measured (four gain a quarter there, profiles/bwt_batch.txt),
 // and the metric's 256 MiB blocks keep the launch sequence and the workspace of a block alone.
 constexpr u32 BWT_BATCH_MAX_N = 64u << 20;
+// Eight beat four with disjoint ranges at 2, 8, 32 and 64 MiB (profiles/front_small.txt), so no size is capped at a shorter run.  Where the seven extra
+// workspaces of a run of eight do not fit beside the ring, the encoder asks for those of a run of BWT_BATCH_SHORT before it gives the runs up.
+constexpr u32 BWT_BATCH_SHORT = 4;
+static_assert(BWT_MAX_BATCH <= SORT_MAX_BATCH && BWT_BATCH_SHORT <= BWT_MAX_BATCH, "the sorter's runs go through sort.hip's batched passes");
 u32 bwt_batch_size(const u32 * n, u32 count, size_t arena_free);
 void bwt_set_batch(int b);  // tests / sweeps: 1..BWT_MAX_BATCH forces the run length where memory allows, -1 = the rule
 

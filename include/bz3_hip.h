@@ -542,10 +542,10 @@ BZIP3_API int32_t bz3_hip_debug_sort_u32(const uint32_t * keys, uint32_t n, int 
  * libsais_unbwt refuses.  bz3_hip_stage_last_ms() then covers all runs of the call. */
 BZIP3_API int32_t bz3_hip_debug_unbwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, const int32_t * idx, int32_t count);
 /* Tests and sweeps only: the forward BWT of `count` blocks on host buffers in one call, through the batched sorter of the encoder's front end in
- * runs of at most four blocks, in the order given (blocks of fewer than 2 bytes are handled apart).  Synchronous.  idx_out[k] receives block k's
+ * runs of at most eight blocks, in the order given (blocks of fewer than 2 bytes are handled apart).  Synchronous.  idx_out[k] receives block k's
  * primary index.  0, or -1 on bad arguments.  bz3_hip_stage_last_ms() then covers all runs of the call. */
 BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count);
-/* Tests and sweeps only: blocks per run of the batched forward BWT (1..4 where memory allows); -1 = the rule (bwt_batch_size). */
+/* Tests and sweeps only: blocks per run of the batched forward BWT (1..8 where memory allows); -1 = the rule (bwt_batch_size). */
 BZIP3_API void bz3_hip_debug_set_bwt_batch(int b);
 BZIP3_API float bz3_hip_stage_last_ms(void); /* wall ms of the transform inside the last bz3_hip_stage_bwt / _unbwt call (allocations and PCIe copies excluded) */
 BZIP3_API int32_t bz3_hip_stage_cm_encode(const uint8_t * in, int32_t n, uint8_t * out);            /* encode_bytes    */

@@ -1,9 +1,10 @@
 """The encoder's front end at the benchmark's shape, with the forward BWT's run length forced and left to the rule (api_encode.hip encode_group
 sends the blocks of a window through bwt_forward_batch in runs of bwt_batch_size's choosing; bz3_hip_debug_set_bwt_batch forces the length).
 One batch of `blocks` text blocks of `MiB` each is encoded in device memory `trials` times under every setting given (-1 = the rule), the
-settings alternating.  Prints t_enc, the CM launch and what is left (the front end and the finish) per trial.  Device memory as in
+settings alternating.  --duo=0,1 alternates the two-thread front end the same way (bz3_hip_set_front_end_duo; -1 = the library's default), inside
+every run-length setting.  Prints t_enc, the CM launch and what is left (the front end and the finish) per trial.  Device memory as in
 tools/tail_pipe_probe.py.  A build without the hook (--lib=<older build>) takes the setting "none" only.
-    python tools/front_pipe_probe.py [MiB=8] [blocks=768] [--batch=1,-1] [--trials=3] [--lib=<another build>] [--emu]"""
+    python tools/front_pipe_probe.py [MiB=8] [blocks=768] [--batch=1,-1] [--duo=-1] [--trials=3] [--lib=<another build>] [--emu]"""
 import ctypes as C
 import json
 import os
@@ -42,6 +43,7 @@ def main():
         mem = HipMem()
     hook = hasattr(lib, "bz3_hip_debug_set_bwt_batch")
     settings = [int(x) for x in opt.get("batch", "1,-1").split(",")] if hook else [None]
+    duos = [int(x) for x in opt["duo"].split(",")] if "duo" in opt else [None]
     lib.bz3_hip_bind_device(0)
     lib.bz3_hip_set_lean_states(1)
     bs = int(mib * (1 << 20))
@@ -54,13 +56,15 @@ def main():
     tm = (C.c_float * 8)()
     first = None
 
-    def encode(setting):
+    def encode(setting, duo=None):
         nonlocal first
         for k in range(nblk):
             mem.h2d(bufs[k], np.roll(base, k * 4099))
         mem.sync()
         if setting is not None:
             lib.bz3_hip_debug_set_bwt_batch(setting)
+        if duo is not None:
+            lib.bz3_hip_set_front_end_duo(duo)
         sizes = (C.c_int32 * nblk)(*[bs] * nblk)
         t0 = time.perf_counter()
         lib.bz3_hip_encode_blocks_device(states, ptrs, sizes, nblk)
@@ -71,13 +75,17 @@ def main():
         assert list(sizes) == first, "coded sizes differ between settings"
         lib.bz3_hip_last_timings(states[0], tm)
         cm = tm[bzip3_amd.T_NAMES.index("cm")] * 1e-3
-        return {"batch": "none" if setting is None else setting, "t_enc_s": round(t, 3), "cm_s": round(cm, 3), "front_s": round(t - cm, 3),
+        ring = lib.bz3_hip_debug_front_end_ring()
+        return {"batch": "none" if setting is None else setting, "duo": "lib" if duo is None else duo, "two_threads": (ring >> 29) & 1, "t_enc_s": round(t, 3), "cm_s": round(cm, 3), "front_s": round(t - cm, 3),
                 "bwt_ms_block0": round(tm[bzip3_amd.T_NAMES.index("bwt")], 3)}
 
-    encode(settings[0])  # warm-up: allocations
+    encode(settings[0], duos[-1])  # warm-up: allocations (the two-thread form's arena is the larger one)
     for _ in range(trials):
         for s in settings:
-            print(json.dumps(encode(s)), flush=True)
+            for d in duos:
+                print(json.dumps(encode(s, d)), flush=True)
+    if duos != [None]:
+        lib.bz3_hip_set_front_end_duo(-1)
     if hook:
         lib.bz3_hip_debug_set_bwt_batch(-1)
 
