@@ -116,6 +116,10 @@ def _declare(L, strict=True):
         "bz3_hip_resize_device_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_uint64), C.POINTER(vp), C.POINTER(sz),
                                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(C.c_int)]),
         "bz3_hip_debug_replane": (i32, [vp, vp, C.POINTER(C.c_uint64), i32]),
+        "bz3_hip_sync_device": (C.c_int, [u32, vp, sz, vp, vp, sz, vp, vp, C.POINTER(sz), C.POINTER(u32)]),
+        "bz3_hip_sync_device_many": (C.c_int, [i32, C.POINTER(u32), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp),
+                                               C.POINTER(vp), C.POINTER(sz), C.POINTER(u32), C.POINTER(C.c_int)]),
+        "bz3_hip_debug_diff": (i32, [vp, vp, C.POINTER(C.c_uint64), i32, C.POINTER(u32)]),
         "bz3_hip_last_timings": (None, [vp, C.POINTER(C.c_float)]),
         "bz3_hip_last_bwt_stats": (None, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint64)]),
         "bz3_hip_stage_crc32c": (u32, [vp, sz, u32]),
@@ -1362,6 +1366,158 @@ def append_state_dict_rows(packed, rows, base=None, lib=None):
             _row_bytes(packed[k], f"tensor {k!r}")
         out.update(zip(names, _resize_rows_many([packed[k] for k in names], [(packed[k].shape[0], rows[k]) for k in names],
                                                 [None if base is None else base.get(k) for k in names], lib)))
+    return out
+
+
+def sync_tensors(frames, datas, olds, planes=1, bases=None, block_sizes=None, lib=None, counts=False):
+    """New frames of datas[i] made from frames[i], which decode to olds[i], for many frames in ONE call (bz3_hip_sync_device_many) and one
+    synchronisation, when nobody knows where the tensors changed: datas[i] is compared with olds[i] on the device, chunk by chunk and byte for
+    byte, only the chunks that differ are coded again, from datas[i] alone, and every other chunk is copied as it is.  Nothing is decoded
+    ("Sync").  Result i is byte for byte the frame compress_tensor gives for datas[i], provided olds[i] is what frames[i] decodes to:
+    the caller vouches for that.  frames, datas and olds: contiguous uint8 tensors on one GPU, datas[i] and olds[i] of one size, which must be the
+    size frames[i] decodes to (Bz3Error with BZ3_ERR_DATA_TOO_BIG otherwise; resize_tensors changes a size).  `planes` as in decompress_tensors.
+    `bases[i]`: None, or for a frame made against a base THE WHOLE base, of datas[i]'s size.  `block_sizes`: the block sizes the frames were made
+    with where the caller knows them (PackedTensor.block_size); without them the 13 header bytes of all frames are read from the device once,
+    which is a second synchronisation.  They only size the outputs, which are views of one allocation with room for every chunk coded again,
+    13 + chunks * (8 + bz3_bound(block size)) bytes each (.clone() one to drop the rest).  The inputs are never written.  Returns the list of
+    frames, and with counts=True also the list of the numbers of chunks that were coded again.  Raises Bz3Error with .index / .codes / .outs as
+    compress_tensors does; a frame that fails has no output.  [] returns []."""
+    import torch
+
+    frames = [_device_u8(f, f"frames[{i}]") for i, f in enumerate(frames)]
+    n = len(frames)
+    datas = [_device_u8(d, f"datas[{i}]") for i, d in enumerate(datas)]
+    olds = [_device_u8(o, f"olds[{i}]") for i, o in enumerate(olds)]
+    if len(datas) != n or len(olds) != n:
+        raise ValueError(f"sync_tensors: {n} frames, {len(datas)} data tensors and {len(olds)} old tensors")
+    for i, (d, o) in enumerate(zip(datas, olds)):
+        if d.numel() != o.numel():
+            raise ValueError(f"sync_tensors: datas[{i}] holds {d.numel()} bytes, olds[{i}] {o.numel()}")
+    if not frames:
+        return ([], []) if counts else []
+    ks = _planes_arg(planes, n)
+    bases = [_base_u8(b, d, f"bases[{i}]") for i, (b, d) in enumerate(zip(_bases_arg(bases, n), datas))]
+    dev = _same_device(frames + datas + olds, "sync_tensors")
+    L = lib or load()
+    if block_sizes is None:
+        heads = torch.stack([torch.nn.functional.pad(f[:13], (0, 13 - min(13, f.numel()))) for f in frames]).cpu().numpy()
+        bss = [int.from_bytes(bytes(h[5:9]), "little") for h in heads]
+        # (a header that lies: a chunk takes 8 bytes of its frame at least, and the call refuses the frame or finds the output too small)
+        chunks = [min(int.from_bytes(bytes(h[9:13]), "little"), max(f.numel() - 13, 0) // 8) for h, f in zip(heads, frames)]
+    else:
+        if len(block_sizes) != n:
+            raise ValueError(f"sync_tensors: {n} frames and {len(block_sizes)} block sizes")
+        bss = [_effective_block_size(int(b), d.numel()) for b, d in zip(block_sizes, datas)]
+        chunks = [-(-d.numel() // bs) for d, bs in zip(datas, bss)]
+    bss = [min(max(b, _KiB65), _MiB511) for b in bss]
+    caps = [13 + c * (8 + L.bz3_bound(bs)) for c, bs in zip(chunks, bss)]
+    outs = _carve(sum(caps), caps, dev)
+    out_sizes = (C.c_size_t * n)(*caps)
+    recoded = (C.c_uint32 * n)()
+    rcs = (C.c_int * n)()
+    torch.cuda.synchronize(dev)
+    rc = L.bz3_hip_sync_device_many(n, (C.c_uint32 * n)(*ks), _ptrs(frames), (C.c_size_t * n)(*[f.numel() for f in frames]),
+                                    (C.c_void_p * n)(*[d.data_ptr() if d.numel() else None for d in datas]),
+                                    (C.c_void_p * n)(*[o.data_ptr() if o.numel() else None for o in olds]), (C.c_size_t * n)(*[d.numel() for d in datas]),
+                                    _ptrs_or_null(bases), _ptrs(outs), out_sizes, recoded, rcs)
+    res = [o[: out_sizes[i]] for i, o in enumerate(outs)]
+    if rc != BZ3_OK:
+        codes = list(rcs)
+        idx = next(i for i, c in enumerate(codes) if c != BZ3_OK)
+        raise Bz3Error(codes[idx], "bz3_hip_sync_device_many", index=idx, codes=codes, outs=res)
+    return (res, list(recoded)) if counts else res
+
+
+def sync_tensor_bytes(frame, data, old, planes=1, base=None, block_size=None, lib=None, counts=False):
+    """The frame of `data` made from `frame`, which decodes to `old` (bz3_hip_sync_device): sync_tensors for one frame.  With counts=True the
+    pair (frame, chunks coded again)."""
+    try:
+        got = sync_tensors([frame], [data], [old], planes=planes, bases=None if base is None else [base], lib=lib,
+                           block_sizes=None if block_size is None else [block_size], counts=counts)
+    except Bz3Error as e:
+        raise Bz3Error(e.code, "bz3_hip_sync_device") from None
+    return (got[0][0], got[1][0]) if counts else got[0]
+
+
+def _sync_many(ps, xs, prevs, bases, check_prev, lib, labels):
+    """The PackedTensors of xs[i] made from ps[i], which hold prevs[i]: every argument is checked before any GPU work, then ONE batched checksum
+    call over every prev that is checked, every base whose checksum is known and every new tensor, then one bz3_hip_sync_device_many call per
+    distinct block size.  Returns (the PackedTensors, per tensor (chunks coded again, chunks))."""
+    import torch
+
+    raws, praws, braws = [], [], []
+    for p, x, prev, b, label in zip(ps, xs, prevs, bases, labels):
+        if not isinstance(p, PackedTensor):
+            raise TypeError("sync: a PackedTensor is expected")
+        for t, what in ((x, "the new tensor"), (prev, "the previous tensor")):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != p.dtype or tuple(t.shape) != tuple(p.shape):
+                raise TypeError(f"sync: {what} of {label} must be a {p.dtype} GPU tensor of shape {tuple(p.shape)}")
+            if t.device != p.frame.device:
+                raise ValueError(f"sync: {what} of {label} is on {t.device}, the frame on {p.frame.device}")
+        if p.delta and b is None:
+            raise ValueError(f"sync: {label} was packed against a base, which is needed to code its changed chunks")
+        if not p.delta:
+            b = None  # (a base beside a tensor that was packed without one is not used)
+        raws.append(_as_bytes(x, f"the new tensor of {label}"))
+        praws.append(_as_bytes(prev, f"the previous tensor of {label}"))
+        braws.append(_base_bytes(b, p.nbytes, p.frame.device, f"the base of {label}"))
+    n = len(ps)
+    if not n:
+        return [], []
+    L = lib or load()
+    # one batched call: the previous tensors that are checked, the bases whose checksum is known, and the new tensors
+    sums = _crcs_where([r if check_prev and p.crc is not None else None for p, r in zip(ps, praws)] +
+                       [b if b is not None and p.base_crc is not None else None for p, b in zip(ps, braws)] + raws, L)
+    for p, got, gotb, label in zip(ps, sums[:n], sums[n : 2 * n], labels):
+        if got is not None and got != p.crc:
+            raise ValueError(f"sync: the previous tensor of {label} is not the tensor this frame was packed from (its checksum differs)")
+        if gotb is not None and gotb != p.base_crc:
+            raise ValueError(f"sync: the base of {label} is not the tensor this frame was packed against (its checksum differs)")
+    frames, recoded = [None] * n, [0] * n
+    for bs in sorted({p.block_size for p in ps}):
+        idx = [i for i in range(n) if ps[i].block_size == bs]
+        got, cnt = sync_tensors([ps[i].frame for i in idx], [raws[i] for i in idx], [praws[i] for i in idx], planes=[ps[i].planes for i in idx],
+                                bases=[braws[i] for i in idx], block_sizes=[bs] * len(idx), lib=L, counts=True)
+        for i, f, c in zip(idx, got, cnt):
+            frames[i], recoded[i] = f, c
+    chunks = [-(-p.nbytes // _effective_block_size(p.block_size, p.nbytes)) for p in ps]
+    out = [PackedTensor(f, p.dtype, p.shape, p.planes, p.block_size, p.nbytes, p.delta, p.base_crc, c) for f, p, c in zip(frames, ps, sums[2 * n :])]
+    return out, list(zip(recoded, chunks))
+
+
+def sync_tensor(p, x, prev, base=None, check_prev=True, lib=None):
+    """A new PackedTensor of `x` made from p, which holds `prev`, when nobody knows where the tensor changed -- a fine-tune with frozen layers, an
+    MoE step that reached a few experts, a sparse embedding step --: x is compared with prev on the GPU, chunk by chunk and byte for byte, only
+    the chunks that differ are coded again and every other chunk of p.frame is copied undecoded (bz3_hip_sync_device; nothing is decoded).  Its
+    frame is byte for byte the one pack_tensor gives for x at p.block_size and p.planes.  `x` and `prev`: GPU tensors of p's dtype and shape on
+    the frame's GPU (TypeError otherwise).  `base`: as in pack_tensor, the WHOLE base, needed where p was packed against one (ValueError without
+    it, or where its checksum is not p.base_crc).  `check_prev`: where p.crc is known, the checksum of prev's bytes must equal it (ValueError),
+    which is checked before any coding work and in the same batched call (crc32c_tensors) as the checksum of x, the result's `crc`; with
+    check_prev=False, or p.crc None, the caller vouches that prev is what p holds (another prev gives a frame that mixes old and new chunks, and
+    no error).  planes, block_size, dtype, shape, nbytes, delta and base_crc are carried over.  `p` is unchanged."""
+    return _sync_many([p], [x], [prev], [base], check_prev, lib, ["the tensor"])[0][0]
+
+
+def sync_state_dict(packed, sd, prev, base=None, check_prev=True, lib=None, stats=None):
+    """sync_tensor for the tensors of a dict: `sd` is {name: new tensor}, `prev` {name: the tensor packed[name] holds} (it may hold more names),
+    and the result a new dict in which the names of sd have new PackedTensors and every other name the PackedTensor of `packed` itself.  One
+    bz3_hip_sync_device_many call per distinct block size over the names of sd, whose changed chunks share its windows of up to 256 blocks: a
+    checkpoint of which 1 % changed codes 1 % of its chunks, in one window where pack_state_dict takes chunks / 256.  `base`: {name: base} for
+    the tensors that were packed against one.  A name of sd that is not in `packed`, or that `prev` lacks: ValueError.  `stats`: a dict that
+    gets {name: (chunks coded again, chunks)}.  Everything is checked before any GPU work; `packed` is unchanged."""
+    for k in sd:
+        if k not in packed:
+            raise ValueError(f"sync_state_dict: {k!r} is not in the packed dict")
+        if k not in prev:
+            raise ValueError(f"sync_state_dict: the previous tensor of {k!r} is missing")
+    names = list(sd)
+    out = dict(packed)
+    if names:
+        got, counts = _sync_many([packed[k] for k in names], [sd[k] for k in names], [prev[k] for k in names],
+                                 [None if base is None else base.get(k) for k in names], check_prev, lib, [repr(k) for k in names])
+        out.update(zip(names, got))
+        if isinstance(stats, dict):
+            stats.update(zip(names, counts))
     return out
 
 

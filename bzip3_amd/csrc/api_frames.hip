@@ -2,7 +2,8 @@
 // range, strided, select), its debug entry points and the batched CRC.  The only unit that includes frame.hpp and planes.hpp: their kernels are
 // ordinary definitions.  The partial decode calls share one request form (Request), one list of gather segments with their side tables
 // (GatherList) and one body (decompress_frames); what differs between them is how an entry point reads its parameters.  The two update calls
-// share the same request form and front (request_front) and one body (update_frames).
+// share the same request form and front (request_front) and one body (update_frames), of which the sync call is a mode: its touched chunks are
+// the ones a device comparison of the new tensor with the old one finds changed (diff_segments, planes.hpp k_diff_segments).
 #include <functional>
 
 #include "api_internal.hpp"
@@ -248,6 +249,31 @@ void copy_segments(const GatherList & g, std::vector<u8> & staging, u8 * d_tab, 
     else launch(delta ? k_delta_segments : planes ? k_move_segments : k_copy_segments, grid, block, 0, s, d_segs, d_starts, (u32)n);
 }
 
+// Compares the diff segments of v (planes.hpp: src and base the two runs, mode the index of the segment's flag) in one launch of k_diff_segments on
+// stream s and reads the flags back: flags[j], j < nflags, is 1 where a segment with mode == j differs and 0 otherwise.  d_tab holds
+// table_bytes(v.size(), SEG_DELTA) bytes, d_flags nflags u32.  Complete on return; nothing is launched for a list without a byte.
+void diff_segments(const std::vector<CopySeg> & v, std::vector<u8> & staging, u8 * d_tab, u32 * d_flags, u32 * flags, size_t nflags, hipStream_t s) {
+    const size_t n = v.size(), seg_bytes = align16(n * sizeof(CopySeg));
+    staging.assign(table_bytes(n, SEG_DELTA), 0);
+    u32 * starts = (u32 *)(staging.data() + seg_bytes);
+    u64 tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (v[i].mode >= nflags) throw std::logic_error("diff flag out of range");
+        memcpy(staging.data() + i * sizeof(CopySeg), &v[i], sizeof(CopySeg));
+        starts[i] = (u32)tiles;
+        tiles += copy_tiles(v[i].src, v[i].len);
+        if (tiles >= ((u64)1 << 24)) throw std::length_error("segment diff larger than 256 GiB");
+    }
+    std::fill(flags, flags + nflags, 0u);
+    if (!tiles) return;
+    starts[n] = (u32)tiles;
+    HIP_CHECK(hipMemcpyAsync(d_tab, staging.data(), staging.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_flags, 0, nflags * sizeof(u32), s));
+    launch(k_diff_segments, dim3((u32)tiles), dim3(COPY_THREADS), 0, s, (const CopySeg *)d_tab, (const u32 *)(d_tab + seg_bytes), (u32)n, d_flags);
+    HIP_CHECK(hipMemcpyAsync(flags, d_flags, nflags * sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+}
+
 constexpr size_t FRAME_WINDOW_MAX = 256;  // blocks per window: one CU per block during the CM stage (the host frame path's rule)
 constexpr size_t WALK_RECORDS = 4096;     // chunk records of one walk (bz3_hip_frame_decoded_sizes_device; a window's walk takes at most FRAME_WINDOW_MAX)
 static_assert(WALK_RECORDS >= FRAME_WINDOW_MAX, "a window's walk must fit the records");
@@ -259,17 +285,20 @@ constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // header; with room for their clips and periods), the walk's arguments, records and tails.  A call that walks with piece tables
 // (piece_bytes > 0 of them, uploaded once per call) has them behind the tails and room for the piece-list parameters in its copy tables;
 // every other call has the layout and the size it had.  An update (update_frames) packs up to two runs of verbatim bytes per frame beside the two
-// segments of every block, the frame header travelling in the first run: `runs` = 2 segments per frame instead of 1.
+// segments of every block, the frame header travelling in the first run: `runs` = 2 segments per frame instead of 1.  A sync (update_frames with
+// `olds`) has behind all that the diff table of a walk round, one segment per record, and the round's flags: `diff_segs` = WALK_RECORDS.
 struct MetaLayout {
-    size_t n = 0, segs = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, pieces = 0, bytes = 0;
+    size_t n = 0, segs = 0, hdr = 0, tab = 0, args = 0, rec = 0, tails = 0, pieces = 0, diff = 0, flags = 0, bytes = 0;
     MetaLayout() = default;
-    explicit MetaLayout(size_t frames, size_t piece_bytes = 0, size_t runs = 1) : n(frames), segs(2 * FRAME_WINDOW_MAX + runs * frames) {
+    explicit MetaLayout(size_t frames, size_t piece_bytes = 0, size_t runs = 1, size_t diff_segs = 0) : n(frames), segs(2 * FRAME_WINDOW_MAX + runs * frames) {
         tab = align256(13 * n + 8 * FRAME_WINDOW_MAX);
         args = tab + align256(table_bytes(segs, piece_bytes ? SEG_SELECT : SEG_STRIDED));
         rec = args + align256(n * sizeof(WalkArg));
         tails = rec + align256(WALK_RECORDS * sizeof(WalkChunk));
         pieces = tails + align256(n * sizeof(WalkTail));
-        bytes = pieces + align256(piece_bytes);
+        diff = pieces + align256(piece_bytes);
+        flags = diff + (diff_segs ? align256(table_bytes(diff_segs, SEG_DELTA)) : 0);
+        bytes = flags + align256(diff_segs * sizeof(u32));
     }
 };
 
@@ -302,10 +331,10 @@ struct DeviceFrames {
         if (meta) (void)hipFree(meta);
         if (own_stream && s) (void)hipStreamDestroy(s);
     }
-    bool open(int dev, size_t n, size_t piece_bytes = 0, size_t runs = 1) {  // the device, a stream and the small buffer
+    bool open(int dev, size_t n, size_t piece_bytes = 0, size_t runs = 1, size_t diff_segs = 0) {  // the device, a stream and the small buffer
         if (dev < 0 || dev >= device_count() || !get_ctx(dev)) return false;
         device = dev;
-        lay = MetaLayout(n, piece_bytes, runs);
+        lay = MetaLayout(n, piece_bytes, runs, diff_segs);
         HIP_CHECK(hipSetDevice(dev));
         HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         own_stream = true;
@@ -967,8 +996,15 @@ void decoded_sizes_frames(int dev, s32 n, const u8 * const * ins, const size_t *
 // a clipped split where its new bytes are one run of the chunk, and a select split otherwise (GatherList::patch_select); the piece tables of a call
 // are uploaded once, beside the walk's arguments, as decompress_frames uploads them.  The walk stays the plain walk: the copies need every record.
 // A call whose touched chunks exceed one window still decodes its cut chunks twice; parking the decoded chunks is open.
+// Sync (olds != nullptr; bz3_hip.h, "Sync"): every request is the range (0, ws[i]), datas[i] is the whole new tensor and olds[i] what the frame
+// decodes to.  The touched chunks are then the DIRTY ones: every walk round's records become one diff table (a segment per chunk with a byte,
+// data[p_j, p_j + o_j) against old[p_j, p_j + o_j); a chunk that runs past ws[i] is left out, its frame fails with T != ws[i] below), one
+// k_diff_segments launch and one read-back of the round's flags, before the round's records are looked at.  A dirty chunk has ta = p_j and
+// tb = p_j + o_j, so it is covered: no chunk of a sync is cut, the decode lambda below is never reached, and everything from 2 on is the update's
+// own path.  recoded[i] (recoded may be nullptr) is the frame's number of dirty chunks, 0 for a frame that fails before a write.
 void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * ins, const size_t * in_sizes, const Request * reqs, const u8 * const * datas,
-                   const size_t * ws, const u8 * const * bases, u8 * const * outs, size_t * out_sizes, int * rcs) {
+                   const size_t * ws, const u8 * const * bases, u8 * const * outs, size_t * out_sizes, int * rcs, const u8 * const * olds = nullptr,
+                   u32 * recoded = nullptr) {
     struct Frame : Request {    // cut at ws[i]: w bytes, the last of them phi(w - 1) = hi - 1 (hi == UINT64_MAX: it does not fit 64 bits)
         u64 need = 13, tail = 0;  // the capacity the frame needs; the offset behind its last chunk
         size_t cap = 0, pos = 0;
@@ -989,6 +1025,7 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     bool any = false;
     for (s32 i = 0; i < n; i++) {
         rcs[i] = BZ3_OK;
+        if (recoded) recoded[i] = 0;
         fr[i].cap = out_sizes[i];
         out_sizes[i] = 0;
         static_cast<Request &>(fr[i]) = reqs[i];
@@ -1009,15 +1046,30 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
     DeviceFrames f;
     u32 bs_max = 0;
     try {
-        if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64), 2)) throw std::runtime_error("no device");
+        if (!f.open(dev, (size_t)n, tables.size() * sizeof(u64), 2, olds ? WALK_RECORDS : 0)) throw std::runtime_error("no device");
         DeviceGuard g(dev);
         const u64 d_pieces = f.upload_pieces(tables);
         for (s32 i = 0; i < n; i++)
             if (fr[i].sel) fr[i].d_tab += d_pieces;
         walk_frame_headers(f, n, ins, in_sizes, pos, live, rcs);  // :930-960
         WalkRound round;
+        std::vector<CopySeg> diffs;  // a sync's diff table of the round, and its flags, one per record
+        std::vector<u32> dirty;
         // every chunk header of every live frame
         while (round.plain(f, pos, ins, in_sizes, 0, n, (u32)WALK_RECORDS, [&](s32 i) { return live[i] != 0; }, [](s32) { return (size_t)SIZE_MAX; })) {
+            if (olds) {
+                diffs.clear();
+                dirty.resize(round.rec.size());
+                for (size_t q = 0; q < round.who.size(); q++) {
+                    const s32 i = round.who[q];
+                    for (u32 r = 0; r < round.tails[q].count && datas[i] != olds[i]; r++) {
+                        const WalkChunk & c = round.rec[round.args[q].rec_base + r];
+                        const u64 p = c.out_off, o = (u64)c.orig;
+                        if (o > 0 && p + o <= fr[i].w) diffs.push_back({(u64)(datas[i] + p), 0, o, (u64)(round.args[q].rec_base + r), (u64)(olds[i] + p)});
+                    }
+                }
+                diff_segments(diffs, f.staging, f.meta + f.lay.diff, (u32 *)(f.meta + f.lay.flags), dirty.data(), dirty.size(), f.s);
+            }
             for (size_t q = 0; q < round.who.size(); q++) {
                 const s32 i = round.who[q];
                 const WalkTail & tail = round.tails[q];
@@ -1026,7 +1078,7 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
                     const WalkChunk & c = round.rec[round.args[q].rec_base + r];
                     const u64 p = c.out_off, o = (u64)c.orig;
                     const u64 ta = o > 0 ? x.below(p) : 0, tb = o > 0 ? x.below(p + o) : 0;  // (touched iff the chunk holds phi(t) for some t < w)
-                    const bool touched = tb > ta;
+                    const bool touched = olds ? dirty[round.args[q].rec_base + r] != 0 : tb > ta;
                     x.need += 8 + (touched ? (u64)bz3_bound((size_t)o) : (u64)c.size);
                     if (!touched) continue;
                     touch.push_back({i, c, ta, tb});
@@ -1039,7 +1091,8 @@ void update_frames(int dev, s32 n, const u32 * elem_sizes, const u8 * const * in
         for (s32 i = 0; i < n; i++) {
             if (!live[i]) continue;
             fr[i].tail = pos[i].off;
-            if (fr[i].hi > pos[i].planned || fr[i].cap < fr[i].need) fail(i, BZ3_ERR_DATA_TOO_BIG);
+            if (fr[i].hi > pos[i].planned || (olds && fr[i].w != pos[i].planned) || fr[i].cap < fr[i].need) fail(i, BZ3_ERR_DATA_TOO_BIG);
+            else if (recoded) recoded[i] = fr[i].chunks;
         }
         touch.erase(std::remove_if(touch.begin(), touch.end(), [&](const Touched & t) { return !live[t.frame]; }), touch.end());
         for (const Touched & t : touch) bs_max = std::max(bs_max, pos[t.frame].block_size);
@@ -1822,6 +1875,42 @@ BZIP3_API int bz3_hip_update_device_range(uint32_t elem_size, const void * in, s
     return bz3_hip_update_device_range_many(1, &elem_size, ins, &in_size, &offset, datas, &w, bases, outs, out_size, &rc);
 }
 
+// Sync (bz3_hip.h).  The whole-call checks of the update calls, with `old` beside `data`: both are device memory of the call's GPU wherever
+// sizes[i] > 0, and a frame's out[0, cap) overlaps none of its input, its data, its old and its base.  Then update_frames in its sync mode.
+BZIP3_API int bz3_hip_sync_device_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[], const void * const datas[],
+                                       const void * const olds[], const size_t sizes[], const void * const bases[], void * const outs[], size_t out_sizes[],
+                                       uint32_t recoded[], int rcs[]) {
+    if (n == 0) return BZ3_OK;
+    for (s32 i = 0; recoded && i < n; i++) recoded[i] = 0;
+    std::vector<Request> reqs;
+    int dev = -2;
+    if (!request_front(n, elem_sizes, ins, in_sizes, datas && olds && sizes, outs, out_sizes, rcs, [](s32, Request & r) { return r = Request::range(0), true; }, reqs, dev) ||
+        dev < 0)
+        return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);  // (dev == -1: every frame is empty and has no room: nothing to walk, nowhere to write)
+    for (s32 i = 0; i < n; i++) {
+        const void * base = bases ? bases[i] : nullptr;
+        if (sizes[i] && (device_of(datas[i]) != dev || device_of(olds[i]) != dev || (base && device_of(base) != dev))) return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+        if (ranges_overlap(outs[i], out_sizes[i], ins[i], in_sizes[i]) || ranges_overlap(outs[i], out_sizes[i], datas[i], sizes[i]) ||
+            ranges_overlap(outs[i], out_sizes[i], olds[i], sizes[i]) || (base && ranges_overlap(outs[i], out_sizes[i], base, sizes[i])))
+            return fail_frames(n, rcs, out_sizes, BZ3_ERR_INIT);
+    }
+    update_frames(dev, n, elem_sizes, (const u8 * const *)ins, in_sizes, reqs.data(), (const u8 * const *)datas, sizes, (const u8 * const *)bases, (u8 * const *)outs, out_sizes,
+                  rcs, (const u8 * const *)olds, recoded);
+    return first_error(n, rcs);
+}
+
+BZIP3_API int bz3_hip_sync_device(uint32_t elem_size, const void * in, size_t in_size, const void * data, const void * old, size_t size, const void * base, void * out,
+                                  size_t * out_size, uint32_t * recoded) {
+    if (!out_size) return BZ3_ERR_INIT;
+    const void * ins[1] = {in};
+    const void * datas[1] = {data};
+    const void * olds[1] = {old};
+    const void * bases[1] = {base};
+    void * outs[1] = {out};
+    int rc = BZ3_OK;
+    return bz3_hip_sync_device_many(1, &elem_size, ins, &in_size, datas, olds, &size, bases, outs, out_size, recoded, &rc);
+}
+
 // Resize (bz3_hip.h).  The whole-call checks of the update calls, the overlaps of a frame's out[0, cap) with its input, its data and its base, then
 // resize_frames.
 BZIP3_API int bz3_hip_resize_device_many(int32_t n, const uint32_t block_sizes[], const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
@@ -1956,6 +2045,28 @@ int32_t debug_clips(const void * src, const void * base, void * dst, const uint6
 BZIP3_API int32_t bz3_hip_debug_copy_segments(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 3); }
 
 BZIP3_API int32_t bz3_hip_debug_planes(const void * src, void * dst, const uint64_t * segs, int32_t n) { return debug_move_segments(src, nullptr, dst, segs, n, 4); }
+
+// n triples (a_off, b_off, len) relative to a / b: flags[i] = 1 iff a[a_off, a_off + len) and b[b_off, b_off + len) differ, else 0, one launch of
+// k_diff_segments through the table a sync call's walk round makes (diff_segments).
+BZIP3_API int32_t bz3_hip_debug_diff(const void * a, const void * b, const uint64_t * segs, int32_t n, uint32_t * flags) {
+    if (n < 0 || (n > 0 && (!segs || !flags))) return BZ3_ERR_INIT;
+    if (n == 0) return BZ3_OK;
+    const int dev = device_of(a);
+    if (dev < 0 || device_of(b) != dev) return BZ3_ERR_INIT;
+    ScratchStream sc;
+    try {
+        DeviceGuard g(dev);
+        const size_t tab_bytes = align256(table_bytes((size_t)n, SEG_DELTA));
+        sc.open(tab_bytes + (size_t)n * sizeof(u32));
+        std::vector<CopySeg> v;
+        for (s32 i = 0; i < n; i++) v.push_back({(u64)a + segs[3 * i], 0, segs[3 * i + 2], (u64)i, (u64)b + segs[3 * i + 1]});
+        std::vector<u8> staging;
+        diff_segments(v, staging, sc.mem, (u32 *)(sc.mem + tab_bytes), flags, (size_t)n, sc.s);
+    } catch (...) {
+        return BZ3_ERR_INIT;
+    }
+    return BZ3_OK;
+}
 
 BZIP3_API int32_t bz3_hip_debug_delta(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n) {
     return debug_move_segments(src, base, dst, segs, n, 5);

@@ -514,6 +514,58 @@ __device__ __forceinline__ void delta1_tile(const u8 * src, const u8 * base, u8 
     }
 }
 
+// ---- diff segments ------------------------------------------------------------------------------------------------------------------
+// Do a[0, len) and b[0, len) differ in any byte?  A diff segment is CopySeg{src = a, dst = 0, len, mode = its flag's index, base = b}: two read
+// streams and no destination.  The tiling is delta1_tile's with `a` in the destination's place: copy_tiles(a, len) tiles of COPY_TILE_GRANULES
+// aligned granules of `a`, one per lane and round.  A granule of `a` that lies inside the run is one aligned 16-byte load, and the 16 bytes of
+// `b` that pair with it are load16_any's one or two aligned granules, which both hold bytes of b[0, len) because the 16 bytes do and, where there
+// are two, straddle their seam.  The partial granules at the run's two ends are compared byte by byte over [max(a, granule), min(a + len, granule
+// + 16)) alone, so a byte before or behind the run is never read, let alone compared: no granule is loaded that holds no byte of the run.
+// Returns the OR of the lane's XORs.
+__device__ __forceinline__ u32 diff_tile(const u8 * a, const u8 * b, u64 len, u64 g_first, u64 g_end) {
+    const u64 a0 = (u64)a, a1 = a0 + len;
+    const u64 db = (u64)b - a0;  // b's address = a's address + db (mod 2^64)
+    u32 acc = 0;
+    if (g_end - g_first == COPY_TILE_GRANULES && (g_first << 4) >= a0 && (g_end << 4) <= a1) {  // every granule of the tile is full: all loads first
+        uint4 x[COPY_GRANULES_PER_LANE], y[COPY_GRANULES_PER_LANE];
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+            const u64 p = (g_first + k * COPY_THREADS + threadIdx.x) << 4;
+            x[k] = *(const uint4 *)p;
+            y[k] = load16_any(p + db);
+        }
+#pragma unroll
+        for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) acc |= (x[k].x ^ y[k].x) | (x[k].y ^ y[k].y) | (x[k].z ^ y[k].z) | (x[k].w ^ y[k].w);
+        return acc;
+    }
+    for (u32 k = 0; k < COPY_GRANULES_PER_LANE; k++) {
+        const u64 g = g_first + k * COPY_THREADS + threadIdx.x;
+        if (g >= g_end) break;
+        const u64 p = g << 4;  // a's granule [p, p + 16)
+        if (p >= a0 && p + 16 <= a1) {
+            const uint4 x = *(const uint4 *)p, y = load16_any(p + db);
+            acc |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+        } else {
+            const u64 b0 = p > a0 ? p : a0, b1 = p + 16 < a1 ? p + 16 : a1;
+            for (u64 q = b0; q < b1; q++) acc |= (u32)(*(const u8 *)q ^ *(const u8 *)(q + db));
+        }
+    }
+    return acc;
+}
+
+// flags[segs[i].mode] becomes 1 where the two runs of diff segment i differ; the caller zeroes `flags` on the stream before the launch, and a flag
+// no workgroup stores to stays 0.  tile_start counts a segment's workgroups with copy_tiles(src, len).  No LDS and no barrier: of every wave that
+// found a difference, the lowest lane that did stores the 1 (an ordinary vector store; several waves and workgroups may store the same value).
+__global__ void __launch_bounds__(COPY_THREADS) k_diff_segments(const CopySeg * __restrict__ segs, const u32 * __restrict__ tile_start, u32 nseg, u32 * __restrict__ flags) {
+    const u32 lo = segment_of_tile(tile_start, nseg, blockIdx.x);
+    const CopySeg sg = segs[lo];
+    const u64 g_first = (sg.src >> 4) + (u64)(blockIdx.x - tile_start[lo]) * COPY_TILE_GRANULES, g_end = (sg.src + sg.len + 15) >> 4;
+    const u64 g_last = g_first + COPY_TILE_GRANULES < g_end ? g_first + COPY_TILE_GRANULES : g_end;
+    const u32 acc = diff_tile((const u8 *)sg.src, (const u8 *)sg.base, sg.len, g_first, g_last);
+    const u64 found = __ballot(acc != 0);
+    if (acc != 0 && (found & (((u64)1 << (threadIdx.x & 63)) - 1)) == 0) flags[sg.mode] = 1;
+}
+
 // ---- clipped merge ------------------------------------------------------------------------------------------------------------------
 // The tiles of a merge of `len` bytes that hold an element byte of its bytes [a, b), a < b <= len: tiles first .. first + count - 1 of
 // planes_tiles(len, k).  A clip that holds tail bytes only still takes one tile, which stores them.

@@ -496,6 +496,44 @@ BZIP3_API int bz3_hip_update_device_select_many(int32_t n, const uint32_t elem_s
 BZIP3_API int32_t bz3_hip_debug_patch_select(const void * src, const void * base, void * dst, const uint64_t * segs, int32_t n,
                                              const uint64_t * pieces, uint64_t n_pieces);
 
+/* Sync: repack a tensor against its previous version when nobody knows where it changed.  `in` is a frame f, `old` the `size` bytes f decodes
+ * to (with a base: f decodes to (old[i] - base[i]) mod 256, split with k), `data` the `size` bytes of the new version.  The call finds the chunks
+ * whose bytes changed by comparing `data` with `old` on the device and codes only those again.  f, k, X, p_j, o_j, c_j and T are those of the
+ * range-update contract above.
+ *   Dirty.  Chunk j is DIRTY iff o_j > 0 and data[p_j, p_j + o_j) != old[p_j, p_j + o_j) byte-wise (an exact comparison, not a checksum), and
+ *   CLEAN otherwise.
+ *   Result.  On BZ3_OK, out[0, *out_size) is a frame f' with f's 13 header bytes and f's number of chunks.  A clean chunk is chunk j of f, copied
+ *   verbatim (8 header bytes and c_j coded bytes): it is never decoded, and corruption in it is not noticed.  A dirty chunk is exactly the chunk
+ *   bz3_hip_compress_device_delta writes for a block with the content data[p_j, p_j + o_j) -- with a base, less base[p_j, p_j + o_j): `base` holds
+ *   `size` bytes, THE WHOLE BASE, and pairs with `data` at equal offsets; NULL means none --, split with k and coded against the frame's block size.
+ *   NO chunk is ever decoded by this call, and the old payload of a dirty chunk is not read.  Consequence: if `old` is what f decodes to and
+ *   f == bz3_compress(bs, S_k(D(old, base))), then f' == bz3_compress(bs, S_k(D(data, base))) byte for byte.  The caller vouches that `old` is what
+ *   f decodes to; the call cannot tell, as it cannot tell a wrong base.
+ *   Count.  *recoded (recoded may be NULL) is the number of dirty chunks on BZ3_OK, and 0 for a frame that fails before a write.
+ *   Order of work.  The frame header and EVERY chunk header are walked and checked first with the plain walk, as in the range update: a malformed
+ *   header anywhere is reported.  The comparison runs beside the walk; then size and capacity are judged; only then is anything written.  A frame
+ *   that fails has its code, *out_size = 0 and an untouched `out`; on an encode error afterwards (not expected) *out_size = 0 and out[0, cap) is
+ *   unspecified.  `in`, `data`, `old` and `base` are never written; nothing outside out[0, cap) is ever written (cap: *out_size on entry).
+ *   Size.  size != T is BZ3_ERR_DATA_TOO_BIG before any write (bz3_hip_resize_device is the call that changes a size).  old == NULL or
+ *   data == NULL with size > 0 is BZ3_ERR_INIT.  data == old is legal and gives the verbatim copy of the frame.
+ *   Capacity.  need = 13 + sum over j of (8 + (dirty_j ? bz3_bound(o_j) : c_j)); cap < need is BZ3_ERR_DATA_TOO_BIG before any write.
+ *   Overlap.  out[0, cap) must not overlap in[0, in_size), data[0, size), old[0, size) or base[0, size): BZ3_ERR_INIT before any write.  `data` and
+ *   `old` may overlap each other.
+ * _many: n independent syncs on ONE GPU; the whole-call checks, return value, rcs[], the independence of frames and the headroom rule are those of
+ * bz3_hip_update_device_range_many; datas, olds and sizes are required, elem_sizes, bases, bases[i] and recoded may be NULL (1, none, not wanted).
+ * The dirty chunks of all frames share windows in frame order, and the states are sized from the dirty list (min(dirty, 256)), never from
+ * n_blocks: a call without a dirty chunk creates no state and launches no CM kernel.  The comparison is one launch (planes.hpp k_diff_segments)
+ * and one read-back of the flags per walk round of 4096 chunk records.  The single call is the n = 1 case. */
+BZIP3_API int bz3_hip_sync_device(uint32_t elem_size, const void * in, size_t in_size, const void * data, const void * old, size_t size,
+                                  const void * base, void * out, size_t * out_size, uint32_t * recoded);
+BZIP3_API int bz3_hip_sync_device_many(int32_t n, const uint32_t elem_sizes[], const void * const ins[], const size_t in_sizes[],
+                                       const void * const datas[], const void * const olds[], const size_t sizes[], const void * const bases[],
+                                       void * const outs[], size_t out_sizes[], uint32_t recoded[], int rcs[]);
+/* Test hook: one launch of the comparison of a sync call: n (a_off, b_off, len) triples relative to `a` / `b` (host array of 3 n u64);
+ * flags: host array of n u32, flags[i] = 1 iff the two runs differ, else 0 (len == 0: 0).  Both sides are read as aligned 16-byte granules, and no
+ * granule is read that holds no byte of a run.  Nothing is written to `a` or `b`.  Returns 0, or BZ3_ERR_INIT. */
+BZIP3_API int32_t bz3_hip_debug_diff(const void * a, const void * b, const uint64_t * segs, int32_t n, uint32_t * flags);
+
 /* Stage timings (milliseconds) of the last block processed by `state`.  Timing a stage means waiting for the stream, so since round 4 only
  * the FIRST state of a batch (per GPU) is timed: its CRC / RLE / BWT entries are stage times, its LZP entry includes the window's driver
  * launch; for every other state of the batch CRC / BWT read 0 and RLE / LZP are launch (enqueue) times, not kernel times.  CM is the batch's
