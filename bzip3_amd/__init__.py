@@ -132,6 +132,8 @@ def _declare(L, strict=True):
         "bz3_hip_stage_unbwt": (i32, [vp, vp, i32, i32]),
         "bz3_hip_debug_unbwt_many": (i32, [vp, vp, vp, vp, i32]),
         "bz3_hip_debug_bwt_many": (i32, [vp, vp, vp, vp, i32]),
+        "bz3_hip_debug_bwt_record": (i32, [vp, i32, vp, C.POINTER(i32), vp, u32]),
+        "bz3_hip_debug_bwt_record_many": (i32, [vp, vp, vp, vp, i32, vp, u32]),
         "bz3_hip_debug_set_bwt_batch": (None, [C.c_int]),
         "bz3_hip_stage_last_ms": (C.c_float, []),
         "bz3_hip_debug_sort_u32": (i32, [vp, u32, C.c_int, C.c_int, vp, vp]),
@@ -266,6 +268,48 @@ class StageApi:
         idx = (C.c_int32 * max(1, k))()
         rc = self.lib.bz3_hip_debug_bwt_many(inp, outp, n, idx, k)
         return rc, [(int(i), C.string_at(o, len(d))) for i, o, d in zip(idx, outs, blocks)]
+
+    BWT_RECORD_CAP = 1024  # words offered per record (the library says how many it writes)
+
+    @staticmethod
+    def _bwt_record(w):
+        """The flat record of bwt.hip's bwt_record_flatten as a dict."""
+        geo = ("WR_A", "WR_G", "TL_GROUP", "TL_COUNT", "TL_CAP", "WR_CAP", "VLC_WINDOW", "VLC_MAXLEN", "SP_GROUP", "big_cap", "WW_KEY", "TL_KEY", "BW_KEY", "BG_TILE", "RT_WAVES")
+        r = {"n": w[1], "deep": w[2], "h": w[3], "stats": {"rounds": w[6], "radix_passes": w[7], "sorted_elements": w[8] | (w[9] << 32)}, "big_rounds": w[10]}
+        r["geo"] = dict(zip(geo, w[12:12 + len(geo)]))
+        max_passes, max_rounds = w[27], w[28]
+        r["vlc"] = tuple(w[32:288])
+        at = 288
+        keys = ("g", "big", "given_up", "overflow", "tail", "tail_valid", "mid")
+        r["passes"] = tuple(dict(zip(keys, w[at + 8 * k: at + 8 * k + 7])) for k in range(w[4]))
+        at += 8 * max_passes
+        r["rounds"] = tuple((w[at + 2 * k], w[at + 2 * k + 1]) for k in range(w[5]))
+        assert w[0] == at + 2 * max_rounds, "the record's layout is not the one this reader knows"
+        return r
+
+    def bwt_record(self, data):
+        """The forward BWT of one block alone and what the sorter did with it: (index, bytes, record)."""
+        out = (C.c_uint8 * max(1, len(data)))()
+        idx = C.c_int32()
+        rec = (C.c_uint32 * self.BWT_RECORD_CAP)()
+        rc = self.lib.bz3_hip_debug_bwt_record(_cbuf(data, len(data)), len(data), out, C.byref(idx), rec, self.BWT_RECORD_CAP)
+        assert rc == 0, rc
+        return idx.value, C.string_at(out, len(data)), self._bwt_record([int(x) for x in rec])
+
+    def bwt_record_many(self, blocks):
+        """bwt_many with a record per block: (rc, [(index, bytes, record), ...])."""
+        k = len(blocks)
+        ins = [_cbuf(d, len(d)) for d in blocks]
+        outs = [(C.c_uint8 * max(1, len(d)))() for d in blocks]
+        inp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in ins])
+        outp = (C.c_void_p * max(1, k))(*[C.cast(b, C.c_void_p) for b in outs])
+        n = (C.c_int32 * max(1, k))(*[len(d) for d in blocks])
+        idx = (C.c_int32 * max(1, k))()
+        cap = self.BWT_RECORD_CAP
+        rec = (C.c_uint32 * (cap * max(1, k)))()
+        rc = self.lib.bz3_hip_debug_bwt_record_many(inp, outp, n, idx, k, rec, cap)
+        flat = [int(x) for x in rec]
+        return rc, [(int(i), C.string_at(o, len(d)), self._bwt_record(flat[cap * q: cap * (q + 1)])) for q, (i, o, d) in enumerate(zip(idx, outs, blocks))]
 
     def unbwt_many(self, jobs):
         """jobs: (bytes, index) pairs, through the batched inverse BWT in runs of at most four in the order given.  (rc, [bytes, ...])."""

@@ -176,9 +176,11 @@ BZIP3_API int32_t bz3_hip_stage_bwt(const uint8_t * in, uint8_t * out, int32_t n
 // order given (blocks of fewer than 2 bytes apart) -- the forward twin of bz3_hip_debug_unbwt_many.  Synchronous.  The arena is sized for a
 // full run of the largest block; how long a run is, is bwt_batch_size's decision (bz3_hip_debug_set_bwt_batch forces it).  idx_out[k] receives
 // block k's primary index (0 for an empty block, 1 for one byte).  Returns 0, or -1 on bad arguments.
-BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count) {
+// rec (may be NULL): BWT_RECORD_WORDS words per block, what the sorter did with it (bwt_record_flatten; a block of fewer than 2 bytes: the geometry alone).
+static s32 debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count, uint32_t * rec) {
     return stage_guard([&]() -> s32 {
         if (count < 0 || (count > 0 && (!in || !out || !n || !idx_out))) return -1;
+        std::vector<BwtRecord> recs(rec ? (size_t)count : 0);
         u64 largest = 0;
         for (s32 k = 0; k < count; k++) {
             if (n[k] < 0) return -1;
@@ -193,10 +195,11 @@ BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * c
             if (n[k] == 1) out[k][0] = in[k][0];
             if (n[k] < 2) continue;
             const u8 * d = e.dev((size_t)n[k] + 64, in[k], (size_t)n[k]);
-            items.push_back(BwtBatchItem{d, (u32)n[k], e.dev((size_t)n[k] + 64), nullptr, nullptr, nullptr, 0});
+            items.push_back(BwtBatchItem{d, (u32)n[k], e.dev((size_t)n[k] + 64), nullptr, nullptr, nullptr, 0, rec ? &recs[(size_t)k] : nullptr});
             sizes.push_back((u32)n[k]);
             owner.push_back(k);
         }
+        for (s32 k = 0; rec && k < count; k++) bwt_record_flatten(recs[(size_t)k], (u32)n[k], rec + (size_t)k * BWT_RECORD_WORDS);  // (blocks that never enter a run)
         if (items.empty()) return 0;
         const size_t plain = workspace_bytes_for(largest + 64), full = (size_t)BWT_MAX_BATCH * bwt_workspace_bytes(largest + 64);
         Arena a = e.ctx->arena_for(plain > full ? plain : full);
@@ -211,9 +214,32 @@ BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * c
         for (size_t j = 0; j < items.size(); j++) {
             e.down(out[owner[j]], items[j].out, (size_t)items[j].n);
             idx_out[owner[j]] = items[j].idx;
+            if (rec) bwt_record_flatten(recs[(size_t)owner[j]], items[j].n, rec + (size_t)owner[j] * BWT_RECORD_WORDS);
         }
         return 0;
     });
+}
+BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count) {
+    return debug_bwt_many(in, out, n, idx_out, count, nullptr);
+}
+// Tests only: bz3_hip_debug_bwt_many plus a record per block of what the sorter did with it -- its code table, the counter words of every pass of the resolve
+// loop, whether and from which depth it went to rank doubling, the rounds of that, the statistics -- and the geometry constants a test needs (the layout:
+// bwt.hip bwt_record_flatten).  rec holds rec_words words per block; rec_words must be at least the record's size, which the call leaves in rec[0].
+// bz3_hip_debug_bwt_record is the same for one block alone.  -1 on bad arguments, -2 when rec_words is too small (nothing is run).
+BZIP3_API int32_t bz3_hip_debug_bwt_record_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count, uint32_t * rec, uint32_t rec_words) {
+    if (!rec) return -1;
+    if (rec_words < BWT_RECORD_WORDS) {
+        if (rec_words) rec[0] = BWT_RECORD_WORDS;
+        return -2;
+    }
+    if (rec_words == BWT_RECORD_WORDS) return debug_bwt_many(in, out, n, idx_out, count, rec);
+    std::vector<uint32_t> flat((size_t)(count > 0 ? count : 0) * BWT_RECORD_WORDS);
+    const s32 rc = debug_bwt_many(in, out, n, idx_out, count, flat.data());
+    for (s32 k = 0; rc == 0 && k < count; k++) memcpy(rec + (size_t)k * rec_words, flat.data() + (size_t)k * BWT_RECORD_WORDS, (size_t)BWT_RECORD_WORDS * 4);
+    return rc;
+}
+BZIP3_API int32_t bz3_hip_debug_bwt_record(const uint8_t * in, int32_t n, uint8_t * out, int32_t * idx_out, uint32_t * rec, uint32_t rec_words) {
+    return bz3_hip_debug_bwt_record_many(&in, &out, &n, idx_out, 1, rec, rec_words);
 }
 BZIP3_API void bz3_hip_debug_set_bwt_batch(int b) { bwt_set_batch(b); }
 

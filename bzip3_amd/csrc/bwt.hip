@@ -1330,6 +1330,7 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
         j = FwJob{};
         all.add(k);
         j.item = &items[k];
+        if (items[k].rec) *items[k].rec = BwtRecord{};
         j.in = items[k].in;
         const u32 n = j.n = items[k].n;
         j.key[0] = tmp.take<u64>(n);
@@ -1463,6 +1464,9 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
         }, [&](const TailJob & j) {
             launch(k_bwt_tail, dim3(j.grid_), dim3(WAVE), 0, s, j.t, j.n, j.v, j.pb, j.vlc, j.tail_v, j.tail_slot, j.tail_d, j.tail_pb, j.counters, j.chain);
         });
+        if (pass == 0)
+            for (u32 k = 0; k < count; k++)  // (tests: a recorder gets the block's code table with the first read-back)
+                if (items[k].rec) HIP_CHECK(hipMemcpyAsync(items[k].rec->vlc, jb[k].vlc, sizeof items[k].rec->vlc, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipMemcpyAsync(h_words, words_all, (size_t)16 * count * sizeof(u32), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
         const int max_big = bwt_switches().big_rounds.load();  // one more window takes text from ~12 % of its suffixes in big groups to ~1 %; what is left is deep and goes to rank doubling
@@ -1471,6 +1475,8 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
             FwJob & j = jb[act.idx[q]];
             const u32 * hw = h_words + 16 * (size_t)act.idx[q];
             const u32 nb = j.nb = hw[0];
+            if (BwtRecord * r = j.item->rec)
+                if (r->passes < BWT_REC_PASSES) r->pass[r->passes++] = BwtRecord::Pass{j.g, hw[0], hw[1], hw[3], hw[4], hw[5], hw[8]};
             if (trace) fprintf(stderr, "[bwt] n %u pass %d depth %u: %u suffixes in groups > %d, %u groups through the wide kernel, %u suffixes through the tail kernel, %u given up, overflow %u\n", j.n, pass, j.g, nb, TR_G, hw[8], hw[4], hw[1], hw[3]);
             if (nb == 0) {  // no group left that is too large: done, unless the resolve kernel gave some up (counted over all passes)
                 j.deep = hw[1] != 0;
@@ -1562,6 +1568,10 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
             j.m = n;
             j.h = j.g < 7u + 5u * (u32)TL_CAP ? j.g : 7u + 5u * (u32)TL_CAP;
             if (trace) fprintf(stderr, "[bwt] n %u deep path from depth %u\n", n, j.h);
+            if (BwtRecord * r = j.item->rec) {
+                r->deep = 1u;
+                r->h = j.h;
+            }
         }
         auto bg_tiles = [](u32 m) { return (u32)(((u64)m + BG_TILE - 1) / BG_TILE); };
         {
@@ -1603,6 +1613,8 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
             for (u32 q = 0; q < dbl.count; q++) {
                 FwJob & j = jb[dbl.idx[q]];
                 const u32 m_next = h_words[16 * (size_t)dbl.idx[q] + 6];
+                if (BwtRecord * r = j.item->rec)
+                    if (r->rounds < BWT_REC_ROUNDS) r->round[r->rounds++] = BwtRecord::Round{j.h, m_next};
                 if (m_next == 0) continue;
                 j.m = m_next;
                 j.st.rounds++;
@@ -1670,8 +1682,37 @@ void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t
     for (u32 k = 0; k < count; k++) {
         items[k].idx = items[k].d_idx ? 0 : (s32)h_words[16 * (size_t)k + 7];
         if (items[k].stats) *items[k].stats = jb[k].st;
+        if (items[k].rec) items[k].rec->st = jb[k].st;
     }
     tmp.release(mk);
+}
+
+// Tests only: a record as BWT_RECORD_WORDS flat words, with the geometry a test needs beside it (so that no test hard-codes a constant of this file):
+//   [0] BWT_RECORD_WORDS  [1] n  [2] went deep  [3] deep path's first depth h  [4] passes of the resolve loop  [5] doubling rounds recorded
+//   [6] BwtStats rounds  [7] radix passes  [8], [9] sorted elements (low, high word)  [10] big rounds allowed (the switch as it stands)
+//   [12] WR_A  [13] WR_G  [14] largest group of the tail list  [15] largest group the tail ranks by counting  [16] TL_CAP  [17] WR_CAP  [18] VLC_WINDOW
+//   [19] VLC_MAXLEN  [20] SP_GROUP  [21] capacity of the big list (n / 4)  [22] WW_KEY: code bits of a wide step  [23] code bits of a tail step
+//   [24] code bits of a window  [25] BG_TILE  [26] RT_WAVES  [27] BWT_REC_PASSES  [28] BWT_REC_ROUNDS
+//   [32 ..) the code table, 256 words; then 8 words per pass: g, [0], [1], [3], [4], [5], [8], 0; then 2 words per doubling round: h, m
+constexpr u32 TL_GROUP = 64, TL_COUNT = 12, TL_KEY = 40, BW_KEY = 56;  // the literals of bwt_route_body.hpp (e - h <= 64) and bwt_tail_body.hpp (maxsz <= 12u, vlc_pack<40>), vlc_pack<56>
+void bwt_record_flatten(const BwtRecord & r, u32 n, u32 * out) {
+    for (u32 k = 0; k < BWT_RECORD_WORDS; k++) out[k] = 0;
+    const u32 head[] = {BWT_RECORD_WORDS, n, r.deep, r.h, r.passes, r.rounds, (u32)r.st.rounds, (u32)r.st.radix_passes, (u32)r.st.sorted_elements, (u32)(r.st.sorted_elements >> 32),
+                        (u32)bwt_switches().big_rounds.load(), 0u, (u32)WR_A, (u32)WR_G, TL_GROUP, TL_COUNT, (u32)TL_CAP, (u32)WR_CAP, (u32)VLC_WINDOW, (u32)VLC_MAXLEN, (u32)SP_GROUP, n / 4,
+                        (u32)WW_KEY, TL_KEY, BW_KEY, (u32)BG_TILE, (u32)RT_WAVES, BWT_REC_PASSES, BWT_REC_ROUNDS};
+    static_assert(sizeof head / sizeof head[0] <= 32, "the record's head is 32 words");
+    for (u32 k = 0; k < sizeof head / sizeof head[0]; k++) out[k] = head[k];
+    u32 * w = out + 32;
+    for (u32 k = 0; k < 256; k++) *w++ = r.vlc[k];
+    for (u32 k = 0; k < BWT_REC_PASSES; k++, w += 8) {
+        const BwtRecord::Pass & p = r.pass[k];
+        const u32 v[8] = {p.g, p.big, p.given_up, p.overflow, p.tail, p.tail_valid, p.mid, 0u};
+        for (u32 q = 0; q < 8; q++) w[q] = v[q];
+    }
+    for (u32 k = 0; k < BWT_REC_ROUNDS; k++) {
+        *w++ = r.round[k].h;
+        *w++ = r.round[k].m;
+    }
 }
 
 // d_idx == nullptr: synchronous, returns the primary index.  d_idx != nullptr: the primary index is left THERE (a device word that outlives

@@ -114,7 +114,22 @@ struct BwtBatchItem {
     u32 * d_outside;  // may be nullptr
     BwtStats * stats; // may be nullptr
     s32 idx;          // out
+    struct BwtRecord * rec = nullptr;  // tests only: what the sorter did with this block (below); nullptr costs no copy, launch or wait
 };
+// Tests only (bz3_hip_debug_bwt_record): the decisions bwt_forward_batch took for one block, as the host saw them.  The code table is copied back
+// for a recorder alone; everything else is what the host reads back anyway.
+constexpr u32 BWT_REC_PASSES = 16, BWT_REC_ROUNDS = 40;
+struct BwtRecord {
+    u32 vlc[256];   // the block's code table (bwt.hip: code << 4 | length, 0 for an absent value)
+    u32 passes;     // passes of the resolve loop, and per pass: the depth g and the counter words [0] big elements, [1] given up (running total), [3] overflow,
+    struct Pass { u32 g, big, given_up, overflow, tail, tail_valid, mid; } pass[BWT_REC_PASSES];  // [4] tail entries, [5], [8] mid descriptors
+    u32 deep, h;    // the block went to rank doubling, from depth h
+    u32 rounds;     // (h, m) per doubling round: m suffixes still active at depth h; the last entry is the one that found m == 0
+    struct Round { u32 h, m; } round[BWT_REC_ROUNDS];
+    BwtStats st;
+};
+constexpr u32 BWT_RECORD_WORDS = 32 + 256 + 8 * BWT_REC_PASSES + 2 * BWT_REC_ROUNDS;
+void bwt_record_flatten(const BwtRecord & r, u32 n, u32 * out);  // BWT_RECORD_WORDS words: layout in bwt.hip, read by bzip3_amd.StageApi.bwt_record
 void bwt_forward_batch(BwtBatchItem * items, u32 count, Arena & tmp, hipStream_t s);
 // How many of the first `count` blocks (sizes n[k]) one run takes, given the bytes the arena has free: 1 to BWT_MAX_BATCH.  Blocks above
 // BWT_BATCH_MAX_N bytes go alone: 64 MiB is the largest size at which a run has been measured (four gain a quarter there, profiles/bwt_batch.txt),

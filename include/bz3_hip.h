@@ -583,6 +583,13 @@ BZIP3_API int32_t bz3_hip_debug_unbwt_many(const uint8_t * const * in, uint8_t *
  * runs of at most eight blocks, in the order given (blocks of fewer than 2 bytes are handled apart).  Synchronous.  idx_out[k] receives block k's
  * primary index.  0, or -1 on bad arguments.  bz3_hip_stage_last_ms() then covers all runs of the call. */
 BZIP3_API int32_t bz3_hip_debug_bwt_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count);
+/* Tests only: bz3_hip_stage_bwt of one block plus a record of what the suffix sorter did with it: its code table, the counter words of every pass of
+ * the resolve loop, whether and from which depth it went to rank doubling, (depth, active suffixes) per doubling round, the statistics, and the
+ * geometry constants of bwt.hip a test needs (layout: bwt.hip bwt_record_flatten; Python: bzip3_amd.StageApi.bwt_record).  rec receives rec[0] words
+ * (rec_words must be at least that many: -2 otherwise, with the size in rec[0]).  *idx_out receives the primary index.  _record_many: the same for the
+ * blocks of one bz3_hip_debug_bwt_many call, rec_words words apart.  0, -1 on bad arguments. */
+BZIP3_API int32_t bz3_hip_debug_bwt_record(const uint8_t * in, int32_t n, uint8_t * out, int32_t * idx_out, uint32_t * rec, uint32_t rec_words);
+BZIP3_API int32_t bz3_hip_debug_bwt_record_many(const uint8_t * const * in, uint8_t * const * out, const int32_t * n, int32_t * idx_out, int32_t count, uint32_t * rec, uint32_t rec_words);
 /* Tests and sweeps only: blocks per run of the batched forward BWT (1..8 where memory allows); -1 = the rule (bwt_batch_size). */
 BZIP3_API void bz3_hip_debug_set_bwt_batch(int b);
 BZIP3_API float bz3_hip_stage_last_ms(void); /* wall ms of the transform inside the last bz3_hip_stage_bwt / _unbwt call (allocations and PCIe copies excluded) */

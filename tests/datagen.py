@@ -204,12 +204,14 @@ def _fib_string(n):
 
 
 def suffix_sorter_cases():
-    """Inputs for every path of the round-3 suffix sorter (bwt.hip): groups the resolve kernel finishes in LDS (text, small
-    alphabets: counting for groups <= 64, the bitonic network above), groups of > 512 suffixes that take the big path once or
-    several times (a phrase repeated in random surroundings), lists that overflow it or repeat too deeply and fall back to rank
-    doubling (runs, periods, Fibonacci strings, a passage repeated verbatim), suffixes that end inside a window (zero-coded tails),
-    and sizes around the tile geometry (round 3's first kernel: 1536-slot anchors, 2048-slot windows; the shipped kernels: 512-slot anchor
-    tiles, groups of <= 64 to the tail list, <= 256 to the wide kernel)."""
+    """Generic inputs for the suffix sorter (bwt.hip), compared with the oracle and nothing more: text and small alphabets (groups the tail kernel
+    finishes a lane per suffix -- counting up to 12 members, a 64-lane bitonic network up to 64 -- and groups of 65 .. 256 the wide kernel takes 2 or 4
+    per lane), a phrase repeated in random surroundings (groups of more than 256 suffixes: the big list, one more 56-bit window), runs, periods,
+    Fibonacci strings and a passage repeated verbatim (the big list overflows n / 4, or the repeat outlasts the windows: rank doubling), suffixes that end
+    inside a window (zero-coded tails), and sizes around the shipped geometry: 512-slot anchor tiles, groups of <= 64 to the tail list, <= 256 to the
+    wide kernel, more to the big list.  (The 1535 .. 3073 sizes date from round 3's first kernel: 1536-slot anchors, 2048-slot windows.)
+    Which path a case takes is NOT asserted here, and some names no longer say it (`mixdeep` gives nothing up: it goes deep from depth 14 because its phrase
+    outlasts two windows).  The cases that prove where they land, from a model and the sorter's record, are tests/bwt_cases.py."""
     rng = np.random.default_rng(5)
     t = shakespeare()
     letters = lambda k: bytes(rng.integers(97, 123, size=k, dtype=np.uint8))
